@@ -6,10 +6,9 @@ import os
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# The streaming pipeline (pp_pipeline_*) and bench.py keep several kernels running side by side on their own streams; the runtime maps
-# streams onto 4 hardware queues by default, and two streams that share a queue serialise.  Read when the HIP runtime starts, so
-# it only takes effect if nothing has touched the GPU yet (set it in the environment otherwise).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# The streaming pipeline (pp_pipeline_*) keeps several kernels running side by side on their own streams; the runtime maps streams onto
+# GPU_MAX_HW_QUEUES hardware queues (read when the HIP runtime starts), and two streams that share a queue serialise.  The library leaves
+# that variable to the process's environment: pp_pipeline_create checks whether its streams run side by side and says so if they do not.
 # PP_HIP_LIB: another build of the same library (tuning experiments: tools/build_variant.py)
 LIB_PATH = os.environ.get("PP_HIP_LIB") or os.path.join(HERE, "lib", "libpphip.so")
 

@@ -578,8 +578,8 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 				" holds back streams 0x" + [&] { char b[16]; snprintf(b, sizeof b, "%x", blockedMask); return std::string(b); }() +
 				"; streams: wavefront, 4 x search, hand-over, control): the HIP runtime maps streams onto GPU_MAX_HW_QUEUES hardware "
 				"queues (default 4, fixed when the runtime starts) and a wavefront launch queued behind the persistent search grid would wait for the grid's idle "
-				"time-out.  Set GPU_MAX_HW_QUEUES=16 in the environment before the process's first HIP call (pathplanning_amd, bench.py and the tests do), or "
-				"PP_PIPE_ALLOW_SHARED_QUEUES=1 to run anyway");
+				"time-out.  Give the runtime a hardware queue per stream (GPU_MAX_HW_QUEUES in the environment before the process's first HIP call), or set "
+				"PP_PIPE_ALLOW_SHARED_QUEUES=1 to run anyway (bench.py and the tests do)");
 			return PP_ERR_INVALID;
 		}
 	}

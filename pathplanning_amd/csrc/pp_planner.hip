@@ -1256,7 +1256,7 @@ using pph::set_error;
 
 // Scratch the planner's kernels need per lane (largest private segment among them; tests/test_kernel_resources.py keeps
 // the figure honest against the built code object) and the number of hardware queues whose first dispatch may still have to
-// allocate it after this planner took its memory (bench.py runs with GPU_MAX_HW_QUEUES=16).
+// allocate it after this planner took its memory (GPU_MAX_HW_QUEUES; reserved for a process that gives the runtime up to 16).
 constexpr size_t kMaxPrivateBytes = 1024;
 constexpr size_t kReserveQueues = 16;
 
