@@ -688,7 +688,7 @@ int ppo_hybrid_search(void* hv, const double* start, const double* goal, uint64_
 	h->last = h->algo->Search(P3(start), P3(goal), seed);
 	return h->last.status;
 }
-/// info = {status, nExpanded, nPathNodes, nNodes, nStateChecks, nPathChecks, nRngDraws, nRsAttempts, nChildren, nLatticeBoundary}
+/// info = {status, nExpanded, nPathNodes, nNodes, nStateChecks, nPathChecks, nRngDraws, nRsAttempts, nChildren, nLatticeBoundary, nNegativeKStride}
 void ppo_hybrid_result_info(void* hv, int64_t* info, double* cost)
 {
 	auto* h = (HybridHandle*)hv;
@@ -703,6 +703,7 @@ void ppo_hybrid_result_info(void* hv, int64_t* info, double* cost)
 	info[7] = (int64_t)r.nRsAttempts;
 	info[8] = (int64_t)r.nChildren;
 	info[9] = (int64_t)r.nLatticeBoundary;
+	info[10] = (int64_t)r.nNegativeKStride;
 	*cost = r.cost;
 }
 void ppo_hybrid_result_expanded(void* hv, int* cells3)

@@ -164,6 +164,7 @@ struct NonHolonomicHeuristic { // heuristics.cpp:7-95
 	std::vector<double> values; // [i][j][k], k fastest, stride numAngular
 	Pose2d goal;
 	bool negativeKRead = true;
+	mutable uint64_t nNegativeKStride = 0; // reads of row j-1 through the heap-chunk stride (k <= -2, j >= 1; instrumentation, not the reference's)
 
 	static std::unique_ptr<NonHolonomicHeuristic> Build(const Pose2d& lb, const Pose2d& ub, const HybridParams& p)
 	{
@@ -220,6 +221,7 @@ struct NonHolonomicHeuristic { // heuristics.cpp:7-95
 			return d;
 		}
 		if (j >= 1) {
+			nNegativeKStride++;
 			const int stride = (int)((na * 8 + 8 + 15) / 16 * 16 / 8); // 74 for na = 73
 			int kk = stride + k;
 			if (kk >= 0 && kk < (int)na)
@@ -437,6 +439,7 @@ struct HybridResult {
 	std::vector<int> pathNodes; // node indices root..solution
 	uint64_t nStateChecks = 0, nPathChecks = 0, nRngDraws = 0, nRsAttempts = 0, nChildren = 0;
 	uint64_t nLatticeBoundary = 0; // poses discretised within 1e-9 cells of a lattice boundary (instrumentation, not the reference's)
+	uint64_t nNegativeKStride = 0; // non-holonomic table reads taken through the chunk-stride path (NonHolonomicHeuristic::Lookup)
 };
 
 struct HybridAStar {
@@ -593,6 +596,7 @@ struct HybridAStar {
 		Rng rng(seed);
 		const uint64_t sc0 = world->nStateChecks, pc0 = world->nPathChecks;
 		nLatticeBoundary = 0;
+		nonHolo->nNegativeKStride = 0;
 		goalPose = goal;
 		if (!skipObstacleUpdate)
 			obstacle->Update(goal); // hybrid_a_star.cpp:249
@@ -685,6 +689,7 @@ struct HybridAStar {
 		res.nPathChecks = world->nPathChecks - pc0;
 		res.nRngDraws = rng.draws;
 		res.nLatticeBoundary = nLatticeBoundary;
+		res.nNegativeKStride = nonHolo->nNegativeKStride;
 		return res;
 	}
 };

@@ -82,10 +82,18 @@ def params_array(**kw):
 class World:
     """The reference's StateSpaceSE2 + ObstacleListOccupancyMap + StateValidatorOccupancyMap + GVD."""
 
-    def __init__(self, half_x, half_y=None, resolution=0.1):
-        half_y = half_x if half_y is None else half_y
-        self.lb = np.array([-half_x, -half_y, -math.pi])
-        self.ub = np.array([half_x, half_y, math.pi])
+    def __init__(self, half_x=None, half_y=None, resolution=0.1, lower=None, upper=None):
+        """World(half_x, half_y, res): state bounds [-half, +half]; World(lower=, upper=, resolution=): any box (x, y or x, y, theta;
+        theta defaults to [-pi, pi]).  The grid is sized by the box's extent and centred on the local origin either way
+        (state_validator_occupancy_map.cpp:6-13, occupancy_map.cpp:6-14), so an off-centre box and its grid disagree."""
+        if lower is None:
+            assert upper is None and half_x is not None
+            half_y = half_x if half_y is None else half_y
+            lower, upper = (-half_x, -half_y), (half_x, half_y)
+        else:
+            assert upper is not None and half_x is None and half_y is None
+        self.lb = np.array([lower[0], lower[1], lower[2] if len(lower) > 2 else -math.pi], dtype=np.float64)
+        self.ub = np.array([upper[0], upper[1], upper[2] if len(upper) > 2 else math.pi], dtype=np.float64)
         self.resolution = np.float32(resolution)
         self.h = C.c_void_p(lib().ppo_world_create(dptr(self.lb), dptr(self.ub), C.c_float(resolution)))
         assert self.h
@@ -95,6 +103,8 @@ class World:
         o = np.zeros(2)
         lib().ppo_world_origin(self.h, dptr(o))
         self.origin = o
+        self.grid_lo = o.copy()  # world extent of the grid: [origin, origin + dims * res)
+        self.grid_hi = o + np.array([self.rows, self.cols]) * float(self.resolution)
         self.min_safe_radius = 1.0
         self.min_interp = 0.1
 
@@ -379,7 +389,7 @@ class Hybrid:
     def search(self, start, goal, seed=0):
         lib().ppo_hybrid_search.argtypes = [C.c_void_p, _dp, _dp, C.c_uint64]
         status = lib().ppo_hybrid_search(self.h, dptr(arr3(start)), dptr(arr3(goal)), C.c_uint64(seed))
-        info = np.zeros(10, dtype=np.int64)
+        info = np.zeros(11, dtype=np.int64)
         cost = C.c_double()
         lib().ppo_hybrid_result_info(self.h, info.ctypes.data_as(_i64p), C.byref(cost))
         ne, npth = int(info[1]), int(info[2])
@@ -398,7 +408,8 @@ class Hybrid:
         return dict(status=status, cost=cost.value, expanded=expanded, path_poses=poses, path_kind=kind, path_steering=steering,
                     path_length=length, path_direction=direction, path_rsword=rsword, path_cost=pcost, n_nodes=int(info[3]),
                     n_state_checks=int(info[4]), n_path_checks=int(info[5]), n_rng_draws=int(info[6]), n_rs_attempts=int(info[7]),
-                    n_children=int(info[8]), n_lattice_boundary_hits=int(info[9]))
+                    n_children=int(info[8]), n_lattice_boundary_hits=int(info[9]),
+                    n_negative_k_stride_reads=int(info[10]))
 
 
 SMOOTHER_DEFAULTS = dict(step_tolerance=1e-3, max_iterations=2000, learning_rate=0.01, path_weight=0.0, smooth_weight=0.4, voronoi_weight=0.02,
@@ -560,13 +571,25 @@ def neighbors(row, col, rows, cols):
     return rc[:n.value]
 
 
-def synthetic_world(n_cells, n_obstacles, seed, resolution=0.1):
-    """SURVEY 8(d) map generator: K rectangle outlines (0.3*half x 0.04*half) at seeded poses within +-0.7*half."""
-    half = n_cells * resolution / 2.0
-    w = World(half, half, resolution)
+def synthetic_world(n_cells, n_obstacles, seed, resolution=0.1, lower=None, upper=None):
+    """SURVEY 8(d) map generator: K rectangle outlines (0.3*half x 0.04*half) at seeded poses within +-0.7*half.
+    With lower / upper (state bounds, n_cells ignored): the same outlines on any box and cell size -- half is the smaller half-extent
+    of the grid, and the centres lie within 0.7 of the grid's own half-extents around its centre (the local origin), so that
+    non-square and off-centre maps get their obstacles inside the grid."""
+    if lower is None:
+        half = n_cells * resolution / 2.0
+        w = World(half, half, resolution)
+        hx = hy = half
+    else:
+        w = World(lower=lower, upper=upper, resolution=resolution)
+        hx, hy = (w.grid_hi - w.grid_lo) / 2.0
+        half = min(hx, hy)
     rng = np.random.RandomState(seed)
     for _ in range(n_obstacles):
-        x, y = rng.uniform(-0.7 * half, 0.7 * half, 2)
+        if lower is None:
+            x, y = rng.uniform(-0.7 * half, 0.7 * half, 2)
+        else:
+            x, y = rng.uniform(-0.7 * hx, 0.7 * hx), rng.uniform(-0.7 * hy, 0.7 * hy)
         th = rng.uniform(-math.pi, math.pi)
         w.add_rectangle(0.3 * half, 0.04 * half, [x, y, th])
     w.update()
