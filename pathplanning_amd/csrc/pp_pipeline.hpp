@@ -198,8 +198,6 @@ struct pp_pipeline {
 	long long wfLaunches = 0, wfGoals = 0, searchLaunches = 0;
 	ppd::MapView lastView {}; // the map view of the last submission (see pp_pipeline_submit_dev)
 	bool viewValid = false;
-	int boostAfter = 0; // PP_PIPE_BOOST_AFTER: expansions after which a query's wave runs at issue priority 3 (0 = off)
-	int soloAfter = 0, soloBacklog = 256; // PP_PIPE_SOLO_AFTER / PP_PIPE_SOLO_BACKLOG: see k_hybrid_search_rows (0 = off, the default: measured neutral, profiles/r04_solo_sweep.txt)
 	unsigned long long idleTicks = 250000ull; // idle loop passes of ~4 us: about 1 s.  (50 ms until round 4: shorter than the ~100 ms the first fields of a run take, so the
 	                                         // grid's waves left before their first work arrived and came back by the luck of the top-up launches.)  Idle waves leave at once when
 	                                         // the host has polled every result (PipeCtl::quiesce), so the time-out only matters when a producer really cannot run.
@@ -319,9 +317,6 @@ PipeView pipe_view(const pp_pipeline* P)
 	v.waveAlive = P->waveAlive;
 	v.idleTicks = P->idleTicks;
 	v.lingerTicks = P->lingerTicks;
-	v.soloAfter = P->soloAfter;
-	v.soloBacklog = P->soloBacklog;
-	v.boostAfter = P->boostAfter;
 	v.pathHost = P->pathHost;
 	v.pathHostCap = P->pathHostCap;
 	return v;
@@ -361,8 +356,8 @@ int pipe_launch_search(pp_pipeline* P)
 	pl->args.m = pl->map->view(); // validator tunables may have changed
 	const pp_pipeline::Timed tm = timed_take(P, s, 1, 0);
 	hipLaunchKernelGGL(k_hybrid_search_rows<true>, dim3((P->waves + kWg - 1) / kWg), dim3(64 * kWg), 0, s, pl->args, 0, pl->dStarts, pl->dGoals, pl->dSeeds, pl->costFields, pl->nodes, pl->heaps,
-		pl->keymaps, pl->expanded, pl->rsLogs, pl->paths, pl->mtStates, pl->results, (int*)nullptr, (SuspendRec*)nullptr, (const int32_t*)nullptr, 0, (const SuspendRec*)nullptr,
-		(const int*)nullptr, (int*)nullptr, (int*)nullptr, 0, pl->bands, pl->bandInvW, pl->bandMeta, pipe_view(P));
+		pl->keymaps, pl->expanded, pl->rsLogs, pl->paths, pl->mtStates, pl->results, (int*)nullptr, (SuspendRec*)nullptr, (const int32_t*)nullptr, 0, (int*)nullptr, (int*)nullptr,
+		pl->bands, pl->bandInvW, pl->bandMeta, pipe_view(P));
 	PP_HIP_TRY(hipGetLastError());
 	timed_done(P, s, tm);
 	P->lastLaunch = std::chrono::steady_clock::now();
@@ -416,27 +411,6 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 		if (x >= 1 && x <= kPipeWavefrontStreams)
 			P->nWf = (int)x;
 	}
-	// Experiment switch PP_PIPE_WF_CUS=n: the wavefront streams run on the first n compute units only and the search streams on the others
-	// (hipExtStreamCreateWithCUMask): no stage can take the other's LDS or registers.  0 / unset = no masks.
-	int wfCus = 0, totalCus = 0;
-	{
-		int dev = 0;
-		hipDeviceProp_t prop;
-		if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-			totalCus = prop.multiProcessorCount;
-		if (const char* v = getenv("PP_PIPE_WF_CUS")) {
-			const long x = strtol(v, nullptr, 10);
-			if (x > 0 && x < totalCus && totalCus <= 512)
-				wfCus = (int)x;
-		}
-	}
-	auto masked_stream = [&](hipStream_t* out, bool forWavefront) -> hipError_t {
-		uint32_t mask[16] = {};
-		for (int c = 0; c < totalCus; c++)
-			if ((c < wfCus) == forWavefront)
-				mask[c >> 5] |= 1u << (c & 31);
-		return hipExtStreamCreateWithCUMask(out, (uint32_t)((totalCus + 31) / 32), mask);
-	};
 	for (int i = 0; i < P->nWf && e == hipSuccess; i++) {
 		e = hipMalloc(&P->wfWorkspace[i], (size_t)pl->wfBytesPerSlot * pl->wfSlots);
 		if (const size_t qw = pph::wavefront_tiles_queue_words(pl->map->desc.rows, pl->map->desc.cols)) {
@@ -450,7 +424,7 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 			e = hipMemset(P->wfCtl[i], 0, 64);
 
 		if (e == hipSuccess)
-			e = wfCus ? masked_stream(&P->wfStream[i], true) : hipStreamCreateWithFlags(&P->wfStream[i], hipStreamNonBlocking);
+			e = hipStreamCreateWithFlags(&P->wfStream[i], hipStreamNonBlocking);
 	}
 	for (int i = 0; i < pp_pipeline::kFbSets && e == hipSuccess; i++) {
 		e = hipMalloc((void**)&P->fbCtl[i], 64);
@@ -464,19 +438,19 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 			e = hipEventCreateWithFlags(&P->fbAfterTiles[i], hipEventDisableTiming);
 	}
 	if (e == hipSuccess)
-		e = wfCus ? masked_stream(&P->fbStream, true) : hipStreamCreateWithFlags(&P->fbStream, hipStreamNonBlocking);
+		e = hipStreamCreateWithFlags(&P->fbStream, hipStreamNonBlocking);
 	// The wavefront workgroups of a launch in flight stay until its list AND the urgent ring are empty, and launches queue: room on the chip
 	// frees rarely and in bursts.  When it does, the waves that top up the search grid and the scatter kernel of a new submission should get
 	// it before the next wavefront launch's pending workgroups refill the chip: their streams have the highest priority.  A safeguard, not a
-	// measured gain: 14 driver-style runs each way give 16.8-17.4 k with it and 17.0-17.5 k without (PP_PIPE_FLAT_PRIORITY=1); one run in
-	// about forty had come in at 12 k before, consistent results, cause not established (profiles/r03_repeat_runs.txt).
+	// measured gain: 14 driver-style runs each way give 16.8-17.4 k with it and 17.0-17.5 k without; one run in about forty had come in at
+	// 12 k before, consistent results, cause not established (profiles/r03_repeat_runs.txt).
 	int prioLow = 0, prioHigh = 0;
 	(void)hipDeviceGetStreamPriorityRange(&prioLow, &prioHigh);
-	const bool flatPriority = getenv("PP_PIPE_FLAT_PRIORITY") != nullptr || prioHigh == prioLow;
+	const bool flatPriority = prioHigh == prioLow; // a device with an empty priority range: equal priorities
 	if (flatPriority)
-		prioHigh = prioLow = 0;
+		prioHigh = 0;
 	for (int i = 0; i < kPipeSearchStreams && e == hipSuccess; i++)
-		e = wfCus ? masked_stream(&P->searchStream[i], false) : hipStreamCreateWithPriority(&P->searchStream[i], hipStreamNonBlocking, prioHigh);
+		e = hipStreamCreateWithPriority(&P->searchStream[i], hipStreamNonBlocking, prioHigh);
 	if (e == hipSuccess)
 		e = hipStreamCreateWithPriority(&P->ctlStream, hipStreamNonBlocking, prioHigh);
 	if (e == hipSuccess)
@@ -606,18 +580,6 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 		if (v && *v) {
 			const long ms = strtol(v, nullptr, 10);
 			P->idleTicks = (unsigned long long)(ms < 1 ? 1 : (ms > 10000 ? 10000 : ms)) * 250ull;
-		}
-		if (const char* ba = getenv("PP_PIPE_BOOST_AFTER")) {
-			const long x = strtol(ba, nullptr, 10);
-			P->boostAfter = x < 0 ? 0 : (x > 0x7FFFFFFF ? 0x7FFFFFFF : (int)x);
-		}
-		if (const char* sa = getenv("PP_PIPE_SOLO_AFTER")) {
-			const long x = strtol(sa, nullptr, 10);
-			P->soloAfter = x < 0 ? 0 : (x > 0x7FFFFFFF ? 0x7FFFFFFF : (int)x);
-		}
-		if (const char* sb = getenv("PP_PIPE_SOLO_BACKLOG")) {
-			const long x = strtol(sb, nullptr, 10);
-			P->soloBacklog = x < 0 ? 0 : (x > 0x7FFFFFFF ? 0x7FFFFFFF : (int)x);
 		}
 		P->lingerTicks = P->idleTicks; // idle waves stay until the idle time-out or until the host has polled everything (see k_hybrid_search_rows)
 		if (const char* lg = getenv("PP_PIPE_LINGER_MS")) {

@@ -115,13 +115,11 @@ struct SearchArgs {
 	float rsRev, rsFwd, rsSw; // Reeds-Shepp cost weights as floats (reeds_shepp.cpp:654)
 	int maxNodes;
 	int maxPath; // PathRec entries per query
-	int suspendAfter;  // rows kernel, first pass: expansions after which a query is set aside for the second pass (0 = never)
-	int suspendAfter2; // second pass (rows kernel over the set-aside queries): expansions after which the one-query kernel takes over
+	int suspendAfter;  // rows kernel: expansions after which a query is set aside for the one-query kernel (0 = never)
 	int extraSlots;    // buffer slots beyond the rows' own, taken by rows whose query was set aside
 	int searchRows;    // rows the planner's buffers were sized for (spare slots start here)
 	int listCap;       // capacity of each SuspendRec list: one record per spare slot + one per row
 	int rowsWaves;     // rows kernel: waves of this launch (the grid is rounded up to whole workgroups)
-	int directCount;   // rows kernel: the first `directCount` queries of the hand-out order are not its own (they run one per wave)
 	size_t cells;
 	int64_t fieldElems; // floats per query in costFields (8 x 8-tiled obstacle-heuristic field)
 	GuardRec* guardLog; // [queries][kGuardLogCap], nullptr: no log (throughput planners)
@@ -133,18 +131,6 @@ struct DevResult {
 	int32_t solutionNode;
 	int32_t nRsLog;
 };
-
-#ifndef PP_SEARCH_FIELD_PREFETCH
-#define PP_SEARCH_FIELD_PREFETCH 0 // (experiment, measured neutral to harmful) one-query kernel: touch the children's heuristic-field lines
-                                   // as soon as the parent pose is known.  The child phase's wait went 10.0 k -> 9.8 k cycles, the added code cost
-                                   // 1.4 k: the wait is the slowest of five independent gathers (key map, field, table, distance, path cost)
-#endif
-#ifndef PP_SEARCH_DIST_WINDOW
-#define PP_SEARCH_DIST_WINDOW 0 // (experiment, measured harmful) one-query kernel: LDS window of the distance grid around the expanded
-                                // node (pp_device.hpp: DistWindow), filled by LDS-DMA at the pop.  Same results; the marches' distance reads
-                                // hit L2 / MALL and were already hidden under the heuristic-field gathers (HBM misses), so the window only
-                                // adds its 18 load instructions: 25.7 k -> 29 k cycles per expansion (tools/diag_search.py, PP_SEARCH_ROWS=0)
-#endif
 
 constexpr uint32_t kExplored = 0xFFFFFFFFu;
 constexpr uint32_t kNoKey = 0xFFFFFFFFu;
@@ -163,12 +149,8 @@ __device__ __forceinline__ void wave_lds_sync()
 /// waits until this wave's global stores are visible to its other lanes' loads
 __device__ __forceinline__ void wave_vmem_sync()
 {
-#if PP_WAVE_SYNC_DRAIN
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
 	__builtin_amdgcn_s_waitcnt(0);
-#else
-	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#endif
 	__builtin_amdgcn_wave_barrier();
 }
 
@@ -233,18 +215,15 @@ __global__ void __launch_bounds__(64, PP_SEARCH_WAVES_PER_SIMD) k_hybrid_search(
 	const uint64_t* __restrict__ seeds, const float* __restrict__ costFields, Node* __restrict__ nodesBase, HeapEntry* __restrict__ heapBase,
 	uint32_t* __restrict__ keymapBase, uint32_t* __restrict__ expandedBase, RsLogEntry* __restrict__ rsLogBase, PathRec* __restrict__ pathBase,
 	DevResult* __restrict__ results, unsigned long long* __restrict__ prof, const SuspendRec* __restrict__ resume, const int* __restrict__ nResume,
-	const unsigned long long* __restrict__ mtBase, HeapEntry* __restrict__ bandBase, double bandInvW, uint8_t* __restrict__ bandMetaBase,
-	const int32_t* __restrict__ queryList, int slotBase)
+	const unsigned long long* __restrict__ mtBase, HeapEntry* __restrict__ bandBase, double bandInvW, uint8_t* __restrict__ bandMetaBase)
 {
-	// Three uses: (a) one block per query of the batch, buffers indexed by the query (resume == nullptr, queryList == nullptr);
-	// (b) continuation of the queries the rows kernel suspended: one block per SuspendRec, buffers indexed by its slot;
-	// (c) the probable longest queries of a batch the rows kernel works on: block i takes query queryList[i] and buffer slot
-	// slotBase + i (nQueries = length of the list).
+	// Two uses: (a) one block per query of the batch, buffers indexed by the query (resume == nullptr);
+	// (b) continuation of the queries the rows kernel suspended: one block per SuspendRec, buffers indexed by its slot.
 	if (resume ? ((int)blockIdx.x >= *nResume || (int)blockIdx.x >= A.listCap) : (int)blockIdx.x >= nQueries)
 		return;
 	const SuspendRec rec = resume ? resume[blockIdx.x] : SuspendRec {};
-	const int q = resume ? rec.q : (queryList ? queryList[blockIdx.x] : (int)blockIdx.x);
-	const size_t slot = resume ? (size_t)rec.slot : (queryList ? (size_t)slotBase + blockIdx.x : (size_t)q);
+	const int q = resume ? rec.q : (int)blockIdx.x;
+	const size_t slot = resume ? (size_t)rec.slot : (size_t)q;
 	const int lane = threadIdx.x;
 #if PP_SEARCH_SETPRIO
 	__builtin_amdgcn_s_setprio(3); // see k_hybrid_search_rows
@@ -270,9 +249,6 @@ __global__ void __launch_bounds__(64, PP_SEARCH_WAVES_PER_SIMD) k_hybrid_search(
 	__shared__ int16_t c_action[kSlots];
 	__shared__ int s_rsChecks;
 	__shared__ double s_rsPre[24]; // rs::Path::make_prefix of the Reeds-Shepp attempt (23 doubles)
-#if PP_SEARCH_DIST_WINDOW
-	__shared__ __attribute__((aligned(16))) float s_win[kDistWinElems]; // obstacle distances around the expanded node (pp_device.hpp: DistWindow)
-#endif
 	__shared__ HeapEntry s_spill[16]; // entries that left the front buffer during this expansion
 	__shared__ uint8_t s_bandCnt[kBands]; // f-bands of the open list (pp_search_device.hpp): entries per ring slot
 
@@ -491,12 +467,8 @@ __global__ void __launch_bounds__(64, PP_SEARCH_WAVES_PER_SIMD) k_hybrid_search(
 			const int cntSl = s_bandCnt[sl];
 			const bool mineBand = cntSl > 0 && bn >= bandLo && bn < bandLo + kBands;
 			const bool have = mineBand && (lane & 15) < cntSl;
-#if PP_WAVE_SYNC_DRAIN
 			__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
 			__builtin_amdgcn_s_waitcnt(0); // lane 0's band stores
-#else
-			__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#endif
 			HeapEntry e;
 			e.ckey = ~0ull;
 			e.nseq = ~0u;
@@ -606,28 +578,6 @@ __global__ void __launch_bounds__(64, PP_SEARCH_WAVES_PER_SIMD) k_hybrid_search(
 				pDist0 = nd.dist0;
 			}
 		}
-#if PP_SEARCH_FIELD_PREFETCH
-		// The obstacle-heuristic value of a child is a gather from this query's own 4 MB field: an HBM miss every time (17 GB of
-		// fields per planner), and the child phase waits for it.  Its cell is known to within float rounding as soon as the parent
-		// pose is: touch that cache line now (fast float sin / cos: the value is discarded, only the line matters); the exact look-up
-		// two phases later finds it in L2 or on its way.
-		float prefetched = 0.0f;
-		if (lane < P) {
-			const double kap = A.prims.kappa[lane];
-			const double d = A.prims.backward[lane] ? -A.rp.arcLength : A.rp.arcLength;
-			double ax = px + d * pCos, ay = py + d * pSin;
-			if (fabs(kap) > 1e-9) {
-				const float tf = (float)(pt + d * kap);
-				const double ik = A.prims.invKappa[lane];
-				ax = px + ik * ((double)__sinf(tf) - pSin);
-				ay = py + ik * (pCos - (double)__cosf(tf));
-			}
-			int row, col;
-			world_to_cell(m, ax, ay, row, col);
-			if (inside_map(m, row, col))
-				prefetched = field[field_tiled_index(m.cols, row, col)];
-		}
-#endif
 		wave_lds_sync(); // staging is about to be overwritten
 		if (pDead)
 			continue; // entry of a node replaced by ProcessPossibleShortcut
@@ -638,38 +588,6 @@ __global__ void __launch_bounds__(64, PP_SEARCH_WAVES_PER_SIMD) k_hybrid_search(
 			solutionCost = pPathCost;
 			break;
 		}
-#if PP_SEARCH_DIST_WINDOW
-		// the children's marches read the distance grid within 1.5 m of this pose: fetch that window into LDS now (LDS-DMA: no
-		// registers, one round trip, lands while the heuristic and the child end points are computed)
-		DistWindow dwin;
-		{
-			int prow, pcol;
-			world_to_cell(m, ppose.x, ppose.y, prow, pcol);
-			prow = min(max(prow, 0), m.rows - 1); // (a popped node is a valid state, i.e. inside the map)
-			pcol = min(max(pcol, 0), m.cols - 1);
-			const uint32_t winLds = (uint32_t)(uintptr_t)s_win; // low half of the generic address = the LDS byte address
-			dwin.win = (LdsFloatPtr)(uintptr_t)winLds;
-			dwin.r0 = prow - kDistWinHalf;
-			dwin.c0 = pcol - kDistWinHalf;
-			// element e = k * 64 + lane of the window is cell (e / kDistWin, e % kDistWin); stepping e by 64 = one row + 31 columns
-			int wr = lane / kDistWin, wc = lane - wr * kDistWin;
-#pragma unroll 1
-			for (int k = 0; k < kDistWinElems / 64; k++) {
-				// cells beyond the map edge are never asked for (is_state_valid tests the map first): any in-range address serves
-				const int gr = min(max(dwin.r0 + wr, 0), m.rows - 1), gc = min(max(dwin.c0 + wc, 0), m.cols - 1);
-				// (the LDS address goes through an integer: the folded generic -> LDS cast of a constant address trips the gfx950 backend,
-				// "Illegal instruction: V_CMP_NE_U32 0, src_shared_base")
-				__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(m.dist + (size_t)gr * m.cols + gc),
-					(__attribute__((address_space(3))) void*)(uintptr_t)(winLds + (uint32_t)(k * 64 * sizeof(float))), 4, 0, 0);
-				wr += 1;
-				wc += 64 - kDistWin;
-				if (wc >= kDistWin) {
-					wc -= kDistWin;
-					wr += 1;
-				}
-			}
-		}
-#endif
 		// ---- Expand, a_star.h:377-409
 		if (lane == 0) {
 			if (pKey != kNoKey)
@@ -728,19 +646,10 @@ __global__ void __launch_bounds__(64, PP_SEARCH_WAVES_PER_SIMD) k_hybrid_search(
 				// validity / distance of the child's own pose: the first march sample of ITS children (not a counted check)
 				float cd0;
 				const bool cIn = is_state_valid_issue(m, child.x, child.y, child.t, cd0);
-#if PP_SEARCH_DIST_WINDOW
-				__builtin_amdgcn_s_waitcnt(0); // the window has landed (issued a phase ago) -- and so have the look-ups just issued
-				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-				const bool pathValid = is_path_valid_from(m, dwin, a, a.init, pDist0, lastValidRatio, checks);
-#else
 				const bool pathValid = is_path_valid_from(m, a, a.init, pDist0, lastValidRatio, checks);
-#endif
 				PP_STAMP(PH_DUP); // [diagnostic: look-up issue + validity march]
 				// the values the look-ups above fetched (loaded under the march)
 				hh = combined_heuristic_finish(A.heur, hl);
-#if PP_SEARCH_FIELD_PREFETCH
-				asm volatile("" : : "v"(prefetched)); // keeps the touch above alive; it arrived before the look-up it served
-#endif
 				const double voroFull = voronoi_cost_finish(voroRaw, A.rp.voroDiagRes, A.rp.voronoiMult);
 				d0 = is_state_valid_finish(m, cIn, cd0) ? cd0 : -1.0f;
 				if (!pathValid) {
@@ -1179,9 +1088,6 @@ struct PipeView {
 	double* pathHost = nullptr;       // pinned host memory, [capacity][pathHostCap][3]: the solution path's poses, goal first (write_path)
 	int pathHostCap = 0;
 	unsigned long long idleTicks = 0; // loop passes (~4 us each: a sleep and three polls) a wave waits without work before it leaves on its own
-	int soloAfter = 0;                // > 0: a wave one of whose rows has passed this many expansions takes no new queries while the ready ring holds fewer than soloBacklog
-	int soloBacklog = 0;
-	int boostAfter = 0;               // > 0: a wave one of whose rows has passed this many expansions runs at issue priority 3 (the run's longest chains share their SIMDs with throughput work)
 };
 
 #include "pp_planner_rows.hpp"
@@ -1216,8 +1122,8 @@ struct pp_planner {
 	unsigned long long* prof = nullptr; // diagnostic phase cycles, [maxBatch][PH_COUNT]
 	bool profile = false;
 	unsigned long long* mtStates = nullptr; // [searchRows][312] mt19937_64 engine state per row (rows kernel)
-	int* nextQuery = nullptr;               // = wfError + 2: {query counter of the persistent rows kernel, spare slots handed out}
-	SuspendRec* suspended = nullptr;        // [2][extraSlots] queries set aside by the first / second pass of the rows kernel
+	int* nextQuery = nullptr;               // = wfError + 2: {query counter of the persistent rows kernel, set-aside count}
+	SuspendRec* suspended = nullptr;        // [listCap] queries set aside by the rows kernel
 	int32_t* order = nullptr;               // [maxBatch] query indices, probable longest first (rows kernel)
 	float* orderKeys = nullptr;             // [maxBatch] field value at each query's start pose (the sort key)
 	HeapEntry* bands = nullptr;             // [slots][kBands * kBandCap] f-bands of the open list
@@ -1226,7 +1132,6 @@ struct pp_planner {
 	int searchWaves = 0;                    // resident waves of k_hybrid_search_rows on this device
 	int searchRows = 0;                     // rows (= search buffer slots) this planner runs with
 	bool rowsKernel = false;                // four-queries-per-wave kernel (throughput) vs one query per wave (latency)
-	int compactBelow = 0;                   // first pass: a wave with an empty queue and <= this many busy rows re-queues them
 	GuardRec* guardLog = nullptr;           // [maxBatch][kGuardLogCap] lattice-line children (one-query-per-wave planners only)
 	int* guardCount = nullptr;              // [maxBatch]
 	PathRec* paths = nullptr;               // [maxBatch][maxPath] solution paths, goal first
@@ -1235,10 +1140,6 @@ struct pp_planner {
 	uint64_t* dSeeds = nullptr;
 	hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
 	hipEvent_t startAfter = nullptr; // one-shot: the next batch waits for this event (pp_planner_start_after_fields_of)
-	// the probable longest queries of a batch run one per wave next to the rows kernel (PP_SEARCH_DIRECT), on their own stream
-	hipStream_t directStream = nullptr;
-	hipEvent_t e3 = nullptr;
-	int directCount = 0;
 	float wavefrontMs = 0, searchMs = 0;
 	int lastBatch = 0;
 	pp_pipeline* owner = nullptr; // (set with pipelineOwned)
@@ -1278,14 +1179,14 @@ int warm_up_kernels(pp_planner* p, pp_map* map)
 		none.listCap = 0;
 		hipLaunchKernelGGL(k_hybrid_search_rows<false>, dim3(1), dim3(64 * PP_ROWS_WAVES_PER_WG), 0, s, none, 0, (const double*)nullptr, (const double*)nullptr, (const uint64_t*)nullptr,
 			(const float*)nullptr, (Node*)nullptr, (HeapEntry*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (RsLogEntry*)nullptr, (PathRec*)nullptr, (unsigned long long*)nullptr,
-			(DevResult*)nullptr, (int*)nullptr, (SuspendRec*)nullptr, (const int32_t*)nullptr, 0, (const SuspendRec*)nullptr, (const int*)nullptr, (int*)nullptr, (int*)nullptr, 0,
-			(HeapEntry*)nullptr, 0.0, (uint8_t*)nullptr, PipeView {});
+			(DevResult*)nullptr, (int*)nullptr, (SuspendRec*)nullptr, (const int32_t*)nullptr, 0, (int*)nullptr, (int*)nullptr, (HeapEntry*)nullptr, 0.0, (uint8_t*)nullptr,
+			PipeView {});
 		e = hipGetLastError();
 	}
 	if (e == hipSuccess) {
 		hipLaunchKernelGGL(k_hybrid_search<false>, dim3(1), dim3(64), 0, s, p->args, 0, (const double*)nullptr, (const double*)nullptr, (const uint64_t*)nullptr, (const float*)nullptr,
 			(Node*)nullptr, (HeapEntry*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (RsLogEntry*)nullptr, (PathRec*)nullptr, (DevResult*)nullptr, (unsigned long long*)nullptr,
-			(const SuspendRec*)nullptr, (const int*)nullptr, (const unsigned long long*)nullptr, (HeapEntry*)nullptr, 0.0, (uint8_t*)nullptr, (const int32_t*)nullptr, 0);
+			(const SuspendRec*)nullptr, (const int*)nullptr, (const unsigned long long*)nullptr, (HeapEntry*)nullptr, 0.0, (uint8_t*)nullptr);
 		e = hipGetLastError();
 	}
 	if (e == hipSuccess) {
@@ -1355,10 +1256,6 @@ void free_planner(pp_planner* p)
 	for (void* q : ptrs)
 		if (q)
 			(void)hipFree(q);
-	if (p->directStream)
-		(void)hipStreamDestroy(p->directStream);
-	if (p->e3)
-		(void)hipEventDestroy(p->e3);
 	if (p->e0)
 		(void)hipEventDestroy(p->e0);
 	if (p->e1)
@@ -1513,9 +1410,8 @@ static int create_planner(pp_map* map, const pp_hybrid_params* params, int32_t m
 		// `suspendAfter` expansions are set aside by the rows kernel (open list flushed into the heap, scalars in a
 		// SuspendRec, the row goes on in a spare slot) and finished one query per wave, 14 instead of ~25 us per expansion.
 		// Only the extreme tail moves: per expansion the rows kernel is the cheaper one and the GPU is capacity-bound with
-		// eight batches in flight (measured: 32768 -> 10.2 k plans/s, 8192 -> 8.0 k, never -> 9.8 k).  Optionally a second
-		// pass of the rows kernel continues the set-aside queries up to `suspendAfter2` first (PP_SEARCH_SUSPEND_AFTER2;
-		// measured no better: 8192 / 32768 -> 7.6 k, 12288 / 32768 -> 10.1 k).  PP_SEARCH_SUSPEND_AFTER=0: no hand-over.
+		// eight batches in flight (measured: 32768 -> 10.2 k plans/s, 8192 -> 8.0 k, never -> 9.8 k).  PP_SEARCH_SUSPEND_AFTER=0:
+		// no hand-over.
 		// tuning knobs from the environment are clamped to their meaningful ranges: none of them may change results or
 		// make an allocation size negative
 		auto env_int = [](const char* name, int dflt, int lo, int hi) {
@@ -1526,22 +1422,9 @@ static int create_planner(pp_map* map, const pp_hybrid_params* params, int32_t m
 			return (int)(x < lo ? lo : (x > hi ? hi : x));
 		};
 		A.suspendAfter = p->rowsKernel && !forPipeline ? env_int("PP_SEARCH_SUSPEND_AFTER", 32768, 0, 1 << 30) : 0; // (a pipeline's rows keep their queries)
-		A.suspendAfter2 = env_int("PP_SEARCH_SUSPEND_AFTER2", 0, 0, 1 << 30);
 		A.extraSlots = A.suspendAfter > 0 ? env_int("PP_SEARCH_EXTRA_SLOTS", (max_batch + 15) / 16, 0, max_batch) : 0; // queries that may be set aside (the rest stays)
 		A.searchRows = p->searchRows;
 		A.listCap = A.extraSlots + p->searchRows;
-		// A batch lasts as long as its longest query, and a query is a chain of dependent expansions: it runs faster alone in
-		// a wave (k_hybrid_search: ~11 us per expansion) than as one of four (rows kernel: 15-20 us).  The wavefront kernel
-		// already ranks the queries by probable length for the hand-out order; the first PP_SEARCH_DIRECT of that order get
-		// a wave of their own, in slots behind the spare ones.
-		p->directCount = p->rowsKernel && !forPipeline ? env_int("PP_SEARCH_DIRECT", 0, 0, max_batch / 2) : 0;
-		A.directCount = 0; // set per call (only when the order is available)
-		// compaction (pp_planner_rows.hpp): waves whose queue is empty and that have at most this many busy rows re-queue
-		// their queries for a second pass that packs them four per wave.  Off by default: it issues fewer instructions
-		// (a wave costs the same with one busy row as with four) but the passes of one batch run one after the other, and
-		// with eight batches in flight the longer per-batch latency costs more than the saved issue slots
-		// (measured: 8.1 k plans/s with PP_SEARCH_COMPACT=2 against 10.9 k without).
-		p->compactBelow = p->rowsKernel && !forPipeline ? env_int("PP_SEARCH_COMPACT", 0, 0, kRowsPerWave) : 0;
 	}
 	hipError_t e = hipSuccess;
 	// Headroom.  The kernels this planner launches need scratch (private segment: k_hybrid_search_rows 408 B, k_wavefront
@@ -1563,11 +1446,11 @@ static int create_planner(pp_map* map, const pp_hybrid_params* params, int32_t m
 	alloc((void**)&p->wfWorkspace, (size_t)p->wfBytesPerSlot * p->wfSlots);
 	alloc((void**)&p->tilesCtl, 64);
 	alloc((void**)&p->tilesFallback, B * 4);
-	alloc((void**)&p->wfError, 32); // control block: {wavefront error flag, wavefront goal counter, pass-1 query counter, pass-1 set-aside count,
-	                                // pass-2 record counter, pass-2 set-aside count}
+	alloc((void**)&p->wfError, 32); // control block: {wavefront error flag, wavefront goal counter, rows query counter, set-aside count, (unused),
+	                                // (unused), wavefront done counter, spare slots handed out}
 	// search buffers: one set per resident row (rows kernel) or per query (one-query-per-wave kernel)
-	const size_t S = p->rowsKernel ? (size_t)p->searchRows + (size_t)A.extraSlots + (size_t)p->directCount : B;
-	alloc((void**)&p->suspended, 2 * (size_t)(A.listCap > 0 ? A.listCap : 1) * sizeof(SuspendRec));
+	const size_t S = p->rowsKernel ? (size_t)p->searchRows + (size_t)A.extraSlots : B;
+	alloc((void**)&p->suspended, (size_t)(A.listCap > 0 ? A.listCap : 1) * sizeof(SuspendRec));
 	alloc((void**)&p->mtStates, (p->rowsKernel ? S : 1) * Mt64::N * sizeof(unsigned long long));
 	alloc((void**)&p->nodes, S * N * sizeof(Node));
 	alloc((void**)&p->bands, S * (size_t)(kBands * kBandCap) * sizeof(HeapEntry));
@@ -1621,10 +1504,6 @@ static int create_planner(pp_map* map, const pp_hybrid_params* params, int32_t m
 		e = hipEventCreate(&p->e1);
 	if (e == hipSuccess)
 		e = hipEventCreate(&p->e2);
-	if (e == hipSuccess && p->directCount > 0)
-		e = hipEventCreateWithFlags(&p->e3, hipEventDisableTiming);
-	if (e == hipSuccess && p->directCount > 0)
-		e = hipStreamCreateWithFlags(&p->directStream, hipStreamNonBlocking);
 	if (e != hipSuccess) {
 		free_planner(p);
 		return pph::hip_fail(e, "planner allocation");
@@ -1765,59 +1644,32 @@ int pp_planner_search_batch_dev(pp_planner* planner, int32_t n_queries, const do
 			planner->wfError + 6, planner->orderKeys, pub));
 	}
 	PP_HIP_TRY(hipEventRecord(planner->e1, s));
-	const int nDirect = ordered && planner->directCount > 0 && dbgSkip != 2 ? (planner->directCount < n_queries / 2 ? planner->directCount : n_queries / 2) : 0;
-	planner->args.directCount = nDirect;
-	if (nDirect > 0) {
-		hipStream_t const ds = planner->directStream;
-		PP_HIP_TRY(hipStreamWaitEvent(ds, planner->e1, 0));
-		hipLaunchKernelGGL(k_hybrid_search<false>, dim3(nDirect), dim3(64), 0, ds, planner->args, nDirect, starts_dev, goals_dev, seeds_dev, planner->costFields, planner->nodes,
-			planner->heaps, planner->keymaps, planner->expanded, planner->rsLogs, planner->paths, planner->results, planner->prof, nullptr, nullptr, nullptr, planner->bands,
-			planner->bandInvW, planner->bandMeta, planner->order, planner->searchRows + planner->args.extraSlots);
-		PP_HIP_TRY(hipGetLastError());
-		PP_HIP_TRY(hipEventRecord(planner->e3, ds));
-	}
 	if (dbgSkip == 2) {
 	} else if (planner->rowsKernel) {
 		// four queries per wave, taken from a counter by a persistent grid (pp_planner_rows.hpp)
 		const int wavesWanted = (n_queries + kRowsPerWave - 1) / kRowsPerWave;
 		const int wavesMax = planner->searchRows / kRowsPerWave;
 		const int grid = wavesWanted < wavesMax ? wavesWanted : wavesMax;
-		int* const ctl = planner->nextQuery; // {pass-1 query counter, list-1 count, pass-2 record counter, list-2 count, (wavefront), spare slots}
+		int* const ctl = planner->nextQuery; // {query counter, set-aside count}
 		int* const spare = planner->wfError + 7;
-		SuspendRec* const list1 = planner->suspended;
-		SuspendRec* const list2 = planner->suspended + planner->args.listCap;
-		const int cap1 = planner->args.suspendAfter, cap2 = planner->args.suspendAfter2, cpt = planner->compactBelow;
+		const int cap = planner->args.suspendAfter;
 		constexpr int kWg = PP_ROWS_WAVES_PER_WG;
 		planner->args.rowsWaves = grid;
 		hipLaunchKernelGGL(k_hybrid_search_rows<false>, dim3((grid + kWg - 1) / kWg), dim3(64 * kWg), 0, s, planner->args, n_queries, starts_dev, goals_dev, seeds_dev, planner->costFields, planner->nodes,
-			planner->heaps, planner->keymaps, planner->expanded, planner->rsLogs, planner->paths, planner->mtStates, planner->results, ctl, list1,
-			ordered ? planner->order : nullptr, cap1, nullptr, nullptr, ctl + 1, spare, cpt, planner->bands, planner->bandInvW, planner->bandMeta, PipeView {});
+			planner->heaps, planner->keymaps, planner->expanded, planner->rsLogs, planner->paths, planner->mtStates, planner->results, ctl, planner->suspended,
+			ordered ? planner->order : nullptr, cap, ctl + 1, spare, planner->bands, planner->bandInvW, planner->bandMeta, PipeView {});
 		PP_HIP_TRY(hipGetLastError());
-		const bool secondPass = cpt > 0 || (cap1 > 0 && cap2 > cap1);
-		if (secondPass) {
-			// second pass of the rows kernel over list 1 (its length is read on the device); it ends waves with a single
-			// busy row, and the one-query-per-wave kernel finishes those
-			const int waves2 = (planner->args.listCap + kRowsPerWave - 1) / kRowsPerWave;
-			planner->args.rowsWaves = waves2 < wavesMax ? waves2 : wavesMax;
-			hipLaunchKernelGGL(k_hybrid_search_rows<false>, dim3((planner->args.rowsWaves + kWg - 1) / kWg), dim3(64 * kWg), 0, s, planner->args, n_queries, starts_dev, goals_dev, seeds_dev,
-				planner->costFields, planner->nodes, planner->heaps, planner->keymaps, planner->expanded, planner->rsLogs, planner->paths, planner->mtStates,
-				planner->results, ctl + 2, list2, nullptr, cap2 > cap1 ? cap2 : 0, list1, ctl + 1, ctl + 3, spare, cpt > 0 ? 1 : 0, planner->bands, planner->bandInvW,
-				planner->bandMeta, PipeView {});
-			PP_HIP_TRY(hipGetLastError());
-		}
-		if ((secondPass || cap1 > 0) && dbgSkip != 3) // whatever is still set aside: one wave per query (the block count is read on the device)
+		if (cap > 0 && dbgSkip != 3) // whatever was set aside: one wave per query (the block count is read on the device)
 			hipLaunchKernelGGL(k_hybrid_search<false>, dim3(planner->args.listCap), dim3(64), 0, s, planner->args, n_queries, starts_dev, goals_dev, seeds_dev,
 				planner->costFields, planner->nodes, planner->heaps, planner->keymaps, planner->expanded, planner->rsLogs, planner->paths, planner->results, planner->prof,
-				secondPass ? list2 : list1, secondPass ? ctl + 3 : ctl + 1, planner->mtStates, planner->bands, planner->bandInvW, planner->bandMeta, nullptr, 0);
+				planner->suspended, ctl + 1, planner->mtStates, planner->bands, planner->bandInvW, planner->bandMeta);
 	} else if (planner->profile)
 		hipLaunchKernelGGL(k_hybrid_search<true>, dim3(n_queries), dim3(64), 0, s, planner->args, n_queries, starts_dev, goals_dev, seeds_dev, planner->costFields,
-			planner->nodes, planner->heaps, planner->keymaps, planner->expanded, planner->rsLogs, planner->paths, planner->results, planner->prof, nullptr, nullptr, nullptr, planner->bands, planner->bandInvW, planner->bandMeta, nullptr, 0);
+			planner->nodes, planner->heaps, planner->keymaps, planner->expanded, planner->rsLogs, planner->paths, planner->results, planner->prof, nullptr, nullptr, nullptr, planner->bands, planner->bandInvW, planner->bandMeta);
 	else
 		hipLaunchKernelGGL(k_hybrid_search<false>, dim3(n_queries), dim3(64), 0, s, planner->args, n_queries, starts_dev, goals_dev, seeds_dev, planner->costFields,
-			planner->nodes, planner->heaps, planner->keymaps, planner->expanded, planner->rsLogs, planner->paths, planner->results, planner->prof, nullptr, nullptr, nullptr, planner->bands, planner->bandInvW, planner->bandMeta, nullptr, 0);
+			planner->nodes, planner->heaps, planner->keymaps, planner->expanded, planner->rsLogs, planner->paths, planner->results, planner->prof, nullptr, nullptr, nullptr, planner->bands, planner->bandInvW, planner->bandMeta);
 	PP_HIP_TRY(hipGetLastError());
-	if (nDirect > 0)
-		PP_HIP_TRY(hipStreamWaitEvent(s, planner->e3, 0)); // before e2: the search time covers both kernels
 	PP_HIP_TRY(hipEventRecord(planner->e2, s));
 	planner->lastBatch = n_queries;
 	return PP_OK;

@@ -47,15 +47,13 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 	const double* __restrict__ goals, const uint64_t* __restrict__ seeds, const float* __restrict__ costFields, Node* __restrict__ nodesBase,
 	HeapEntry* __restrict__ heapBase, uint32_t* __restrict__ keymapBase, uint32_t* __restrict__ expandedBase, RsLogEntry* __restrict__ rsLogBase,
 	PathRec* __restrict__ pathBase, unsigned long long* __restrict__ mtBase, DevResult* __restrict__ results, int* __restrict__ nextQuery,
-	SuspendRec* __restrict__ suspended, const int32_t* __restrict__ order, int suspendAfter, const SuspendRec* __restrict__ resumeList,
-	const int* __restrict__ nResumeDev, int* __restrict__ suspendedCount, int* __restrict__ spareCount, int compactBelow, HeapEntry* __restrict__ bandBase, double bandInvW,
-	uint8_t* __restrict__ bandMetaBase, PipeView pipe)
+	SuspendRec* __restrict__ suspended, const int32_t* __restrict__ order, int suspendAfter, int* __restrict__ suspendedCount, int* __restrict__ spareCount,
+	HeapEntry* __restrict__ bandBase, double bandInvW, uint8_t* __restrict__ bandMetaBase, PipeView pipe)
 {
-	// Two uses.  (a) resumeList == nullptr: the rows take the batch's queries (nextQuery[0] counts them, order[] gives the
-	// hand-out order); a query that reaches `suspendAfter` expansions is written to suspended[] and its row continues in a
-	// spare slot (suspendedCount counts both).  (b) resumeList != nullptr: the rows take the records of that list
-	// (*nResumeDev of them) and continue those queries in the records' own slots; one that reaches `suspendAfter` is written
-	// to suspended[] again (for the one-query-per-wave kernel).
+	// Two forms.  (a) Batch (kPiped = false): the rows take the batch's queries (nextQuery[0] counts them, order[] gives the
+	// hand-out order); a query that reaches `suspendAfter` expansions is written to suspended[] (suspendedCount counts the
+	// records) for the one-query-per-wave kernel to finish, and its row continues with the next query in a spare slot
+	// (spareCount hands them out; when none is left the query stays in its row).  (b) Pipeline (kPiped = true): see below.
 #if PP_SEARCH_SETPRIO
 	// the searches are chains of dependent steps (a batch lasts as long as its longest query), the wavefront kernels they share
 	// the SIMDs with are throughput work: search waves issue first
@@ -79,7 +77,7 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 	// search buffers (node records, heap, key map, engine state) belong to the ROW, not to the query: the row's
 	// queries use them one after the other, so a planner needs them for its resident rows only
 	// (a row that hands its query over to the one-query-per-wave kernel leaves the slot to it and takes a spare one)
-	// Third use (c), pipe.ctl != nullptr: the grid is the consumer of a streaming pipeline (pp_pipeline.hpp).  Rows take FIELD SLOTS from
+	// Pipeline form (b), pipe.ctl != nullptr: the grid is the consumer of a streaming pipeline (pp_pipeline.hpp).  Rows take FIELD SLOTS from
 	// the ready ring the wavefront kernel appends to (`q` below is then the slot: start / goal / seed, field, path and log buffers are
 	// all indexed by it), announce results in a ring in host memory, and the wave leaves when nothing is left to claim; launches
 	// only top the grid up -- a wave whose index is still owned by a wave of an earlier launch leaves at once.
@@ -93,7 +91,6 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); // the previous owner's last stores to the rows' buffers
 	}
 	int idleIters = 0; // (wave-uniform) consecutive loop passes with every row idle
-	bool boosted = false; // (wave-uniform, pipeline) the wave runs at issue priority 3: it hosts a query past pipe.boostAfter expansions
 	unsigned passCount = 0; // (wave-uniform, pipeline) loop passes: a row that found the ring empty looks again every kPollEvery-th pass only
 	bool pollNow = true;    // (pipeline) this row looks at the ring on the next pass whatever the pass count (it has just finished a query, or lost a race)
 	int slot = waveIdx * kRowsPerWave + (lane >> 4);
@@ -388,23 +385,6 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 #define ROWS_STAMP(ph)
 #endif
 	for (;;) {
-		// (pipeline) A wave iterates in ~30 us with four busy rows and in ~13 us with one, and a run ends with its longest chains of dependent expansions
-		// (the lattice-exhausting queries: 65 k): once a row's query has passed `soloAfter` expansions the wave's other rows take nothing new while the
-		// ready ring is short -- rows are idle then anyway (the wavefront stage paces the pipeline), and these are the ones that should be.  With a
-		// backlog of soloBacklog fields or more every row claims as before.
-		const bool waveLong = piped && pipe.soloAfter > 0 && __ballot(act && nExpanded >= pipe.soloAfter) != 0ull;
-		// (pipeline) the same queries from the other side: their chains run at ~13 us per expansion on an empty chip and at ~22 us next to the tile waves and the other
-		// search waves of a full one; a wave that hosts one asks for the SIMD's issue slots first (s_setprio 3) until the query ends
-		if (piped && pipe.boostAfter > 0) {
-			const bool hot = __ballot(act && nExpanded >= pipe.boostAfter) != 0ull;
-			if (hot != boosted) {
-				boosted = hot;
-				if (hot)
-					__builtin_amdgcn_s_setprio(3);
-				else
-					__builtin_amdgcn_s_setprio(PP_ROWS_PRIO);
-			}
-		}
 		// ================= rows without a query take the next one =================
 		if (!act && !done) {
 			bool none = false;
@@ -422,10 +402,7 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 				if (rl == 0 && look) {
 					unsigned long long h = __hip_atomic_load(&pipe.ctl->readyHead, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 					const unsigned long long e = __hip_atomic_load(pipe.ready + (h & pipe.readyMask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					bool take = (uint32_t)(e >> 32) == (uint32_t)(h + 1ull);
-					if (take && waveLong) // leave it to a wave without a long query unless fields are piling up
-						take = __hip_atomic_load(&pipe.ctl->readyTail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - h >= (unsigned long long)pipe.soloBacklog;
-					if (take)
+					if ((uint32_t)(e >> 32) == (uint32_t)(h + 1ull))
 						got = __hip_atomic_compare_exchange_strong(&pipe.ctl->readyHead, &h, h + 1ull, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 							? (int)(uint32_t)e : -2;
 				}
@@ -440,62 +417,12 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 				if (rl == 0)
 					nq = atomicAdd(nextQuery, 1);
 				q = (int)row_read((uint32_t)nq, lane, 0);
-				if (!resumeList)
-					q += A.directCount; // the first entries of the hand-out order run one query per wave (k_hybrid_search)
-				const int nAvail = resumeList ? min(*nResumeDev, A.listCap) : nQueries;
-				if (q >= nAvail) {
+				if (q >= nQueries) {
 					done = true;
 					none = true;
 				}
 			}
-			if (none) {
-			} else if (!piped && resumeList) {
-				// ---- continue a suspended query where it stopped, in the slot that holds its nodes / heap / key map / engine
-				const SuspendRec rec = resumeList[q];
-				q = rec.q;
-				set_slot((size_t)rec.slot);
-				field = costFields + (size_t)q * A.fieldElems;
-				goal = { goals[3 * q], goals[3 * q + 1], wrap_theta(goals[3 * q + 2]) };
-				myNode = -1;
-				rsNode = -1;
-				pfNode = -1;
-				pfDead = false;
-				noSuspend = false;
-				front_clear(front);
-				frontCount = 0;
-				nSpill = 0;
-				heapSize = rec.heapSize;
-				heapTop.ckey = ~0ull;
-				heapTop.nseq = ~0u;
-				heapTop.node = 0;
-				if (heapSize > 0)
-					heapTop = ROW_HEAP[0];
-				// the open list was moved out of the front buffer at suspension: band window and slot counts come back, the
-				// lowest possible bound keeps everything out of the empty buffer until the first refill
-				{
-					const uint4* src = reinterpret_cast<const uint4*>(bandMetaBase + (size_t)slot * (size_t)kBands);
-					wave_lds_sync();
-					for (int i = rl; i < kBands / 16; i += kRowLanes)
-						reinterpret_cast<uint4*>(bandCnt)[i] = src[i];
-					wave_lds_sync();
-				}
-				bandLo = rec.bandLo;
-				bandLoSet = true;
-				nOutside = rec.nOutside;
-				lowK = 0ull;
-				lowS = 0u;
-				nNodes = rec.nNodes;
-				seq = rec.seq;
-				nExpanded = rec.nExpanded;
-				nRngDraws = rec.nRngDraws;
-				nRsAttempts = rec.nRsAttempts;
-				nRsLog = rec.nRsLog;
-				mtIdx = rec.mtIdx;
-				laneStateChecks = rl == 0 ? rec.stateChecks : 0; // the totals so far ride in the row's first lane
-				lanePathChecks = rl == 0 ? rec.pathChecks : 0;
-				rsStateChecks = rsPathChecks = 0;
-				act = true;
-			} else {
+			if (!none) {
 				if (order)
 					q = order[q]; // probable longest first (written by the wavefront kernel's last workgroup)
 				field = costFields + (size_t)q * A.fieldElems;
@@ -634,8 +561,6 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 			continue;
 		}
 		idleIters = 0;
-		// compaction trigger (all lanes vote): some row found the queue empty and few rows of the wave are still busy
-		const bool compact = !piped && compactBelow > 0 && __ballot(done) != 0ull && __popcll(actMask) <= compactBelow * kRowLanes;
 		if (!act)
 			continue;
 
@@ -644,23 +569,15 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 			finish(-1, -1, __builtin_huge_val()); // open list exhausted: status -1
 			continue;
 		}
-		// ---- setting a query aside: its open list goes entirely into the heap, the scalars into a SuspendRec of the next
-		// stage's list.  Two triggers: (a) the query reached `suspendAfter` expansions -- a row working on the batch then
-		// continues with the next query in a spare slot, a row working on a resume list takes the next record (and its
-		// slot); (b) compaction: the queue is empty and at most `compactBelow` rows of this wave are still busy -- a wave
-		// costs the same with one busy row as with four, so the leftovers of all such waves are re-packed four per wave
-		// by the next stage and this wave ends.
+		// ---- setting a query aside: once it has reached `suspendAfter` expansions its open list goes entirely into the heap,
+		// the scalars into a SuspendRec for the one-query-per-wave kernel, and the row continues with the next query in a spare slot
 		const bool capHit = !piped && suspendAfter > 0 && nExpanded >= suspendAfter && !noSuspend;
-		if (capHit || compact) {
-			bool ok = true;
+		if (capHit) {
 			int sp = 0;
-			if (!compact && !resumeList) { // the row goes on: it needs a spare slot
-				if (rl == 0)
-					sp = atomicAdd(spareCount, 1);
-				sp = (int)row_read((uint32_t)sp, lane, 0);
-				ok = sp < A.extraSlots;
-			}
-			if (!ok) {
+			if (rl == 0)
+				sp = atomicAdd(spareCount, 1);
+			sp = (int)row_read((uint32_t)sp, lane, 0);
+			if (sp >= A.extraSlots) {
 				noSuspend = true;
 			} else {
 				int ns = 0;
@@ -711,11 +628,7 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 					r.pad = 0;
 					suspended[ns] = r;
 				}
-				if (compact) {
-					done = true; // nothing left to fetch: the wave ends once its rows have stored their records
-				} else if (!resumeList) {
-					set_slot((size_t)firstSpareSlot + (size_t)sp);
-				}
+				set_slot((size_t)firstSpareSlot + (size_t)sp);
 				wave_vmem_sync();
 				act = false;
 				continue;

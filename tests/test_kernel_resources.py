@@ -65,7 +65,7 @@ def test_search_kernel_scratch_stays_out_of_the_expansion_path(tmp_path):
     """What an expansion waits for is scratch traffic INSIDE its chain, not the kernel's spill count (with launch bounds of 3 / 4 waves
     per SIMD the pop, node and children phases get 43-78 scratch loads each and the same grid runs at 17.7 / 13.4 k plans/s instead of 27.2 k).  The pipeline form's
     listing (hipcc -S with line tables) is attributed to the phases between the kernel's own ROWS_STAMP markers (tools/isa_spill_map.py): the per-expansion phases
-    together hold 22 scratch loads and 2 stores today; the Reeds-Shepp block (0.9 % of the expansions) holds the other 300."""
+    together hold 23 scratch loads and 1 store today; the Reeds-Shepp block (0.9 % of the expansions) holds the other 300."""
     import subprocess
     import isa_spill_map
     from pathplanning_amd import build
