@@ -1147,7 +1147,8 @@ struct pp_planner {
 	std::vector<DevResult> hostResults;
 	// post-processing (pp_postprocess.hpp), allocated at the first pp_planner_postprocess
 	PostBuffers post {};
-	int postMaxPoints = 0, postDone = 0;
+	int postMaxPoints = 0, postDone = 0; // capacity of the buffers per query; queries of the last call
+	int postPoints = 0; // the last call's max_points: its sample limit and the buffers' per-query stride
 	std::vector<pp_post_result> hostPost;
 };
 
@@ -1982,9 +1983,9 @@ int pp_planner_postprocess(pp_planner* planner, int32_t n_queries, float path_in
 	P.maxCurvature = sp.max_curvature;
 	P.alpha = 20.0f; // GVD::alpha / dMax, gvd.h:181
 	P.dMax = 30.0f;
-	P.maxPoints = planner->postMaxPoints;
+	P.maxPoints = max_points; // the caller's limit, even below a capacity an earlier call allocated (status -4 beyond it)
 	planner->args.m = map->view();
-	const size_t lds = (size_t)planner->postMaxPoints * 16;
+	const size_t lds = (size_t)max_points * 16;
 	hipLaunchKernelGGL(k_postprocess, dim3(n_queries), dim3(kPostThreads), lds, s, planner->args, P, n_queries, planner->paths, planner->rsLogs, planner->results,
 		map->obstLabel[map->obstResult], map->voroLabel[map->voroResult], planner->post);
 	PP_HIP_TRY(hipGetLastError());
@@ -1992,6 +1993,7 @@ int pp_planner_postprocess(pp_planner* planner, int32_t n_queries, float path_in
 	PP_HIP_TRY(hipMemcpyAsync(planner->hostPost.data(), planner->post.out, (size_t)n_queries * sizeof(pp_post_result), hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	planner->postDone = n_queries;
+	planner->postPoints = max_points;
 	if (results_host)
 		for (int i = 0; i < n_queries; i++)
 			results_host[i] = planner->hostPost[i];
@@ -2005,7 +2007,7 @@ int pp_planner_get_processed_path(pp_planner* planner, int32_t q, double* sample
 		return PP_ERR_INVALID;
 	}
 	PP_HIP_TRY(hipSetDevice(planner->map->ctx->device));
-	const size_t n = (size_t)planner->hostPost[q].n_points, cap = (size_t)planner->postMaxPoints;
+	const size_t n = (size_t)planner->hostPost[q].n_points, cap = (size_t)planner->postPoints;
 	if (n == 0)
 		return PP_OK;
 	if (sampled_host)

@@ -12,18 +12,10 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from gpu_common import circle_vertices, rect_vertices
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def rect_vertices(dx, dy):
-    return [(dx / 2.0, dy / 2.0), (-dx / 2.0, dy / 2.0), (-dx / 2.0, -dy / 2.0), (dx / 2.0, -dy / 2.0)]  # RectangleShape, obstacle.cpp:106-110
-
-
-def circle_vertices(radius, count):
-    radius *= 1.0 / math.cos(math.pi / count)  # CircleShape, obstacle.cpp:112-122 (the angle goes through a float division)
-    return [(radius * math.cos(2 * math.pi * i / float(np.float32(count))), radius * math.sin(2 * math.pi * i / float(np.float32(count)))) for i in range(count)]
 
 
 def build_pair(n_cells, shapes, resolution=0.1):

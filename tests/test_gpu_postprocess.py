@@ -12,21 +12,29 @@ from gpu_common import make_pair, valid_random_poses
 pytestmark = pytest.mark.gpu
 
 
-def run(w, ms, val, n, seed, path_interpolation, smoother=None, costs=None, chaotic_ok=False, strict_points=False):
+def square_pairs(rng, w, n):
+    return valid_random_poses(rng, w, n), valid_random_poses(rng, w, n)
+
+
+def run(w, ms, val, n, seed, path_interpolation, smoother=None, costs=None, chaotic_ok=False, strict_points=False, pairs=square_pairs, upload_labels=True,
+        max_nodes=32768):
+    """`pairs(rng, w, n)` draws the (starts, goals); `upload_labels`: the oracle's brushfire labels go to the device first (else the map's
+    own, e.g. from pp_map_update_gvd, are read)"""
     import pathplanning_amd as pa
     kw = costs or {}
-    ms.upload_nearest_cells(*O.world_nearest(w))
+    if upload_labels:
+        ms.upload_nearest_cells(*O.world_nearest(w))
     rng = np.random.RandomState(seed)
-    starts, goals = valid_random_poses(rng, w, n), valid_random_poses(rng, w, n)
+    starts, goals = pairs(rng, w, n)
     goals[0] = starts[0]  # start == goal: a one-node solution, nothing to sample
     seeds = np.arange(n, dtype=np.uint64) + 17
-    planner = pa.HybridAStarBatch(val, pa.HybridAStarSearchParameters(**kw), max_batch=n, max_nodes=32768)
+    planner = pa.HybridAStarBatch(val, pa.HybridAStarSearchParameters(**kw), max_batch=n, max_nodes=max_nodes)
     planner.initialize()
     res = planner.search_batch(starts, goals, seeds)
     post = planner.postprocess(path_interpolation=path_interpolation, smoother=smoother)
     h = O.Hybrid(w, O.params_array(**kw), table=planner.nonholo_table())
-    sp = O.smoother_array(max_curvature=1.0 / 2.0, **(smoother or {}))
-    stats = dict(compared=0, smoothed_ok=0, max_apart=0.0, failed=0, unstable_in_the_reference=0)
+    sp = O.smoother_array(max_curvature=1.0 / {**O.DEFAULT_PARAMS, **kw}["min_turning_radius"], **(smoother or {}))
+    stats = dict(compared=0, smoothed_ok=0, max_apart=0.0, failed=0, unstable_in_the_reference=0, short=0)
     for q in range(n):
         r = h.search(starts[q], goals[q], int(seeds[q]))
         assert res[q].status == r["status"]
@@ -40,6 +48,7 @@ def run(w, ms, val, n, seed, path_interpolation, smoother=None, costs=None, chao
         assert np.array_equal(g["cusp"], want["cusp"])
         assert np.abs(g["sampled"] - want["resampled"]).max() < 1e-9
         stats["compared"] += 1
+        stats["short"] += want["n_points"] < 5
         # Smoothing status equal and every path the reference keeps (status >= 0) within north_star's 1e-5.  The only escape, and only
         # where the caller allows it (`chaotic_ok`, the 0.1 m spacing at which the reference's descent is unstable): a query on which
         # the ORACLE ITSELF does not reproduce its result once the cosine of its curvature term moves by one ulp -- the amount by which
