@@ -37,6 +37,7 @@ extern "C" {
 typedef struct pp_ctx pp_ctx;         /* one device + one stream */
 typedef struct pp_map pp_map;         /* device-resident map set of one OccupancyMap */
 typedef struct pp_planner pp_planner; /* Hybrid-A* tables + per-query workspaces */
+typedef struct pp_footprint pp_footprint; /* vehicle footprint: discs in the vehicle frame, bound to one map */
 
 const char* pp_last_error(void);
 int pp_version(void);
@@ -212,6 +213,56 @@ int pp_check_rs_paths(pp_map* map, int64_t n, const pp_rs_path* paths_host, uint
 /* ... and over PathSE2 (paths/path_se2.cpp:5-22: position and heading interpolated linearly, length = |to - from|). */
 int pp_check_se2_paths(pp_map* map, int64_t n, const double* from_host, const double* to_host, uint8_t* valid_host, float* last_ratio_host);
 
+/* ---- vehicle footprint: multi-disc collision test ----------------------------
+ * An extension with no counterpart in the reference, whose validator compares ONE look-up of the obstacle-distance grid at
+ * the pose's reference point with minSafeRadius.  A footprint is K discs, 1 <= K <= 8, each (ox, oy, r): centre in the
+ * vehicle frame (origin = the pose's reference point, x forward, y left; metres) and radius (finite, >= 0).
+ * rho = max_i hypot(ox_i, oy_i).
+ *
+ * State check of a pose (x, y, theta):
+ *  1. the reference point passes everything IsStateValid tests except the distance comparison: local position inside the
+ *     state bounds, wrapped heading inside the heading bounds, cell inside the grid;
+ *  2. for every disc in order: centre cx = (x + ox*c) - oy*s, cy = (y + ox*s) + oy*c with (s, c) = sin, cos of the
+ *     UNWRAPPED theta in double (a disc with ox == 0 && oy == 0 uses (x, y) itself and no trigonometry).  The centre must
+ *     lie inside the position bounds and its cell (same truncation as the reference point's) inside the grid; then
+ *     d_i = distance grid at that cell, and the disc passes iff d_i >= r_i (float compare);
+ *  3. valid iff all pass.  clearance = min_i (d_i - r_i) as float; border = (float) min over the reference point and every
+ *     disc centre of its four distances to the position bounds (double min, then one conversion).
+ * Path check: the march of IsPathValid (state_validator_occupancy_map.cpp:28-71) with
+ *     step = fmaxf(fminf(clearance, border) / gain, minPathInterpolationDistance)          (all float)
+ *     gain = (float)(1.0 + kappaMax * rho)                                               (double, then one conversion)
+ * because a disc centre moves up to (1 + kappa * rho) times as fast as the reference point while the vehicle turns.
+ * kappaMax: |curvature| of a constant-steer arc; 1 / min_turning_radius of a Reeds-Shepp path; |to.theta - from.theta| /
+ * length of a PathSE2.  last_ratio, the zero-length case and the sample limit are IsPathValid's.  minSafeRadius plays no part
+ * once a footprint is used.  The footprint {(0, 0, minSafeRadius)} is the point validator, bit for bit.
+ * A footprint follows its map's distance grid: after pp_map_upload_dist2 / pp_map_upload_distance / pp_map_update_gvd* the
+ * next check uses the new grid.  A footprint used with another map than its own is PP_ERR_INVALID. */
+#define PP_FOOTPRINT_MAX_DISCS 8
+typedef struct pp_footprint_disc {
+	double ox, oy; /* centre in the vehicle frame, metres */
+	float r;       /* radius, metres */
+	float pad;
+} pp_footprint_disc;
+/* n_discs outside 1..8, a non-finite value or a negative radius: PP_ERR_INVALID.  The footprint keeps its map alive. */
+int pp_footprint_create(pp_map* map, int32_t n_discs, const pp_footprint_disc* discs, pp_footprint** out);
+int pp_footprint_destroy(pp_footprint* fp);
+/* Pure host arithmetic, no device: n equal discs on the long axis covering a length x width rectangle whose rear edge lies
+ * rear_overhang behind the reference point: s = length / n, ox_i = -rear_overhang + (i + 0.5) * s, oy_i = 0,
+ * r = sqrt((s/2)^2 + (width/2)^2) rounded UP to float.  discs_out holds n_discs records. */
+int pp_footprint_cover_rectangle(double length, double width, double rear_overhang, int32_t n_discs, pp_footprint_disc* discs_out);
+/* The state check above, batched.  clearance_host may be NULL; where the pose is invalid it receives -1. */
+int pp_check_states_footprint(pp_map* map, pp_footprint* fp, int64_t n, const double* poses_host, uint8_t* valid_host, float* clearance_host);
+int pp_check_states_footprint_dev(pp_map* map, pp_footprint* fp, int64_t n, const double* poses_dev, uint8_t* valid_dev);
+/* The path check above over constant-steer arcs (arguments as pp_check_arcs), Reeds-Shepp paths (pp_check_rs_paths) and
+ * PathSE2 (pp_check_se2_paths). */
+int pp_check_arcs_footprint_dev(pp_map* map, pp_footprint* fp, int64_t n, const double* from_dev, const double* curvature_dev, const double* length_dev,
+	const int32_t* direction_dev, uint8_t* valid_dev, float* last_ratio_dev);
+int pp_check_arcs_footprint(pp_map* map, pp_footprint* fp, int64_t n, const double* from_host, const double* curvature_host, const double* length_host,
+	const int32_t* direction_host, uint8_t* valid_host, float* last_ratio_host);
+int pp_check_rs_paths_footprint_dev(pp_map* map, pp_footprint* fp, int64_t n, const pp_rs_path* paths_dev, uint8_t* valid_dev, float* last_ratio_dev);
+int pp_check_rs_paths_footprint(pp_map* map, pp_footprint* fp, int64_t n, const pp_rs_path* paths_host, uint8_t* valid_host, float* last_ratio_host);
+int pp_check_se2_paths_footprint(pp_map* map, pp_footprint* fp, int64_t n, const double* from_host, const double* to_host, uint8_t* valid_host, float* last_ratio_host);
+
 /* ---- a10: NonHolonomicHeuristic::Build (algo/heuristics.cpp:36-76) ---------
  * dims = {nX, nY, nAngular}; table[(i*nY + j)*nAngular + k]. */
 int pp_nonholo_dims(const double lower[3], const double upper[3], const pp_hybrid_params* params, int32_t dims[3], double offsets[2]);
@@ -267,6 +318,13 @@ int pp_planner_destroy(pp_planner* planner);
 int pp_planner_set_nonholo_table(pp_planner* planner, const double* table_host);
 int pp_planner_get_nonholo_table(pp_planner* planner, double* table_host);
 int pp_planner_num_primitives(pp_planner* planner);
+/* Vehicle footprint for the search (see "vehicle footprint" above): everything that asks "is this pose / arc / Reeds-Shepp path valid"
+ * -- the start pose, each child's own pose, the arc march and its truncation, the analytic expansion -- goes through the footprint;
+ * heuristics, costs, open list, RNG gate and discretisation are untouched.  fp == NULL: back to the point validator.  The planner holds
+ * a reference to the footprint.  One-query-per-wave planners only: a planner that runs the rows kernel (pp_planner_search_rows() > 0;
+ * create it with max_batch <= 64, or with PP_SEARCH_ROWS=0 in the environment) or is a pipeline's buffer set, and a footprint of
+ * another map, are PP_ERR_INVALID. */
+int pp_planner_set_footprint(pp_planner* planner, pp_footprint* fp);
 /* Replaces StatePropagator::m_deltas (algo/hybrid_a_star.cpp:21-28 generates {0, +-0.5 dMax, +-1.0 dMax, ...} from num_generated_motion,
  * which can only give 2 * odd primitives): any list of steering angles [rad]; every angle gives a forward and a backward primitive,
  * children in list order, forward first (hybrid_a_star.cpp:65-77).  36 angles = the "72 motion primitives" of BASELINE config 2.

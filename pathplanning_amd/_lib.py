@@ -63,6 +63,14 @@ RS_PATH_DTYPE = np.dtype([("start", "<f8", 3), ("final_pose", "<f8", 3), ("motio
 assert RS_PATH_DTYPE.itemsize == 128
 
 
+class FootprintDisc(C.Structure):
+    """pp_footprint_disc: centre in the vehicle frame (x forward, y left; metres) and radius"""
+    _fields_ = [("ox", C.c_double), ("oy", C.c_double), ("r", C.c_float), ("pad", C.c_float)]
+
+
+PP_FOOTPRINT_MAX_DISCS = 8
+
+
 class SmootherParams(C.Structure):
     """Smoother::Parameters, algo/smoother.h:28-60"""
     _fields_ = [("step_tolerance", C.c_float), ("max_iterations", C.c_int32), ("learning_rate", C.c_float), ("path_weight", C.c_float), ("smooth_weight", C.c_float),
@@ -139,6 +147,17 @@ def load():
     L.pp_check_rs_paths.argtypes = [vp, C.c_int64, vp, vp, vp]
     L.pp_check_rs_paths_dev.argtypes = [vp, C.c_int64, vp, vp, vp]
     L.pp_check_se2_paths.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
+    L.pp_footprint_create.argtypes = [vp, C.c_int32, vp, C.POINTER(vp)]
+    L.pp_footprint_destroy.argtypes = [vp]
+    L.pp_footprint_cover_rectangle.argtypes = [C.c_double, C.c_double, C.c_double, C.c_int32, vp]
+    L.pp_check_states_footprint.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
+    L.pp_check_states_footprint_dev.argtypes = [vp, vp, C.c_int64, vp, vp]
+    L.pp_check_arcs_footprint.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
+    L.pp_check_arcs_footprint_dev.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
+    L.pp_check_rs_paths_footprint.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
+    L.pp_check_rs_paths_footprint_dev.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
+    L.pp_check_se2_paths_footprint.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp]
+    L.pp_planner_set_footprint.argtypes = [vp, vp]
     L.pp_rs_solve.argtypes = [vp, C.c_int64, vp, vp, C.c_double, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp]
     L.pp_rs_solve_dev.argtypes = [vp, C.c_int64, vp, vp, C.c_double, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp]
     L.pp_nonholo_dims.argtypes = [vp, vp, C.POINTER(HybridParams), vp, vp]

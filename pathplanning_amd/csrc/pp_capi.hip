@@ -93,6 +93,7 @@ int check_map(pp_map* map, bool needDist)
 } // namespace
 
 namespace pph {
+void dist_changed(pp_map* map) { map->distVersion++; }
 void ctx_release(pp_ctx* ctx)
 {
 	if (!ctx || __atomic_sub_fetch(&ctx->refs, 1, __ATOMIC_ACQ_REL) > 0)
@@ -274,6 +275,7 @@ int pp_map_upload_dist2(pp_map* map, const int32_t* d2_host)
 	if (!map->validBits)
 		PP_HIP_TRY(hipMalloc((void**)&map->validBits, ((n + 63) / 64) * 8)); // whole 64-cell groups: one ballot each
 	PP_HIP_TRY(launch_valid_bits(map->ctx->stream, map->dist, (int64_t)n, map->minSafeRadius, map->validBits));
+	pph::dist_changed(map);
 	PP_HIP_TRY(hipStreamSynchronize(map->ctx->stream));
 	return PP_OK;
 }

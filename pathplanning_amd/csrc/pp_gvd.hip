@@ -560,6 +560,7 @@ int pp_map_update_gvd_ex(pp_map* map, float alpha, float d_max, int32_t mode, in
 	PP_HIP_TRY(hipGetLastError());
 	PP_HIP_TRY(pph::launch_d2_to_distance(s, map->d2, map->dist, (int64_t)n, map->desc.resolution));
 	PP_HIP_TRY(pph::launch_valid_bits(s, map->dist, (int64_t)n, map->minSafeRadius, map->validBits));
+	pph::dist_changed(map);
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	if (iterations_out)
 		*iterations_out = (int32_t)(work > INT_MAX ? INT_MAX : work);

@@ -8,6 +8,7 @@
 
 #include "../../include/pp_hip.h"
 #include "pp_device.hpp"
+#include "pp_footprint_device.hpp"
 
 namespace pph {
 
@@ -151,6 +152,8 @@ void gvd_reference_free(pp_map* map); // pp_gvd.hip
 int refresh_occupancy_views(pp_map* map, hipStream_t s);
 void ctx_release(pp_ctx* ctx); // drops one reference, frees at zero
 void map_release(pp_map* map);
+/// every writer of pp_map::dist ends here (after the write is enqueued on the map's stream)
+void dist_changed(pp_map* map);
 } // namespace pph
 
 // Lifetimes: a map keeps its context alive and a planner its map (reference counts), so the handles may be destroyed
@@ -174,6 +177,7 @@ struct pp_map {
 	float* pathcost = nullptr;
 	uint8_t* occ8 = nullptr;
 	uint32_t* validBits = nullptr; // one bit per cell: dist >= minSafeRadius
+	uint64_t distVersion = 0;      // counts the writes of `dist` (pph::dist_changed): a footprint rebuilds its bitmaps when it lags behind
 	uint64_t* occBits = nullptr;   // occupancy as padded bit rows (WavefrontPublish::occBits), rebuilt whenever occ8 is
 	// map authoring / field construction on the device (pp_gvd.hip)
 	int32_t* occ32 = nullptr;      // occupancy ids as the reference holds them (-1 free)
@@ -192,3 +196,24 @@ struct pp_map {
 	ppd::MapView view() const;
 	size_t cells() const { return (size_t)desc.rows * desc.cols; }
 };
+
+/// A vehicle footprint bound to one map (include/pp_hip.h).  It keeps its map alive; its validity bitmaps (one per distinct
+/// radius, the map's own layout: pp_map::validBits) follow the map's distance grid through pp_map::distVersion.
+struct pp_footprint {
+	int refs = 1;
+	pp_map* map = nullptr;
+	ppd::Footprint fp {};
+	int nRadii = 0;
+	float radii[ppd::kFootprintMaxDiscs] = {};
+	uint32_t* bits = nullptr;  // nRadii bitmaps, wordsPer 32-bit words apart
+	uint32_t wordsPer = 0;
+	uint64_t bitsVersion = 0;  // the map's distVersion the bitmaps were built from
+	bool bitsBuilt = false;
+};
+namespace pph {
+/// Checks that `fp` belongs to `map` and that the map has a distance grid (PP_ERR_INVALID with a message otherwise);
+/// needBits: also brings the footprint's bitmaps up to date with the map's distance grid, on the map's stream.
+int footprint_prepare(pp_map* map, pp_footprint* fp, bool needBits);
+void footprint_release(pp_footprint* fp); // drops one reference, frees at zero
+hipError_t launch_check_states_footprint(hipStream_t s, const ppd::MapView& m, const pp_footprint* fp, int64_t n, const double* poses, uint8_t* valid, float* clearance);
+} // namespace pph

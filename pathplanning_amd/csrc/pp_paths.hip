@@ -7,6 +7,7 @@
 // One thread per path; the arithmetic is pp_rs_device.hpp's, the same functions the search kernels inline.
 #include "pp_internal.hpp"
 #include "pp_rs_device.hpp"
+#include "pp_paths_device.hpp"
 
 using namespace ppd;
 
@@ -17,25 +18,6 @@ inline int grid_for(int64_t n, int block)
 {
 	int64_t g = (n + block - 1) / block;
 	return (int)(g < 1 ? 1 : (g > 65535 * 4 ? 65535 * 4 : g));
-}
-
-static_assert(sizeof(pp_rs_path) == 128, "pp_rs_path is a 128-byte record");
-
-__device__ __forceinline__ rs::Path load_path(const pp_rs_path& r)
-{
-	rs::Path p;
-	p.init = { r.start[0], r.start[1], r.start[2] };
-	p.rmin = r.min_turning_radius;
-	p.length = r.length;
-	p.seg.length = 0.0;
-	p.seg.n = 0;
-#pragma unroll
-	for (int i = 0; i < rs::kNumMotion; i++) {
-		p.seg.len[i] = r.motion_length[i];
-		p.seg.steer[i] = r.steer[i];
-		p.seg.dir[i] = r.direction[i];
-	}
-	return p;
 }
 
 __device__ __forceinline__ void store_motions(pp_rs_path& r, const rs::Path& p)
@@ -130,20 +112,6 @@ __global__ void __launch_bounds__(kBlock) k_check_rs_paths(MapView m, int64_t n,
 			last[i] = l;
 	}
 }
-
-/// PathSE2, paths/path_se2.cpp:5-22
-struct Se2Line {
-	Pose init, fin;
-	double length;
-	__device__ __forceinline__ Pose interpolate(double ratio) const
-	{
-		Pose s;
-		s.x = (1 - ratio) * init.x + ratio * fin.x;
-		s.y = (1 - ratio) * init.y + ratio * fin.y;
-		s.t = (1 - ratio) * init.t + ratio * fin.t; // assigned to the member: not wrapped
-		return s;
-	}
-};
 
 __global__ void __launch_bounds__(kBlock) k_check_se2_paths(MapView m, int64_t n, const double* __restrict__ from, const double* __restrict__ to, uint8_t* __restrict__ valid,
 	float* __restrict__ last)
@@ -362,6 +330,7 @@ int pp_map_upload_distance(pp_map* map, const float* distance_host)
 	if (!map->validBits)
 		PP_HIP_TRY(hipMalloc((void**)&map->validBits, ((n + 63) / 64) * 8));
 	PP_HIP_TRY(pph::launch_valid_bits(s, map->dist, (int64_t)n, map->minSafeRadius, map->validBits));
+	pph::dist_changed(map);
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	return PP_OK;
 }

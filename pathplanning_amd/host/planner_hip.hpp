@@ -15,6 +15,9 @@
 #include <random>
 #include <limits>
 #include <cstdio>
+#include <cmath>
+#include <algorithm>
+#include <tuple>
 
 #include "types.hpp"
 #include "paths.hpp"
@@ -415,7 +418,26 @@ public:
 	}
 };
 
+/// One disc of a vehicle footprint: centre in the vehicle frame (origin = the pose's reference point, x forward, y left; metres), radius
+struct FootprintDisc {
+	double ox = 0.0, oy = 0.0;
+	float r = 0.0f;
+};
+/// pp_footprint_cover_rectangle: n equal discs on the long axis covering a length x width rectangle whose rear edge lies rearOverhang
+/// behind the reference point (host arithmetic)
+inline std::vector<FootprintDisc> RectangleFootprint(double length, double width, double rearOverhang, int nDiscs)
+{
+	pp_footprint_disc d[PP_FOOTPRINT_MAX_DISCS];
+	ppCheck(pp_footprint_cover_rectangle(length, width, rearOverhang, nDiscs, d));
+	std::vector<FootprintDisc> out((size_t)nDiscs);
+	for (int i = 0; i < nDiscs; i++)
+		out[(size_t)i] = { d[i].ox, d[i].oy, d[i].r };
+	return out;
+}
+
 /// state_validator/state_validator_occupancy_map.{h,cpp}, GPU-backed.
+/// Extension (include/pp_hip.h, "vehicle footprint"): with SetFootprint the checks test the vehicle's discs against the distance map instead
+/// of the reference point against minSafeRadius; without one everything is the reference's validator.
 class StateValidatorOccupancyMap : public StateValidatorSE2Base {
 public:
 	StateValidatorOccupancyMap(const Ref<StateSpaceSE2>& stateSpace, const Ref<OccupancyMap>& map) : StateValidatorSE2Base(stateSpace), m_map(map)
@@ -426,18 +448,63 @@ public:
 		m_map->InitializeSize(width, height);
 		m_map->SetStateBounds(stateSpace->bounds);
 	}
+	~StateValidatorOccupancyMap() override { DropDeviceFootprint(); }
+	/// 1 to 8 discs with finite centres and finite radii >= 0; anything else throws std::invalid_argument and leaves the footprint as it was
+	void SetFootprint(std::vector<FootprintDisc> discs)
+	{
+		if (discs.empty() || discs.size() > PP_FOOTPRINT_MAX_DISCS)
+			throw std::invalid_argument("a footprint has 1 to 8 discs");
+		for (const FootprintDisc& d : discs)
+			if (!std::isfinite(d.ox) || !std::isfinite(d.oy) || !std::isfinite(d.r) || d.r < 0.0f)
+				throw std::invalid_argument("footprint disc centres must be finite and radii finite and >= 0");
+		DropDeviceFootprint();
+		m_footprint = std::move(discs);
+	}
+	void ClearFootprint()
+	{
+		DropDeviceFootprint();
+		m_footprint.clear();
+	}
+	const std::vector<FootprintDisc>& GetFootprint() const { return m_footprint; }
+	bool HasFootprint() const { return !m_footprint.empty(); }
+	/// the footprint on the device, bound to the map's current device map set (nullptr without a footprint); call after Device()
+	pp_footprint* DeviceFootprint()
+	{
+		if (m_footprint.empty())
+			return nullptr;
+		pp_map* d = m_map->Device();
+		if (m_fp && m_fpMap != d) // the map set was rebuilt: a footprint belongs to one map set
+			DropDeviceFootprint();
+		if (!m_fp) {
+			pp_footprint_disc discs[PP_FOOTPRINT_MAX_DISCS];
+			for (size_t i = 0; i < m_footprint.size(); i++)
+				discs[i] = { m_footprint[i].ox, m_footprint[i].oy, m_footprint[i].r, 0.0f };
+			ppCheck(pp_footprint_create(d, (int32_t)m_footprint.size(), discs, &m_fp));
+			m_fpMap = d;
+		}
+		return m_fp;
+	}
 	bool IsStateValid(const Pose2d& state) override
 	{
 		uint8_t v = 0;
-		ppCheck(pp_check_states(Device(), 1, &state.position.v[0], &v));
+		pp_map* d = Device();
+		if (pp_footprint* fp = DeviceFootprint())
+			ppCheck(pp_check_states_footprint(d, fp, 1, &state.position.v[0], &v, nullptr));
+		else
+			ppCheck(pp_check_states(d, 1, &state.position.v[0], &v));
 		return v != 0;
 	}
 	/// batched: n poses -> n flags
 	std::vector<uint8_t> IsStateValid(const std::vector<Pose2d>& states)
 	{
 		std::vector<uint8_t> out(states.size());
-		if (!states.empty())
-			ppCheck(pp_check_states(Device(), (int64_t)states.size(), &states[0].position.v[0], out.data()));
+		if (states.empty())
+			return out;
+		pp_map* d = Device();
+		if (pp_footprint* fp = DeviceFootprint())
+			ppCheck(pp_check_states_footprint(d, fp, (int64_t)states.size(), &states[0].position.v[0], out.data(), nullptr));
+		else
+			ppCheck(pp_check_states(d, (int64_t)states.size(), &states[0].position.v[0], out.data()));
 		return out;
 	}
 	/// IsPathValid over constant-steer arcs given as (start, curvature, length, direction)
@@ -446,7 +513,11 @@ public:
 		uint8_t v = 0;
 		float l = 0;
 		int32_t d = dir == Direction::Backward ? 1 : 0;
-		ppCheck(pp_check_arcs(Device(), 1, &from.position.v[0], &curvature, &length, &d, &v, &l));
+		pp_map* dev = Device();
+		if (pp_footprint* fp = DeviceFootprint())
+			ppCheck(pp_check_arcs_footprint(dev, fp, 1, &from.position.v[0], &curvature, &length, &d, &v, &l));
+		else
+			ppCheck(pp_check_arcs(dev, 1, &from.position.v[0], &curvature, &length, &d, &v, &l));
 		if (last)
 			*last = l;
 		return v != 0;
@@ -455,31 +526,51 @@ public:
 	/// PathConstantSteer -> pp_check_arcs, PathReedsShepp -> pp_check_rs_paths, PathSE2 -> pp_check_se2_paths.  A path type
 	/// defined by the caller (a C++ or Python subclass of Path) can only be sampled through its own virtual Interpolate on the
 	/// host, so for those the march runs here, sample by sample, over the host copy of the distance grid.
+	/// With a footprint the three device types go to the footprint entries; a caller-defined path type is REFUSED (std::runtime_error): the
+	/// footprint's march divides its step by 1 + kappaMax * rho, and an opaque Interpolate gives no bound kappaMax on its heading rate.
 	bool IsPathValid(const PathSE2Base& path, float* last = nullptr) override
 	{
 		uint8_t v = 0;
 		float l = 0.0f;
+		pp_map* dev = Device();
+		pp_footprint* fp = DeviceFootprint();
 		if (auto* arc = dynamic_cast<const PathConstantSteer*>(&path)) {
+			if (fp && arc->GetModel()->RearToCenter() != 0.0)
+				throw std::runtime_error("StateValidatorOccupancyMap::IsPathValid: a footprint is set and this PathConstantSteer uses a bicycle model with rearToCenter != 0; "
+										 "the footprint's arc march is the rear-axle model's (rearToCenter = 0). Use such a model, or ClearFootprint()");
 			if (arc->GetModel()->RearToCenter() == 0.0) { // the device arc is the rear-axle model the planner uses (hybrid_a_star.cpp:19)
 				const double kappa = arc->GetModel()->Curvature(arc->GetSteeringAngle());
 				const double len = arc->GetLength();
 				const int32_t d = arc->GetDirection(0.0) == Direction::Backward ? 1 : 0;
-				ppCheck(pp_check_arcs(Device(), 1, &arc->GetInitialState().position.v[0], &kappa, &len, &d, &v, &l));
+				if (fp)
+					ppCheck(pp_check_arcs_footprint(dev, fp, 1, &arc->GetInitialState().position.v[0], &kappa, &len, &d, &v, &l));
+				else
+					ppCheck(pp_check_arcs(dev, 1, &arc->GetInitialState().position.v[0], &kappa, &len, &d, &v, &l));
 				if (last)
 					*last = l;
 				return v != 0;
 			}
 		} else if (auto* rs = dynamic_cast<const PathReedsShepp*>(&path)) {
-			ppCheck(pp_check_rs_paths(Device(), 1, &rs->Record(), &v, &l));
+			if (fp)
+				ppCheck(pp_check_rs_paths_footprint(dev, fp, 1, &rs->Record(), &v, &l));
+			else
+				ppCheck(pp_check_rs_paths(dev, 1, &rs->Record(), &v, &l));
 			if (last)
 				*last = l;
 			return v != 0;
 		} else if (auto* line = dynamic_cast<const PathSE2*>(&path)) {
-			ppCheck(pp_check_se2_paths(Device(), 1, &line->GetInitialState().position.v[0], &line->GetFinalState().position.v[0], &v, &l));
+			if (fp)
+				ppCheck(pp_check_se2_paths_footprint(dev, fp, 1, &line->GetInitialState().position.v[0], &line->GetFinalState().position.v[0], &v, &l));
+			else
+				ppCheck(pp_check_se2_paths(dev, 1, &line->GetInitialState().position.v[0], &line->GetFinalState().position.v[0], &v, &l));
 			if (last)
 				*last = l;
 			return v != 0;
 		}
+		if (fp)
+			throw std::runtime_error("StateValidatorOccupancyMap::IsPathValid: a footprint is set and this path type is defined by the caller; the footprint's "
+									 "march needs a bound on the path's heading rate, which only PathConstantSteer (rear-axle model), PathReedsShepp and PathSE2 "
+									 "provide. Use one of those, or ClearFootprint()");
 		return MarchOnHost(path, last);
 	}
 	/// IsPathValid over many paths of one of the reference's types at once (one launch per type); `last` may be null
@@ -504,7 +595,11 @@ public:
 		if (!recs.empty()) {
 			std::vector<uint8_t> v(recs.size());
 			std::vector<float> l(recs.size());
-			ppCheck(pp_check_rs_paths(Device(), (int64_t)recs.size(), recs.data(), v.data(), l.data()));
+			pp_map* dev = Device();
+			if (pp_footprint* fp = DeviceFootprint())
+				ppCheck(pp_check_rs_paths_footprint(dev, fp, (int64_t)recs.size(), recs.data(), v.data(), l.data()));
+			else
+				ppCheck(pp_check_rs_paths(dev, (int64_t)recs.size(), recs.data(), v.data(), l.data()));
 			for (size_t k = 0; k < recs.size(); k++) {
 				out[recIdx[k]] = v[k];
 				if (last)
@@ -525,6 +620,16 @@ public:
 	float minSafeRadius = 1.0f;
 
 private:
+	void DropDeviceFootprint()
+	{
+		if (m_fp)
+			pp_footprint_destroy(m_fp);
+		m_fp = nullptr;
+		m_fpMap = nullptr;
+	}
+	std::vector<FootprintDisc> m_footprint;
+	pp_footprint* m_fp = nullptr;
+	pp_map* m_fpMap = nullptr;
 	/// the reference's loop, verbatim in structure, for caller-defined path types (see IsPathValid)
 	bool MarchOnHost(const PathSE2Base& path, float* last)
 	{
@@ -634,6 +739,9 @@ public:
 			return isInitialized = false;
 		if (pp_planner_set_nonholo_table(m_planner, nullptr))
 			return isInitialized = false;
+		m_plannerFootprint = nullptr;
+		if (!SyncFootprint("Initialize")) // the validator's footprint goes to the planner (a planner sized for the rows kernel refuses it)
+			return isInitialized = false;
 		return isInitialized = true;
 	}
 	Status SearchPath() override
@@ -643,6 +751,8 @@ public:
 		if (m_validator->GetOccupancyMap()->FieldsOutdated())
 			m_validator->GetOccupancyMap()->BuildFields(20.0f, 30.0f); // m_gvd->Update(), hybrid_a_star.cpp:250 (GVD::alpha / dMax, gvd.h:181)
 		m_validator->Device(); // pushes map edits / tunables
+		if (!SyncFootprint("SearchPath"))
+			return m_stats.graphSearchStatus = Status::Failure;
 		pp_query_result r {};
 		uint64_t seed = m_seed;
 		if (pp_planner_search_batch(m_planner, 1, &m_init.position.v[0], &m_goal.position.v[0], &seed, &r))
@@ -674,6 +784,16 @@ public:
 				m_stats.smoothingStatus = (Smoother::Status)post.smoothing_status;
 				m_smoothed = smoothed;
 				m_path = post.smoothing_status >= 0 ? smoothed : sampled;
+				// The smoother knows the point validator only.  With a footprint the path it returns is checked sample by sample against the
+				// footprint; if any fails, the resampled (unsmoothed) path is returned with smoothingStatus = Collision -- the reference's own
+				// fall-back shape (hybrid_a_star.cpp:294-303).
+				if (m_validator->HasFootprint() && post.smoothing_status >= 0) {
+					const std::vector<uint8_t> ok = m_validator->IsStateValid(smoothed);
+					if (std::find(ok.begin(), ok.end(), (uint8_t)0) != ok.end()) {
+						m_stats.smoothingStatus = Smoother::Status::Collision;
+						m_path = sampled;
+					}
+				}
 			}
 		}
 		return Status::Success;
@@ -797,6 +917,8 @@ public:
 		if (m_validator->GetOccupancyMap()->FieldsOutdated())
 			m_validator->GetOccupancyMap()->BuildFields(20.0f, 30.0f);
 		m_validator->Device();
+		if (!SyncFootprint("SearchBatch"))
+			throw std::runtime_error(std::string("libpphip: ") + pp_last_error());
 		std::vector<pp_query_result> res(starts.size());
 		if (!starts.empty())
 			ppCheck(pp_planner_search_batch(m_planner, (int32_t)starts.size(), &starts[0].position.v[0], &goals[0].position.v[0], seeds.data(), res.data()));
@@ -812,6 +934,20 @@ public:
 	float pathInterpolation = 0.1f; // algo/hybrid_a_star.h:249: spacing of the sampled path
 
 private:
+	/// hands the validator's footprint as it is now (set, changed or cleared since the last search) to the planner; refusals go to stderr
+	bool SyncFootprint(const char* where)
+	{
+		pp_footprint* want = m_validator->DeviceFootprint();
+		if (want == m_plannerFootprint)
+			return true;
+		if (pp_planner_set_footprint(m_planner, want)) {
+			std::fprintf(stderr, "[pathplanning_amd] HybridAStar::%s: %s\n", where, pp_last_error());
+			return false;
+		}
+		m_plannerFootprint = want; // (the planner holds a reference: the address stays taken while it is set)
+		return true;
+	}
+	pp_footprint* m_plannerFootprint = nullptr;
 	SearchParameters m_param;
 	int m_maxBatch, m_maxNodes;
 	bool isInitialized = false;

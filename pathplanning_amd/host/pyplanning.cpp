@@ -255,7 +255,13 @@ PYBIND11_MODULE(pyplanning, m)
 					throw std::invalid_argument("poses must be (n, 3)");
 				py::array_t<uint8_t> out(poses.shape(0));
 				if (poses.shape(0))
-					ppCheck(pp_check_states(v.Device(), poses.shape(0), poses.data(), out.mutable_data()));
+				{
+					pp_map* dev = v.Device();
+					if (pp_footprint* fp = v.DeviceFootprint())
+						ppCheck(pp_check_states_footprint(dev, fp, poses.shape(0), poses.data(), out.mutable_data(), nullptr));
+					else
+						ppCheck(pp_check_states(dev, poses.shape(0), poses.data(), out.mutable_data()));
+				}
 				return out;
 			})
 		.def("is_arc_valid",
@@ -264,8 +270,32 @@ PYBIND11_MODULE(pyplanning, m)
 				bool ok = v.IsArcValid(from, curvature, length, dir, &last);
 				return py::make_tuple(ok, last);
 			})
+		// vehicle footprint (include/pp_hip.h): discs (ox, oy, r) in the vehicle frame instead of the reference point against min_safe_radius
+		.def("set_footprint",
+			[](StateValidatorOccupancyMap& v, const std::vector<std::tuple<double, double, double>>& discs) {
+				std::vector<FootprintDisc> d;
+				for (const auto& t : discs)
+					d.push_back({ std::get<0>(t), std::get<1>(t), (float)std::get<2>(t) });
+				v.SetFootprint(d);
+				v.Device();
+				v.DeviceFootprint(); // bad values are refused here, not at the first check
+			})
+		.def("clear_footprint", &StateValidatorOccupancyMap::ClearFootprint)
+		.def_property_readonly("footprint",
+			[](const StateValidatorOccupancyMap& v) {
+				std::vector<std::tuple<double, double, double>> out;
+				for (const auto& d : v.GetFootprint())
+					out.emplace_back(d.ox, d.oy, (double)d.r);
+				return out;
+			})
 		.def_readwrite("min_path_interpolation_distance", &StateValidatorOccupancyMap::minPathInterpolationDistance)
 		.def_readwrite("min_safe_radius", &StateValidatorOccupancyMap::minSafeRadius);
+	m.def("rectangle_footprint", [](double length, double width, double rear_overhang, int n_discs) {
+		std::vector<std::tuple<double, double, double>> out;
+		for (const auto& d : RectangleFootprint(length, width, rear_overhang, n_discs))
+			out.emplace_back(d.ox, d.oy, (double)d.r);
+		return out;
+	}, py::arg("length"), py::arg("width"), py::arg("rear_overhang"), py::arg("n_discs"));
 
 	struct PathPlannerSE2BaseWrapper : PathPlannerSE2Base {
 		using PathPlannerSE2Base::PathPlannerSE2Base;

@@ -12,7 +12,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import RS_PATH_DTYPE, HybridParams, MapDesc, PostResult, QueryResult, SmootherParams, check, ptr
+from ._lib import RS_PATH_DTYPE, FootprintDisc, HybridParams, MapDesc, PostResult, QueryResult, SmootherParams, check, ptr
 
 
 class Status:
@@ -204,8 +204,49 @@ class OccupancyMapSet:
             pass
 
 
+class Footprint:
+    """A vehicle footprint (include/pp_hip.h, "vehicle footprint"): 1 to 8 discs (ox, oy, r) in the vehicle frame (origin = the pose's
+    reference point, x forward, y left; metres), bound to one map set.  Passed as `footprint=` to the validator's checks and to
+    HybridAStarBatch.set_footprint; {(0, 0, min_safe_radius)} is the point validator."""
+
+    def __init__(self, map_set, discs):
+        self.map = map_set
+        self.lib = map_set.lib
+        self.discs = [(float(ox), float(oy), float(np.float32(r))) for ox, oy, r in discs]
+        arr = (FootprintDisc * max(len(self.discs), 1))()
+        for i, (ox, oy, r) in enumerate(self.discs):
+            arr[i].ox, arr[i].oy, arr[i].r = ox, oy, r
+        h = C.c_void_p()
+        check(self.lib.pp_footprint_create(map_set.h, len(self.discs), arr, C.byref(h)))
+        self.h = h
+
+    @staticmethod
+    def rectangle_discs(length, width, rear_overhang, n_discs):
+        """pp_footprint_cover_rectangle: n equal discs on the long axis covering a length x width rectangle whose rear edge lies
+        rear_overhang behind the reference point (host arithmetic, no device) -> [(ox, oy, r)]"""
+        arr = (FootprintDisc * max(int(n_discs), 1))()
+        check(_lib.load().pp_footprint_cover_rectangle(float(length), float(width), float(rear_overhang), int(n_discs), arr))
+        return [(arr[i].ox, arr[i].oy, arr[i].r) for i in range(int(n_discs))]
+
+    @classmethod
+    def cover_rectangle(cls, map_set, length, width, rear_overhang, n_discs):
+        return cls(map_set, cls.rectangle_discs(length, width, rear_overhang, n_discs))
+
+    def close(self):
+        if self.h:
+            self.lib.pp_footprint_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class StateValidatorOccupancyMap:
-    """state_validator/state_validator_occupancy_map.{h,cpp}: is_state_valid / is_path_valid, batched."""
+    """state_validator/state_validator_occupancy_map.{h,cpp}: is_state_valid / is_path_valid, batched.  With `footprint=` a check
+    tests the vehicle's discs instead of the reference point against min_safe_radius (class Footprint)."""
 
     def __init__(self, map_set):
         self.map = map_set
@@ -238,20 +279,30 @@ class StateValidatorOccupancyMap:
     def get_occupancy_map(self):
         return self.map
 
-    def is_state_valid(self, poses):
-        """poses: (n, 3) array-like -> bool array; or a CUDA float64 tensor -> CUDA uint8 tensor."""
+    def is_state_valid(self, poses, footprint=None, return_clearance=False):
+        """poses: (n, 3) array-like -> bool array; or a CUDA float64 tensor -> CUDA uint8 tensor.
+        return_clearance (host arrays with a footprint): also min_i (d_i - r_i) as float32, -1 where invalid."""
         if _is_tensor(poses):
             import torch
             n = poses.numel() // 3
             out = torch.empty(n, dtype=torch.uint8, device=poses.device)
-            check(self.lib.pp_check_states_dev(self.map.h, n, _dev_ptr(poses), _dev_ptr(out)))
+            if footprint is not None:
+                check(self.lib.pp_check_states_footprint_dev(self.map.h, footprint.h, n, _dev_ptr(poses), _dev_ptr(out)))
+            else:
+                check(self.lib.pp_check_states_dev(self.map.h, n, _dev_ptr(poses), _dev_ptr(out)))
             return out
         p = _f64(poses, 3)
         out = np.empty(len(p), dtype=np.uint8)
+        if footprint is not None:
+            clear = np.empty(len(p), dtype=np.float32) if return_clearance else None
+            check(self.lib.pp_check_states_footprint(self.map.h, footprint.h, len(p), ptr(p), ptr(out), ptr(clear)))
+            return (out.astype(bool), clear) if return_clearance else out.astype(bool)
+        if return_clearance:
+            raise ValueError("return_clearance needs a footprint")
         check(self.lib.pp_check_states(self.map.h, len(p), ptr(p), ptr(out)))
         return out.astype(bool)
 
-    def is_path_valid(self, start, curvature, length, direction):
+    def is_path_valid(self, start, curvature, length, direction, footprint=None):
         """IsPathValid over constant-steer arcs.  Returns (valid, last_valid_ratio)."""
         s = _f64(start, 3)
         n = len(s)
@@ -260,7 +311,10 @@ class StateValidatorOccupancyMap:
         d = np.ascontiguousarray(np.broadcast_to(np.asarray(direction, dtype=np.int32), n))
         valid = np.empty(n, dtype=np.uint8)
         last = np.empty(n, dtype=np.float32)
-        check(self.lib.pp_check_arcs(self.map.h, n, ptr(s), ptr(k), ptr(ln), ptr(d), ptr(valid), ptr(last)))
+        if footprint is not None:
+            check(self.lib.pp_check_arcs_footprint(self.map.h, footprint.h, n, ptr(s), ptr(k), ptr(ln), ptr(d), ptr(valid), ptr(last)))
+        else:
+            check(self.lib.pp_check_arcs(self.map.h, n, ptr(s), ptr(k), ptr(ln), ptr(d), ptr(valid), ptr(last)))
         return valid.astype(bool), last
 
     def is_segment_valid(self, start_xy, end_xy):
@@ -270,20 +324,26 @@ class StateValidatorOccupancyMap:
         check(self.lib.pp_check_segments(self.map.h, len(a), ptr(a), ptr(b), ptr(valid)))
         return valid.astype(bool)
 
-    def is_rs_path_valid(self, paths):
+    def is_rs_path_valid(self, paths, footprint=None):
         """IsPathValid over Reeds-Shepp paths (records of RS_PATH_DTYPE, e.g. from ReedsSheppPaths.connect).  Returns (valid, last)."""
         p = np.ascontiguousarray(paths, dtype=RS_PATH_DTYPE).reshape(-1)
         valid = np.empty(len(p), dtype=np.uint8)
         last = np.empty(len(p), dtype=np.float32)
-        check(self.lib.pp_check_rs_paths(self.map.h, len(p), ptr(p), ptr(valid), ptr(last)))
+        if footprint is not None:
+            check(self.lib.pp_check_rs_paths_footprint(self.map.h, footprint.h, len(p), ptr(p), ptr(valid), ptr(last)))
+        else:
+            check(self.lib.pp_check_rs_paths(self.map.h, len(p), ptr(p), ptr(valid), ptr(last)))
         return valid.astype(bool), last
 
-    def is_se2_path_valid(self, start, end):
+    def is_se2_path_valid(self, start, end, footprint=None):
         """IsPathValid over PathSE2 (paths/path_se2.cpp: linear in position and heading).  Returns (valid, last)."""
         a, b = _f64(start, 3), _f64(end, 3)
         valid = np.empty(len(a), dtype=np.uint8)
         last = np.empty(len(a), dtype=np.float32)
-        check(self.lib.pp_check_se2_paths(self.map.h, len(a), ptr(a), ptr(b), ptr(valid), ptr(last)))
+        if footprint is not None:
+            check(self.lib.pp_check_se2_paths_footprint(self.map.h, footprint.h, len(a), ptr(a), ptr(b), ptr(valid), ptr(last)))
+        else:
+            check(self.lib.pp_check_se2_paths(self.map.h, len(a), ptr(a), ptr(b), ptr(valid), ptr(last)))
         return valid.astype(bool), last
 
     def count_valid_fused(self, n, seed, count_tensor):
@@ -479,6 +539,7 @@ class HybridAStarBatch:
         self._goal = np.zeros(3)
         self._seed = 0
         self._results = None
+        self.footprint = None  # set_footprint
         self.is_initialized = False
 
     def set_primitives(self, steering_angles):
@@ -486,6 +547,13 @@ class HybridAStarBatch:
         d = np.ascontiguousarray(steering_angles, dtype=np.float64)
         check(self.lib.pp_planner_set_primitives(self.h, len(d), ptr(d)))
         self.num_primitives = self.lib.pp_planner_num_primitives(self.h)
+
+    def set_footprint(self, footprint):
+        """Every validity question of the search (start pose, child poses, arc marches and their truncation, the analytic expansion)
+        goes through `footprint` (class Footprint) instead of the point validator; None restores the point validator.  Planners of the
+        one-query-per-wave kernel only (max_batch <= 64, or PP_SEARCH_ROWS=0 in the environment): others raise PPError."""
+        check(self.lib.pp_planner_set_footprint(self.h, footprint.h if footprint is not None else None))
+        self.footprint = footprint  # (keeps it alive on this side too)
 
     def initialize(self, nonholo_table=None):
         """HybridAStar::Initialize (hybrid_a_star.cpp:206-235): builds the non-holonomic table on the
