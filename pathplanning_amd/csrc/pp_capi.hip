@@ -51,31 +51,16 @@ ppd::MapView pp_map::view() const
 int pph::refresh_occupancy_views(pp_map* map, hipStream_t s)
 {
 	const size_t n = map->cells();
-	if (!map->occ8)
-		PP_HIP_TRY(hipMalloc((void**)&map->occ8, n));
+	PP_HIP_TRY(map->occ8.ensure(n));
 	int wpr = 0, nWordRows = 0;
 	pph::occ_bits_dims(map->desc.rows, map->desc.cols, wpr, nWordRows);
-	if (!map->occBits)
-		PP_HIP_TRY(hipMalloc((void**)&map->occBits, (size_t)wpr * nWordRows * 8));
+	PP_HIP_TRY(map->occBits.ensure((size_t)wpr * nWordRows * 8));
 	PP_HIP_TRY(pph::launch_occ_to_u8(s, map->occ32, map->occ8, (int64_t)n));
 	PP_HIP_TRY(pph::launch_occ_bits(s, map->occ8, map->desc.rows, map->desc.cols, map->occBits));
 	return PP_OK;
 }
 
 namespace {
-
-/// RAII device scratch for the host-pointer convenience entry points.
-struct DevBuf {
-	void* p = nullptr;
-	~DevBuf()
-	{
-		if (p)
-			(void)hipFree(p);
-	}
-	hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-	template <typename T>
-	T* as() { return (T*)p; }
-};
 
 int check_map(pp_map* map, bool needDist)
 {
@@ -99,12 +84,6 @@ void ctx_release(pp_ctx* ctx)
 	if (!ctx || __atomic_sub_fetch(&ctx->refs, 1, __ATOMIC_ACQ_REL) > 0)
 		return;
 	(void)hipSetDevice(ctx->device);
-	if (ctx->ev0)
-		(void)hipEventDestroy(ctx->ev0);
-	if (ctx->ev1)
-		(void)hipEventDestroy(ctx->ev1);
-	if (ctx->ownsStream && ctx->stream)
-		(void)hipStreamDestroy(ctx->stream);
 	delete ctx;
 }
 void map_release(pp_map* map)
@@ -113,22 +92,6 @@ void map_release(pp_map* map)
 		return;
 	(void)hipSetDevice(map->ctx->device);
 	(void)hipStreamSynchronize(map->ctx->stream);
-	if (map->d2)
-		(void)hipFree(map->d2);
-	if (map->dist)
-		(void)hipFree(map->dist);
-	if (map->pathcost)
-		(void)hipFree(map->pathcost);
-	if (map->occ8)
-		(void)hipFree(map->occ8);
-	if (map->occBits)
-		(void)hipFree(map->occBits);
-	if (map->validBits)
-		(void)hipFree(map->validBits);
-	void* more[] = { map->occ32, map->obstLabel[0], map->obstLabel[1], map->voroLabel[0], map->voroLabel[1], map->voroD2, map->voroEdge, map->gvdFlag };
-	for (void* q : more)
-		if (q)
-			(void)hipFree(q);
 	gvd_reference_free(map);
 	pp_ctx* ctx = map->ctx;
 	delete map;
@@ -168,15 +131,11 @@ int pp_ctx_create(int device, void* stream, pp_ctx** out)
 	PP_HIP_TRY(hipSetDevice(device));
 	auto ctx = std::make_unique<pp_ctx>();
 	ctx->device = device;
-	if (stream) {
-		ctx->stream = (hipStream_t)stream;
-		ctx->ownsStream = false;
-	} else {
-		PP_HIP_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-		ctx->ownsStream = true;
-	}
-	PP_HIP_TRY(hipEventCreate(&ctx->ev0));
-	PP_HIP_TRY(hipEventCreate(&ctx->ev1));
+	if (!stream)
+		PP_HIP_TRY(ctx->ownStream.create());
+	ctx->stream = stream ? (hipStream_t)stream : ctx->ownStream.get();
+	PP_HIP_TRY(ctx->ev0.create());
+	PP_HIP_TRY(ctx->ev1.create());
 	*out = ctx.release();
 	return PP_OK;
 }
@@ -266,14 +225,11 @@ int pp_map_upload_dist2(pp_map* map, const int32_t* d2_host)
 	}
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
 	const size_t n = map->cells();
-	if (!map->d2)
-		PP_HIP_TRY(hipMalloc((void**)&map->d2, n * sizeof(int32_t)));
-	if (!map->dist)
-		PP_HIP_TRY(hipMalloc((void**)&map->dist, n * sizeof(float)));
+	PP_HIP_TRY(map->d2.ensure(n * sizeof(int32_t)));
+	PP_HIP_TRY(map->dist.ensure(n * sizeof(float)));
 	PP_HIP_TRY(hipMemcpyAsync(map->d2, d2_host, n * sizeof(int32_t), hipMemcpyHostToDevice, map->ctx->stream));
 	PP_HIP_TRY(launch_d2_to_distance(map->ctx->stream, map->d2, map->dist, (int64_t)n, map->desc.resolution));
-	if (!map->validBits)
-		PP_HIP_TRY(hipMalloc((void**)&map->validBits, ((n + 63) / 64) * 8)); // whole 64-cell groups: one ballot each
+	PP_HIP_TRY(map->validBits.ensure(((n + 63) / 64) * 8)); // whole 64-cell groups: one ballot each
 	PP_HIP_TRY(launch_valid_bits(map->ctx->stream, map->dist, (int64_t)n, map->minSafeRadius, map->validBits));
 	pph::dist_changed(map);
 	PP_HIP_TRY(hipStreamSynchronize(map->ctx->stream));
@@ -288,8 +244,7 @@ int pp_map_upload_occupancy(pp_map* map, const int32_t* occ_host)
 	}
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
 	const size_t n = map->cells();
-	if (!map->occ32) // kept: pp_map_update_gvd builds the distance / Voronoi / path-cost fields from it
-		PP_HIP_TRY(hipMalloc((void**)&map->occ32, n * sizeof(int32_t)));
+	PP_HIP_TRY(map->occ32.ensure(n * sizeof(int32_t))); // kept: pp_map_update_gvd builds the distance / Voronoi / path-cost fields from it
 	PP_HIP_TRY(hipMemcpyAsync(map->occ32, occ_host, n * sizeof(int32_t), hipMemcpyHostToDevice, map->ctx->stream));
 	// for the reference-order field update (pp_map_update_gvd_ex) a whole-grid upload is "an empty map, then every occupied cell in
 	// row-major order": the reference has no such entry point (its cells only arrive through AddObstacle), so this order is ours
@@ -315,8 +270,7 @@ int pp_map_upload_path_cost(pp_map* map, const float* cost_host)
 	}
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
 	const size_t n = map->cells();
-	if (!map->pathcost)
-		PP_HIP_TRY(hipMalloc((void**)&map->pathcost, n * sizeof(float)));
+	PP_HIP_TRY(map->pathcost.ensure(n * sizeof(float)));
 	PP_HIP_TRY(hipMemcpyAsync(map->pathcost, cost_host, n * sizeof(float), hipMemcpyHostToDevice, map->ctx->stream));
 	PP_HIP_TRY(hipStreamSynchronize(map->ctx->stream));
 	return PP_OK;
@@ -371,12 +325,12 @@ int pp_check_states(pp_map* map, int64_t n, const double* poses_host, uint8_t* v
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
 	hipStream_t s = map->ctx->stream;
-	DevBuf dp, dv;
+	DeviceMem dp, dv;
 	PP_HIP_TRY(dp.alloc((size_t)n * 24));
 	PP_HIP_TRY(dv.alloc((size_t)n));
-	PP_HIP_TRY(hipMemcpyAsync(dp.p, poses_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(dp.get(), poses_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
 	PP_HIP_TRY(launch_check_states(s, map->view(), n, dp.as<double>(), dv.as<uint8_t>()));
-	PP_HIP_TRY(hipMemcpyAsync(valid_host, dv.p, (size_t)n, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(valid_host, dv.get(), (size_t)n, hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	return PP_OK;
 }
@@ -420,21 +374,21 @@ int pp_check_arcs(pp_map* map, int64_t n, const double* from_host, const double*
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
 	hipStream_t s = map->ctx->stream;
-	DevBuf df, dk, dl, dd, dv, dr;
+	DeviceMem df, dk, dl, dd, dv, dr;
 	PP_HIP_TRY(df.alloc((size_t)n * 24));
 	PP_HIP_TRY(dk.alloc((size_t)n * 8));
 	PP_HIP_TRY(dl.alloc((size_t)n * 8));
 	PP_HIP_TRY(dd.alloc((size_t)n * 4));
 	PP_HIP_TRY(dv.alloc((size_t)n));
 	PP_HIP_TRY(dr.alloc((size_t)n * 4));
-	PP_HIP_TRY(hipMemcpyAsync(df.p, from_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
-	PP_HIP_TRY(hipMemcpyAsync(dk.p, curvature_host, (size_t)n * 8, hipMemcpyHostToDevice, s));
-	PP_HIP_TRY(hipMemcpyAsync(dl.p, length_host, (size_t)n * 8, hipMemcpyHostToDevice, s));
-	PP_HIP_TRY(hipMemcpyAsync(dd.p, direction_host, (size_t)n * 4, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(df.get(), from_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(dk.get(), curvature_host, (size_t)n * 8, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(dl.get(), length_host, (size_t)n * 8, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(dd.get(), direction_host, (size_t)n * 4, hipMemcpyHostToDevice, s));
 	PP_HIP_TRY(launch_check_arcs(s, map->view(), n, df.as<double>(), dk.as<double>(), dl.as<double>(), dd.as<int32_t>(), dv.as<uint8_t>(), dr.as<float>()));
-	PP_HIP_TRY(hipMemcpyAsync(valid_host, dv.p, (size_t)n, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(valid_host, dv.get(), (size_t)n, hipMemcpyDeviceToHost, s));
 	if (last_ratio_host)
-		PP_HIP_TRY(hipMemcpyAsync(last_ratio_host, dr.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+		PP_HIP_TRY(hipMemcpyAsync(last_ratio_host, dr.get(), (size_t)n * 4, hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	return PP_OK;
 }
@@ -463,14 +417,14 @@ int pp_check_segments(pp_map* map, int64_t n, const double* from_xy_host, const 
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
 	hipStream_t s = map->ctx->stream;
-	DevBuf df, dt, dv;
+	DeviceMem df, dt, dv;
 	PP_HIP_TRY(df.alloc((size_t)n * 16));
 	PP_HIP_TRY(dt.alloc((size_t)n * 16));
 	PP_HIP_TRY(dv.alloc((size_t)n));
-	PP_HIP_TRY(hipMemcpyAsync(df.p, from_xy_host, (size_t)n * 16, hipMemcpyHostToDevice, s));
-	PP_HIP_TRY(hipMemcpyAsync(dt.p, to_xy_host, (size_t)n * 16, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(df.get(), from_xy_host, (size_t)n * 16, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(dt.get(), to_xy_host, (size_t)n * 16, hipMemcpyHostToDevice, s));
 	PP_HIP_TRY(launch_check_segments(s, map->view(), n, df.as<double>(), dt.as<double>(), dv.as<uint8_t>()));
-	PP_HIP_TRY(hipMemcpyAsync(valid_host, dv.p, (size_t)n, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(valid_host, dv.get(), (size_t)n, hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	return PP_OK;
 }
@@ -536,21 +490,21 @@ int pp_rollout_children(pp_map* map, const pp_hybrid_params* params, int32_t n_p
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
 	hipStream_t s = map->ctx->stream;
 	const size_t total = (size_t)n_parents * n_primitives;
-	DevBuf dp, dv, dpose, dkey, dcost, dlen;
+	DeviceMem dp, dv, dpose, dkey, dcost, dlen;
 	PP_HIP_TRY(dp.alloc((size_t)n_parents * 24));
 	PP_HIP_TRY(dv.alloc(total));
 	PP_HIP_TRY(dpose.alloc(total * 24));
 	PP_HIP_TRY(dkey.alloc(total * 12));
 	PP_HIP_TRY(dcost.alloc(total * 8));
 	PP_HIP_TRY(dlen.alloc(total * 8));
-	PP_HIP_TRY(hipMemcpyAsync(dp.p, parents_host, (size_t)n_parents * 24, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(dp.get(), parents_host, (size_t)n_parents * 24, hipMemcpyHostToDevice, s));
 	PP_HIP_TRY(launch_rollout(s, map->view(), rp, pt, n_parents, dp.as<double>(), dv.as<uint8_t>(), dpose.as<double>(), dkey.as<int32_t>(), dcost.as<double>(),
 		dlen.as<double>()));
-	PP_HIP_TRY(hipMemcpyAsync(valid_host, dv.p, total, hipMemcpyDeviceToHost, s));
-	PP_HIP_TRY(hipMemcpyAsync(pose_host, dpose.p, total * 24, hipMemcpyDeviceToHost, s));
-	PP_HIP_TRY(hipMemcpyAsync(key_host, dkey.p, total * 12, hipMemcpyDeviceToHost, s));
-	PP_HIP_TRY(hipMemcpyAsync(cost_host, dcost.p, total * 8, hipMemcpyDeviceToHost, s));
-	PP_HIP_TRY(hipMemcpyAsync(length_host, dlen.p, total * 8, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(valid_host, dv.get(), total, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(pose_host, dpose.get(), total * 24, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(key_host, dkey.get(), total * 12, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(cost_host, dcost.get(), total * 8, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(length_host, dlen.get(), total * 8, hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	return PP_OK;
 }
@@ -579,24 +533,24 @@ int pp_rs_solve(pp_ctx* ctx, int64_t n, const double* from_host, const double* t
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->stream;
-	DevBuf df, dt, dw, dtuv, dc, dl;
+	DeviceMem df, dt, dw, dtuv, dc, dl;
 	PP_HIP_TRY(df.alloc((size_t)n * 24));
 	PP_HIP_TRY(dt.alloc((size_t)n * 24));
 	PP_HIP_TRY(dw.alloc((size_t)n * 4));
 	PP_HIP_TRY(dtuv.alloc((size_t)n * 24));
 	PP_HIP_TRY(dc.alloc((size_t)n * 4));
 	PP_HIP_TRY(dl.alloc((size_t)n * 8));
-	PP_HIP_TRY(hipMemcpyAsync(df.p, from_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
-	PP_HIP_TRY(hipMemcpyAsync(dt.p, to_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(df.get(), from_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(dt.get(), to_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
 	PP_HIP_TRY(launch_rs_solve(s, n, df.as<double>(), dt.as<double>(), min_turning_radius, reverse_cost, forward_cost, switch_cost, dw.as<int32_t>(),
 		dtuv.as<double>(), dc.as<float>(), dl.as<double>()));
-	PP_HIP_TRY(hipMemcpyAsync(word_host, dw.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(word_host, dw.get(), (size_t)n * 4, hipMemcpyDeviceToHost, s));
 	if (tuv_host)
-		PP_HIP_TRY(hipMemcpyAsync(tuv_host, dtuv.p, (size_t)n * 24, hipMemcpyDeviceToHost, s));
+		PP_HIP_TRY(hipMemcpyAsync(tuv_host, dtuv.get(), (size_t)n * 24, hipMemcpyDeviceToHost, s));
 	if (cost_host)
-		PP_HIP_TRY(hipMemcpyAsync(cost_host, dc.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+		PP_HIP_TRY(hipMemcpyAsync(cost_host, dc.get(), (size_t)n * 4, hipMemcpyDeviceToHost, s));
 	if (seg_length_host)
-		PP_HIP_TRY(hipMemcpyAsync(seg_length_host, dl.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+		PP_HIP_TRY(hipMemcpyAsync(seg_length_host, dl.get(), (size_t)n * 8, hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	return PP_OK;
 }
@@ -674,10 +628,10 @@ int pp_nonholo_build(pp_ctx* ctx, const double lower[3], const double upper[3], 
 		return rc;
 	PP_HIP_TRY(hipSetDevice(ctx->device));
 	const size_t total = (size_t)d.nx * d.ny * d.na;
-	DevBuf dt;
+	DeviceMem dt;
 	PP_HIP_TRY(dt.alloc(total * 8));
 	PP_HIP_TRY(launch_nonholo_build(ctx->stream, d, dt.as<double>()));
-	PP_HIP_TRY(hipMemcpyAsync(table_host, dt.p, total * 8, hipMemcpyDeviceToHost, ctx->stream));
+	PP_HIP_TRY(hipMemcpyAsync(table_host, dt.get(), total * 8, hipMemcpyDeviceToHost, ctx->stream));
 	PP_HIP_TRY(hipStreamSynchronize(ctx->stream));
 	return PP_OK;
 }
@@ -728,24 +682,30 @@ int pp_obstacle_heuristic_dev(pp_map* map, int32_t n_goals, const double* goal_x
 	const bool tiles = map->occBits && wavefront_tiles_enabled() && wavefront_tiles_supported(map->desc.rows, map->desc.cols);
 	if (tiles && nSlots > 16)
 		nSlots = 16; // (the ordered kernel only takes the goals the tile form hands over)
-	DevBuf ws, dc, derr, dtiles;
+	DeviceMem ws, dc, derr, dtiles;
 	PP_HIP_TRY(ws.alloc((size_t)wsb * nSlots));
 	PP_HIP_TRY(dc.alloc((size_t)n_goals * 4));
 	PP_HIP_TRY(derr.alloc(8));
 	PP_HIP_TRY(dtiles.alloc(64 + (size_t)n_goals * 4));
-	PP_HIP_TRY(hipMemsetAsync(derr.p, 0, 8, s));
-	PP_HIP_TRY(hipMemsetAsync(dtiles.p, 0, 64, s));
-	PP_HIP_TRY(hipMemcpyAsync(dc.p, cells.data(), (size_t)n_goals * 4, hipMemcpyHostToDevice, s));
-	WavefrontPublish pub;
+	PP_HIP_TRY(hipMemsetAsync(derr.get(), 0, 8, s));
+	PP_HIP_TRY(hipMemsetAsync(dtiles.get(), 0, 64, s));
+	PP_HIP_TRY(hipMemcpyAsync(dc.get(), cells.data(), (size_t)n_goals * 4, hipMemcpyHostToDevice, s));
+	WavefrontLaunch L;
+	L.nGoals = n_goals;
+	L.goalCells = dc.as<int32_t>();
+	L.cost = cost_dev;
+	L.workspace = ws.get();
+	L.workspaceBytesPerSlot = wsb;
+	L.nSlots = nSlots;
+	L.errorFlag = derr.as<int32_t>();
 	if (tiles) {
-		pub.tilesCtl = dtiles.as<int>();
-		pub.tilesFallback = dtiles.as<int32_t>() + 16;
-		pub.occBits = map->occBits;
+		L.pub.tilesCtl = dtiles.as<int>();
+		L.pub.tilesFallback = dtiles.as<int32_t>() + 16;
+		L.pub.occBits = map->occBits;
 	}
-	PP_HIP_TRY(launch_wavefront(s, map->view(), n_goals, dc.as<int32_t>(), cost_dev, ws.p, wsb, nSlots, derr.as<int32_t>(), nullptr, false, nullptr, false, nullptr, nullptr, nullptr,
-		nullptr, pub));
+	PP_HIP_TRY(launch_wavefront(s, map->view(), L));
 	int32_t err = 0;
-	PP_HIP_TRY(hipMemcpyAsync(&err, derr.p, 4, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(&err, derr.get(), 4, hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	if (err) {
 		set_error("obstacle-heuristic open list exceeded its workspace");
@@ -770,28 +730,34 @@ int pp_obstacle_heuristic_tiles_stats(pp_map* map, int32_t n_goals, const double
 	goal_cells(map, n_goals, goal_xy_host, cells);
 	const int nSlots = n_goals < 16 ? n_goals : 16;
 	const int64_t wsb = wavefront_workspace_bytes(map->desc.rows, map->desc.cols);
-	DevBuf ws, dc, derr, dtiles, dstats;
+	DeviceMem ws, dc, derr, dtiles, dstats;
 	PP_HIP_TRY(ws.alloc((size_t)wsb * nSlots));
 	PP_HIP_TRY(dc.alloc((size_t)n_goals * 4));
 	PP_HIP_TRY(derr.alloc(8));
 	PP_HIP_TRY(dtiles.alloc(64 + (size_t)n_goals * 4));
 	PP_HIP_TRY(dstats.alloc(128));
-	PP_HIP_TRY(hipMemsetAsync(derr.p, 0, 8, s));
-	PP_HIP_TRY(hipMemsetAsync(dtiles.p, 0, 64, s));
-	PP_HIP_TRY(hipMemsetAsync(dstats.p, 0, 128, s));
-	PP_HIP_TRY(hipMemcpyAsync(dc.p, cells.data(), (size_t)n_goals * 4, hipMemcpyHostToDevice, s));
-	WavefrontPublish pub;
-	pub.tilesCtl = dtiles.as<int>();
-	pub.tilesFallback = dtiles.as<int32_t>() + 16;
-	pub.tilesStats = dstats.as<unsigned long long>();
-	pub.occBits = map->occBits;
+	PP_HIP_TRY(hipMemsetAsync(derr.get(), 0, 8, s));
+	PP_HIP_TRY(hipMemsetAsync(dtiles.get(), 0, 64, s));
+	PP_HIP_TRY(hipMemsetAsync(dstats.get(), 0, 128, s));
+	PP_HIP_TRY(hipMemcpyAsync(dc.get(), cells.data(), (size_t)n_goals * 4, hipMemcpyHostToDevice, s));
+	WavefrontLaunch L;
+	L.nGoals = n_goals;
+	L.goalCells = dc.as<int32_t>();
+	L.cost = cost_dev;
+	L.workspace = ws.get();
+	L.workspaceBytesPerSlot = wsb;
+	L.nSlots = nSlots;
+	L.errorFlag = derr.as<int32_t>();
+	L.pub.tilesCtl = dtiles.as<int>();
+	L.pub.tilesFallback = dtiles.as<int32_t>() + 16;
+	L.pub.tilesStats = dstats.as<unsigned long long>();
+	L.pub.occBits = map->occBits;
 	PP_HIP_TRY(hipEventRecord(map->ctx->ev0, s));
-	PP_HIP_TRY(launch_wavefront(s, map->view(), n_goals, dc.as<int32_t>(), cost_dev, ws.p, wsb, nSlots, derr.as<int32_t>(), nullptr, false, nullptr, false, nullptr, nullptr, nullptr,
-		nullptr, pub));
+	PP_HIP_TRY(launch_wavefront(s, map->view(), L));
 	PP_HIP_TRY(hipEventRecord(map->ctx->ev1, s));
 	int32_t err = 0;
-	PP_HIP_TRY(hipMemcpyAsync(&err, derr.p, 4, hipMemcpyDeviceToHost, s));
-	PP_HIP_TRY(hipMemcpyAsync(stats_host, dstats.p, 128, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(&err, derr.get(), 4, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(stats_host, dstats.get(), 128, hipMemcpyDeviceToHost, s));
 	if (handed_over_host) // (the list outlives the launches: only the count is set back)
 		PP_HIP_TRY(hipMemcpyAsync(handed_over_host, dtiles.as<int32_t>() + 16, (size_t)n_goals * 4, hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
@@ -818,16 +784,25 @@ int pp_obstacle_heuristic_profile(pp_map* map, int32_t n_goals, const double* go
 	const int resident = wavefront_resident_blocks();
 	int nSlots = n_goals < resident ? n_goals : resident;
 	const int64_t wsb = wavefront_workspace_bytes(map->desc.rows, map->desc.cols);
-	DevBuf ws, dc, derr, dcost, dprof;
+	DeviceMem ws, dc, derr, dcost, dprof;
 	PP_HIP_TRY(ws.alloc((size_t)wsb * nSlots));
 	PP_HIP_TRY(dc.alloc((size_t)n_goals * 4));
 	PP_HIP_TRY(derr.alloc(8));
 	PP_HIP_TRY(dcost.alloc((size_t)n_goals * map->cells() * 4));
 	PP_HIP_TRY(dprof.alloc((size_t)n_goals * 20 * 8));
-	PP_HIP_TRY(hipMemsetAsync(derr.p, 0, 8, s));
-	PP_HIP_TRY(hipMemcpyAsync(dc.p, cells.data(), (size_t)n_goals * 4, hipMemcpyHostToDevice, s));
-	PP_HIP_TRY(launch_wavefront(s, map->view(), n_goals, dc.as<int32_t>(), dcost.as<float>(), ws.p, wsb, nSlots, derr.as<int32_t>(), dprof.as<unsigned long long>()));
-	PP_HIP_TRY(hipMemcpyAsync(counters_host, dprof.p, (size_t)n_goals * 20 * 8, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemsetAsync(derr.get(), 0, 8, s));
+	PP_HIP_TRY(hipMemcpyAsync(dc.get(), cells.data(), (size_t)n_goals * 4, hipMemcpyHostToDevice, s));
+	WavefrontLaunch L;
+	L.nGoals = n_goals;
+	L.goalCells = dc.as<int32_t>();
+	L.cost = dcost.as<float>();
+	L.workspace = ws.get();
+	L.workspaceBytesPerSlot = wsb;
+	L.nSlots = nSlots;
+	L.errorFlag = derr.as<int32_t>();
+	L.prof = dprof.as<unsigned long long>();
+	PP_HIP_TRY(launch_wavefront(s, map->view(), L));
+	PP_HIP_TRY(hipMemcpyAsync(counters_host, dprof.get(), (size_t)n_goals * 20 * 8, hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	return PP_OK;
 }
@@ -843,12 +818,12 @@ int pp_obstacle_heuristic(pp_map* map, int32_t n_goals, const double* goal_xy_ho
 	if (n_goals == 0)
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
-	DevBuf dcost;
+	DeviceMem dcost;
 	const size_t bytes = (size_t)n_goals * map->cells() * sizeof(float);
 	PP_HIP_TRY(dcost.alloc(bytes));
 	if (int rc = pp_obstacle_heuristic_dev(map, n_goals, goal_xy_host, dcost.as<float>()))
 		return rc;
-	PP_HIP_TRY(hipMemcpy(cost_host, dcost.p, bytes, hipMemcpyDeviceToHost));
+	PP_HIP_TRY(hipMemcpy(cost_host, dcost.get(), bytes, hipMemcpyDeviceToHost));
 	return PP_OK;
 }
 
@@ -875,17 +850,17 @@ int pp_knn(pp_ctx* ctx, int64_t n_points, const double* points_host, int64_t n_q
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->stream;
-	DevBuf dp, dq, di, dd;
+	DeviceMem dp, dq, di, dd;
 	PP_HIP_TRY(dp.alloc((size_t)n_points * 16));
 	PP_HIP_TRY(dq.alloc((size_t)n_queries * 16));
 	PP_HIP_TRY(di.alloc((size_t)n_queries * k * 4));
 	PP_HIP_TRY(dd.alloc((size_t)n_queries * k * 8));
 	if (n_points)
-		PP_HIP_TRY(hipMemcpyAsync(dp.p, points_host, (size_t)n_points * 16, hipMemcpyHostToDevice, s));
-	PP_HIP_TRY(hipMemcpyAsync(dq.p, queries_host, (size_t)n_queries * 16, hipMemcpyHostToDevice, s));
+		PP_HIP_TRY(hipMemcpyAsync(dp.get(), points_host, (size_t)n_points * 16, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(dq.get(), queries_host, (size_t)n_queries * 16, hipMemcpyHostToDevice, s));
 	PP_HIP_TRY(launch_knn(s, n_points, dp.as<double>(), n_queries, dq.as<double>(), k, di.as<int32_t>(), dd.as<double>()));
-	PP_HIP_TRY(hipMemcpyAsync(idx_host, di.p, (size_t)n_queries * k * 4, hipMemcpyDeviceToHost, s));
-	PP_HIP_TRY(hipMemcpyAsync(d2_host, dd.p, (size_t)n_queries * k * 8, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(idx_host, di.get(), (size_t)n_queries * k * 4, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(d2_host, dd.get(), (size_t)n_queries * k * 8, hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	return PP_OK;
 }

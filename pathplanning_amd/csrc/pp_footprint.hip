@@ -144,18 +144,6 @@ __global__ void __launch_bounds__(kBlock) k_check_se2_paths_footprint(MapView m,
 	}
 }
 
-struct DevBuf {
-	void* p = nullptr;
-	~DevBuf()
-	{
-		if (p)
-			(void)hipFree(p);
-	}
-	hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-	template <typename T>
-	T* as() { return (T*)p; }
-};
-
 int bad(const char* msg)
 {
 	set_error(msg);
@@ -179,8 +167,7 @@ int footprint_prepare(pp_map* map, pp_footprint* fp, bool needBits)
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
 	const int64_t cells = (int64_t)map->cells();
 	fp->wordsPer = (uint32_t)(((cells + 63) / 64) * 2); // whole 64-cell groups, as pp_map::validBits
-	if (!fp->bits)
-		PP_HIP_TRY(hipMalloc((void**)&fp->bits, (size_t)fp->nRadii * fp->wordsPer * 4));
+	PP_HIP_TRY(fp->bits.ensure((size_t)fp->nRadii * fp->wordsPer * 4));
 	for (int k = 0; k < fp->nRadii; k++)
 		PP_HIP_TRY(launch_valid_bits(map->ctx->stream, map->dist, cells, fp->radii[k], fp->bits + (size_t)k * fp->wordsPer));
 	fp->bitsBuilt = true;
@@ -301,16 +288,16 @@ int pp_check_states_footprint(pp_map* map, pp_footprint* fp, int64_t n, const do
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
 	hipStream_t s = map->ctx->stream;
-	DevBuf dp, dv, dc;
+	pph::DeviceMem dp, dv, dc;
 	PP_HIP_TRY(dp.alloc((size_t)n * 24));
 	PP_HIP_TRY(dv.alloc((size_t)n));
 	if (clearance_host)
 		PP_HIP_TRY(dc.alloc((size_t)n * 4));
-	PP_HIP_TRY(hipMemcpyAsync(dp.p, poses_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(dp.get(), poses_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
 	PP_HIP_TRY(pph::launch_check_states_footprint(s, map->view(), fp, n, dp.as<double>(), dv.as<uint8_t>(), dc.as<float>()));
-	PP_HIP_TRY(hipMemcpyAsync(valid_host, dv.p, (size_t)n, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(valid_host, dv.get(), (size_t)n, hipMemcpyDeviceToHost, s));
 	if (clearance_host)
-		PP_HIP_TRY(hipMemcpyAsync(clearance_host, dc.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+		PP_HIP_TRY(hipMemcpyAsync(clearance_host, dc.get(), (size_t)n * 4, hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	return PP_OK;
 }
@@ -342,23 +329,23 @@ int pp_check_arcs_footprint(pp_map* map, pp_footprint* fp, int64_t n, const doub
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
 	hipStream_t s = map->ctx->stream;
-	DevBuf df, dk, dl, dd, dv, dr;
+	pph::DeviceMem df, dk, dl, dd, dv, dr;
 	PP_HIP_TRY(df.alloc((size_t)n * 24));
 	PP_HIP_TRY(dk.alloc((size_t)n * 8));
 	PP_HIP_TRY(dl.alloc((size_t)n * 8));
 	PP_HIP_TRY(dd.alloc((size_t)n * 4));
 	PP_HIP_TRY(dv.alloc((size_t)n));
 	PP_HIP_TRY(dr.alloc((size_t)n * 4));
-	PP_HIP_TRY(hipMemcpyAsync(df.p, from_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
-	PP_HIP_TRY(hipMemcpyAsync(dk.p, curvature_host, (size_t)n * 8, hipMemcpyHostToDevice, s));
-	PP_HIP_TRY(hipMemcpyAsync(dl.p, length_host, (size_t)n * 8, hipMemcpyHostToDevice, s));
-	PP_HIP_TRY(hipMemcpyAsync(dd.p, direction_host, (size_t)n * 4, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(df.get(), from_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(dk.get(), curvature_host, (size_t)n * 8, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(dl.get(), length_host, (size_t)n * 8, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(dd.get(), direction_host, (size_t)n * 4, hipMemcpyHostToDevice, s));
 	hipLaunchKernelGGL(k_check_arcs_footprint, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, map->view(), fp->fp, n, df.as<double>(), dk.as<double>(), dl.as<double>(),
 		dd.as<int32_t>(), dv.as<uint8_t>(), dr.as<float>());
 	PP_HIP_TRY(hipGetLastError());
-	PP_HIP_TRY(hipMemcpyAsync(valid_host, dv.p, (size_t)n, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(valid_host, dv.get(), (size_t)n, hipMemcpyDeviceToHost, s));
 	if (last_ratio_host)
-		PP_HIP_TRY(hipMemcpyAsync(last_ratio_host, dr.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+		PP_HIP_TRY(hipMemcpyAsync(last_ratio_host, dr.get(), (size_t)n * 4, hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	return PP_OK;
 }
@@ -387,16 +374,16 @@ int pp_check_rs_paths_footprint(pp_map* map, pp_footprint* fp, int64_t n, const 
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
 	hipStream_t s = map->ctx->stream;
-	DevBuf dp, dv, dl;
+	pph::DeviceMem dp, dv, dl;
 	PP_HIP_TRY(dp.alloc((size_t)n * sizeof(pp_rs_path)));
 	PP_HIP_TRY(dv.alloc((size_t)n));
 	PP_HIP_TRY(dl.alloc((size_t)n * 4));
-	PP_HIP_TRY(hipMemcpyAsync(dp.p, paths_host, (size_t)n * sizeof(pp_rs_path), hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(dp.get(), paths_host, (size_t)n * sizeof(pp_rs_path), hipMemcpyHostToDevice, s));
 	hipLaunchKernelGGL(k_check_rs_paths_footprint, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, map->view(), fp->fp, n, dp.as<pp_rs_path>(), dv.as<uint8_t>(), dl.as<float>());
 	PP_HIP_TRY(hipGetLastError());
-	PP_HIP_TRY(hipMemcpyAsync(valid_host, dv.p, (size_t)n, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(valid_host, dv.get(), (size_t)n, hipMemcpyDeviceToHost, s));
 	if (last_ratio_host)
-		PP_HIP_TRY(hipMemcpyAsync(last_ratio_host, dl.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+		PP_HIP_TRY(hipMemcpyAsync(last_ratio_host, dl.get(), (size_t)n * 4, hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	return PP_OK;
 }
@@ -411,19 +398,19 @@ int pp_check_se2_paths_footprint(pp_map* map, pp_footprint* fp, int64_t n, const
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
 	hipStream_t s = map->ctx->stream;
-	DevBuf df, dt, dv, dl;
+	pph::DeviceMem df, dt, dv, dl;
 	PP_HIP_TRY(df.alloc((size_t)n * 24));
 	PP_HIP_TRY(dt.alloc((size_t)n * 24));
 	PP_HIP_TRY(dv.alloc((size_t)n));
 	PP_HIP_TRY(dl.alloc((size_t)n * 4));
-	PP_HIP_TRY(hipMemcpyAsync(df.p, from_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
-	PP_HIP_TRY(hipMemcpyAsync(dt.p, to_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(df.get(), from_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(dt.get(), to_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
 	hipLaunchKernelGGL(k_check_se2_paths_footprint, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, map->view(), fp->fp, n, df.as<double>(), dt.as<double>(), dv.as<uint8_t>(),
 		dl.as<float>());
 	PP_HIP_TRY(hipGetLastError());
-	PP_HIP_TRY(hipMemcpyAsync(valid_host, dv.p, (size_t)n, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(valid_host, dv.get(), (size_t)n, hipMemcpyDeviceToHost, s));
 	if (last_ratio_host)
-		PP_HIP_TRY(hipMemcpyAsync(last_ratio_host, dl.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+		PP_HIP_TRY(hipMemcpyAsync(last_ratio_host, dl.get(), (size_t)n * 4, hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	return PP_OK;
 }
@@ -439,7 +426,6 @@ void footprint_release(pp_footprint* fp)
 	if (fp->bits) {
 		(void)hipSetDevice(map->ctx->device);
 		(void)hipStreamSynchronize(map->ctx->stream);
-		(void)hipFree(fp->bits);
 	}
 	delete fp;
 	map_release(map);

@@ -657,16 +657,6 @@ __global__ void __launch_bounds__(GT) k_grid_astar(GridArgs A, const GridQuery* 
 	}
 }
 
-struct Buf {
-	void* p = nullptr;
-	~Buf()
-	{
-		if (p)
-			(void)hipFree(p);
-	}
-	hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
-
 } // namespace
 
 int pp_grid_astar_batch(pp_map* map, int32_t n_queries, const int32_t* init_cells, const int32_t* goal_cells, int32_t bidirectional,
@@ -746,30 +736,31 @@ int pp_grid_astar_batch(pp_map* map, int32_t n_queries, const int32_t* init_cell
 		set_error("not enough device memory for one grid search workspace");
 		return PP_ERR_CAPACITY;
 	}
-	Buf ws, dq, dout, dpaths, dexp, dexpR, dcnt;
+	pph::DeviceMem ws, dq, dout, dpaths, dexp, dexpR, dcnt;
+	const auto atLeast16 = [](size_t bytes) { return bytes < 16 ? (size_t)16 : bytes; }; // the kernel is handed a valid 16-byte block even for an empty output
 	PP_HIP_TRY(ws.alloc((size_t)slots * (size_t)A.slotBytes));
 	PP_HIP_TRY(dq.alloc(hq.size() * sizeof(GridQuery)));
 	PP_HIP_TRY(dout.alloc(hq.size() * sizeof(GridOut)));
-	PP_HIP_TRY(dpaths.alloc((size_t)n_queries * (size_t)max_path * 8));
+	PP_HIP_TRY(dpaths.alloc(atLeast16((size_t)n_queries * (size_t)max_path * 8)));
 	if (expanded)
-		PP_HIP_TRY(dexp.alloc((size_t)n_queries * (size_t)max_expanded * 8));
+		PP_HIP_TRY(dexp.alloc(atLeast16((size_t)n_queries * (size_t)max_expanded * 8)));
 	if (expanded_reverse && A.bidirectional)
-		PP_HIP_TRY(dexpR.alloc((size_t)n_queries * (size_t)max_expanded * 8));
+		PP_HIP_TRY(dexpR.alloc(atLeast16((size_t)n_queries * (size_t)max_expanded * 8)));
 	PP_HIP_TRY(dcnt.alloc(16));
-	PP_HIP_TRY(hipMemsetAsync(ws.p, 0, (size_t)slots * (size_t)A.slotBytes, s)); // epoch 0 everywhere
-	PP_HIP_TRY(hipMemsetAsync(dcnt.p, 0, 16, s));
-	PP_HIP_TRY(hipMemcpyAsync(dq.p, hq.data(), hq.size() * sizeof(GridQuery), hipMemcpyHostToDevice, s));
-	hipLaunchKernelGGL(k_grid_astar, dim3((unsigned)slots), dim3(GT), ldsBytes, s, A, (const GridQuery*)dq.p, (GridOut*)dout.p, (int32_t*)dpaths.p,
-		expanded ? (int32_t*)dexp.p : nullptr, dexpR.p ? (int32_t*)dexpR.p : nullptr, (char*)ws.p, (int*)dcnt.p);
+	PP_HIP_TRY(hipMemsetAsync(ws.get(), 0, (size_t)slots * (size_t)A.slotBytes, s)); // epoch 0 everywhere
+	PP_HIP_TRY(hipMemsetAsync(dcnt.get(), 0, 16, s));
+	PP_HIP_TRY(hipMemcpyAsync(dq.get(), hq.data(), hq.size() * sizeof(GridQuery), hipMemcpyHostToDevice, s));
+	hipLaunchKernelGGL(k_grid_astar, dim3((unsigned)slots), dim3(GT), ldsBytes, s, A, (const GridQuery*)dq.get(), (GridOut*)dout.get(), (int32_t*)dpaths.get(),
+		expanded ? (int32_t*)dexp.get() : nullptr, dexpR.get() ? (int32_t*)dexpR.get() : nullptr, (char*)ws.get(), (int*)dcnt.get());
 	PP_HIP_TRY(hipGetLastError());
 	std::vector<GridOut> ho(hq.size());
-	PP_HIP_TRY(hipMemcpyAsync(ho.data(), dout.p, ho.size() * sizeof(GridOut), hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(ho.data(), dout.get(), ho.size() * sizeof(GridOut), hipMemcpyDeviceToHost, s));
 	if (max_path > 0)
-		PP_HIP_TRY(hipMemcpyAsync(paths, dpaths.p, (size_t)n_queries * (size_t)max_path * 8, hipMemcpyDeviceToHost, s));
+		PP_HIP_TRY(hipMemcpyAsync(paths, dpaths.get(), (size_t)n_queries * (size_t)max_path * 8, hipMemcpyDeviceToHost, s));
 	if (expanded)
-		PP_HIP_TRY(hipMemcpyAsync(expanded, dexp.p, (size_t)n_queries * (size_t)max_expanded * 8, hipMemcpyDeviceToHost, s));
-	if (dexpR.p)
-		PP_HIP_TRY(hipMemcpyAsync(expanded_reverse, dexpR.p, (size_t)n_queries * (size_t)max_expanded * 8, hipMemcpyDeviceToHost, s));
+		PP_HIP_TRY(hipMemcpyAsync(expanded, dexp.get(), (size_t)n_queries * (size_t)max_expanded * 8, hipMemcpyDeviceToHost, s));
+	if (dexpR.get())
+		PP_HIP_TRY(hipMemcpyAsync(expanded_reverse, dexpR.get(), (size_t)n_queries * (size_t)max_expanded * 8, hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	bool overflow = false;
 	for (size_t i = 0; i < ho.size(); i++) {

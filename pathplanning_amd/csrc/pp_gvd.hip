@@ -301,21 +301,16 @@ __global__ void __launch_bounds__(kBlock) k_path_cost(int64_t n, const int32_t* 
 	}
 }
 
-hipError_t ensure(void** p, size_t bytes)
-{
-	return *p ? hipSuccess : hipMalloc(p, bytes ? bytes : 1);
-}
-
 /// exact transform of one source set: labels into label[0], squared distances into d2; label[1] is the row pass's scratch
-hipError_t launch_edt(pp_map* map, const int32_t* occ, const uint8_t* edge, uint32_t* label[2], int32_t* d2)
+hipError_t launch_edt(pp_map* map, const int32_t* occ, const uint8_t* edge, const pph::Dev<uint32_t> (&label)[2], int32_t* d2)
 {
 	hipStream_t s = map->ctx->stream;
 	const int rows = map->desc.rows, cols = map->desc.cols;
 	hipError_t e = hipMemsetAsync(map->gvdFlag + 2, 0, 4, s);
 	if (e != hipSuccess)
 		return e;
-	hipLaunchKernelGGL(k_edt_rows, dim3(rows < 4096 ? rows : 4096), dim3(kBlock), 0, s, rows, cols, occ, edge, (int32_t*)label[1], map->gvdFlag + 2);
-	hipLaunchKernelGGL(k_edt_cols, dim3(grid_for((int64_t)rows * cols, kBlock)), dim3(kBlock), 0, s, rows, cols, (const int32_t*)label[1], map->gvdFlag + 2, label[0], d2);
+	hipLaunchKernelGGL(k_edt_rows, dim3(rows < 4096 ? rows : 4096), dim3(kBlock), 0, s, rows, cols, occ, edge, label[1].as<int32_t>(), map->gvdFlag + 2);
+	hipLaunchKernelGGL(k_edt_cols, dim3(grid_for((int64_t)rows * cols, kBlock)), dim3(kBlock), 0, s, rows, cols, label[1].as<const int32_t>(), map->gvdFlag + 2, label[0].get(), d2);
 	return hipGetLastError();
 }
 
@@ -423,35 +418,20 @@ int pp_rasterize_cells(pp_map* map, int32_t n_segments, const double* p0_xy_host
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
 	hipStream_t s = map->ctx->stream;
-	double *d0 = nullptr, *d1 = nullptr;
-	int32_t *dc = nullptr, *dn = nullptr;
 	const size_t cellBytes = (size_t)n_segments * cap_per_segment * 8;
-	hipError_t e = hipMalloc((void**)&d0, (size_t)n_segments * 16);
-	if (e == hipSuccess)
-		e = hipMalloc((void**)&d1, (size_t)n_segments * 16);
-	if (e == hipSuccess)
-		e = hipMalloc((void**)&dc, cellBytes);
-	if (e == hipSuccess)
-		e = hipMalloc((void**)&dn, (size_t)n_segments * 4);
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(d0, p0_xy_host, (size_t)n_segments * 16, hipMemcpyHostToDevice, s);
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(d1, p1_xy_host, (size_t)n_segments * 16, hipMemcpyHostToDevice, s);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_rasterize_list, dim3((n_segments + 63) / 64), dim3(64), 0, s, map->view(), n_segments, d0, d1, cap_per_segment, dc, dn);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(cells_host, dc, cellBytes, hipMemcpyDeviceToHost, s);
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(count_host, dn, (size_t)n_segments * 4, hipMemcpyDeviceToHost, s);
-	if (e == hipSuccess)
-		e = hipStreamSynchronize(s);
-	for (void* q : { (void*)d0, (void*)d1, (void*)dc, (void*)dn })
-		if (q)
-			(void)hipFree(q);
-	if (e != hipSuccess)
-		return pph::hip_fail(e, "pp_rasterize_cells");
+	pph::DeviceMem d0, d1, dc, dn;
+	PP_HIP_TRY(d0.alloc((size_t)n_segments * 16));
+	PP_HIP_TRY(d1.alloc((size_t)n_segments * 16));
+	PP_HIP_TRY(dc.alloc(cellBytes));
+	PP_HIP_TRY(dn.alloc((size_t)n_segments * 4));
+	PP_HIP_TRY(hipMemcpyAsync(d0.get(), p0_xy_host, (size_t)n_segments * 16, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(d1.get(), p1_xy_host, (size_t)n_segments * 16, hipMemcpyHostToDevice, s));
+	hipLaunchKernelGGL(k_rasterize_list, dim3((n_segments + 63) / 64), dim3(64), 0, s, map->view(), n_segments, d0.as<double>(), d1.as<double>(), cap_per_segment, dc.as<int32_t>(),
+		dn.as<int32_t>());
+	PP_HIP_TRY(hipGetLastError());
+	PP_HIP_TRY(hipMemcpyAsync(cells_host, dc.get(), cellBytes, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(count_host, dn.get(), (size_t)n_segments * 4, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipStreamSynchronize(s));
 	return PP_OK;
 }
 
@@ -465,7 +445,7 @@ int pp_map_set_cells(pp_map* map, int64_t n_cells, const int32_t* cells_host, in
 	hipStream_t s = map->ctx->stream;
 	const size_t n = map->cells();
 	if (!map->occ32) {
-		PP_HIP_TRY(hipMalloc((void**)&map->occ32, n * 4));
+		PP_HIP_TRY(map->occ32.ensure(n * 4));
 		PP_HIP_TRY(hipMemsetAsync(map->occ32, 0xFF, n * 4, s));
 	}
 	for (int64_t i = 0; i < n_cells; i++) { // the order of the edits is part of the reference's result (reference-order mode)
@@ -474,18 +454,12 @@ int pp_map_set_cells(pp_map* map, int64_t n_cells, const int32_t* cells_host, in
 			journal_edit(map, r * map->desc.cols + c, value);
 	}
 	if (n_cells > 0) {
-		int32_t* dc = nullptr;
-		PP_HIP_TRY(hipMalloc((void**)&dc, (size_t)n_cells * 8));
-		hipError_t e = hipMemcpyAsync(dc, cells_host, (size_t)n_cells * 8, hipMemcpyHostToDevice, s);
-		if (e == hipSuccess) {
-			hipLaunchKernelGGL(k_set_cells, dim3(grid_for(n_cells, kBlock)), dim3(kBlock), 0, s, map->desc.rows, map->desc.cols, n_cells, dc, value, map->occ32);
-			e = hipGetLastError();
-		}
-		if (e == hipSuccess)
-			e = hipStreamSynchronize(s);
-		(void)hipFree(dc);
-		if (e != hipSuccess)
-			return pph::hip_fail(e, "pp_map_set_cells");
+		pph::DeviceMem dc;
+		PP_HIP_TRY(dc.alloc((size_t)n_cells * 8));
+		PP_HIP_TRY(hipMemcpyAsync(dc.get(), cells_host, (size_t)n_cells * 8, hipMemcpyHostToDevice, s));
+		hipLaunchKernelGGL(k_set_cells, dim3(grid_for(n_cells, kBlock)), dim3(kBlock), 0, s, map->desc.rows, map->desc.cols, n_cells, dc.as<int32_t>(), value, map->occ32.get());
+		PP_HIP_TRY(hipGetLastError());
+		PP_HIP_TRY(hipStreamSynchronize(s));
 	}
 	if (int rc = pph::refresh_occupancy_views(map, s))
 		return rc;
@@ -527,17 +501,17 @@ int pp_map_update_gvd_ex(pp_map* map, float alpha, float d_max, int32_t mode, in
 		set_error("grids beyond 32767 cells a side are not supported (squared distances are int32, as in the reference)");
 		return PP_ERR_CAPACITY;
 	}
-	PP_HIP_TRY(ensure((void**)&map->gvdFlag, 64));
+	PP_HIP_TRY(map->gvdFlag.ensure(64));
 	for (int k = 0; k < 2; k++) {
-		PP_HIP_TRY(ensure((void**)&map->obstLabel[k], n * 4));
-		PP_HIP_TRY(ensure((void**)&map->voroLabel[k], n * 4));
+		PP_HIP_TRY(map->obstLabel[k].ensure(n * 4));
+		PP_HIP_TRY(map->voroLabel[k].ensure(n * 4));
 	}
-	PP_HIP_TRY(ensure((void**)&map->d2, n * 4));
-	PP_HIP_TRY(ensure((void**)&map->voroD2, n * 4));
-	PP_HIP_TRY(ensure((void**)&map->voroEdge, n));
-	PP_HIP_TRY(ensure((void**)&map->dist, n * 4));
-	PP_HIP_TRY(ensure((void**)&map->pathcost, n * 4));
-	PP_HIP_TRY(ensure((void**)&map->validBits, ((n + 63) / 64) * 8));
+	PP_HIP_TRY(map->d2.ensure(n * 4));
+	PP_HIP_TRY(map->voroD2.ensure(n * 4));
+	PP_HIP_TRY(map->voroEdge.ensure(n));
+	PP_HIP_TRY(map->dist.ensure(n * 4));
+	PP_HIP_TRY(map->pathcost.ensure(n * 4));
+	PP_HIP_TRY(map->validBits.ensure(((n + 63) / 64) * 8));
 	const int grid = grid_for((int64_t)n, kBlock);
 	long long work = 0;
 	if (mode == PP_GVD_REFERENCE_ORDER) {
@@ -613,8 +587,8 @@ int pp_map_upload_nearest_cells(pp_map* map, const int32_t* nearest_obstacle_hos
 	}
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
 	const size_t n = map->cells();
-	PP_HIP_TRY(ensure((void**)&map->obstLabel[0], n * 4));
-	PP_HIP_TRY(ensure((void**)&map->voroLabel[0], n * 4));
+	PP_HIP_TRY(map->obstLabel[0].ensure(n * 4));
+	PP_HIP_TRY(map->voroLabel[0].ensure(n * 4));
 	std::vector<uint32_t> a(n), b(n);
 	for (size_t i = 0; i < n; i++) {
 		a[i] = nearest_obstacle_host[2 * i] < 0 ? kNone : ((uint32_t)nearest_obstacle_host[2 * i] << 16) | (uint32_t)nearest_obstacle_host[2 * i + 1];
@@ -638,27 +612,17 @@ int pp_path_cost_update(pp_map* map, const int32_t* obstacle_d2_host, const int3
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
 	hipStream_t s = map->ctx->stream;
 	const size_t n = map->cells();
-	int32_t *a = nullptr, *b = nullptr;
-	PP_HIP_TRY(hipMalloc((void**)&a, n * 4));
-	hipError_t e = hipMalloc((void**)&b, n * 4);
-	if (e == hipSuccess)
-		e = ensure((void**)&map->pathcost, n * 4);
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(a, obstacle_d2_host, n * 4, hipMemcpyHostToDevice, s);
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(b, voronoi_d2_host, n * 4, hipMemcpyHostToDevice, s);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_path_cost, dim3(grid_for((int64_t)n, kBlock)), dim3(kBlock), 0, s, (int64_t)n, a, b, map->desc.resolution, alpha, d_max, map->pathcost);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess && path_cost_host)
-		e = hipMemcpyAsync(path_cost_host, map->pathcost, n * 4, hipMemcpyDeviceToHost, s);
-	if (e == hipSuccess)
-		e = hipStreamSynchronize(s);
-	(void)hipFree(a);
-	(void)hipFree(b);
-	if (e != hipSuccess)
-		return pph::hip_fail(e, "pp_path_cost_update");
+	pph::DeviceMem a, b;
+	PP_HIP_TRY(a.alloc(n * 4));
+	PP_HIP_TRY(b.alloc(n * 4));
+	PP_HIP_TRY(map->pathcost.ensure(n * 4));
+	PP_HIP_TRY(hipMemcpyAsync(a.get(), obstacle_d2_host, n * 4, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(b.get(), voronoi_d2_host, n * 4, hipMemcpyHostToDevice, s));
+	hipLaunchKernelGGL(k_path_cost, dim3(grid_for((int64_t)n, kBlock)), dim3(kBlock), 0, s, (int64_t)n, a.as<int32_t>(), b.as<int32_t>(), map->desc.resolution, alpha, d_max, map->pathcost.get());
+	PP_HIP_TRY(hipGetLastError());
+	if (path_cost_host)
+		PP_HIP_TRY(hipMemcpyAsync(path_cost_host, map->pathcost, n * 4, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipStreamSynchronize(s));
 	return PP_OK;
 }
 

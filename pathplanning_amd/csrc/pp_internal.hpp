@@ -22,6 +22,67 @@ int hip_fail(hipError_t e, const char* what);
 			return pph::hip_fail(_e, #expr);   \
 	} while (0)
 
+// ---- owners of GPU resources -----------------------------------------------
+// Move-only; the destructor releases.  Everything on the host side of libpphip.so that allocates device or pinned memory, or creates
+// an event or a stream, holds it in one of these: no function frees by hand, and an early return cannot leak.
+template <typename H, hipError_t (*Release)(H)>
+class Owner {
+protected:
+	H h_ = nullptr;
+
+public:
+	Owner() = default;
+	Owner(Owner&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+	~Owner() { reset(); }
+	void reset()
+	{
+		if (h_)
+			(void)Release(h_);
+		h_ = nullptr;
+	}
+	H get() const { return h_; }
+};
+struct DeviceMem : Owner<void*, hipFree> {
+	/// a zero-byte request still yields a valid pointer
+	hipError_t alloc(size_t bytes)
+	{
+		reset();
+		return hipMalloc(&h_, bytes ? bytes : 1);
+	}
+	/// allocates only if empty
+	hipError_t ensure(size_t bytes) { return h_ ? hipSuccess : alloc(bytes); }
+	template <typename T>
+	T* as() const { return (T*)h_; }
+};
+/// a DeviceMem that reads as a T* (the members of the long-lived handles)
+template <typename T>
+struct Dev : DeviceMem {
+	T* get() const { return (T*)h_; }
+	operator T*() const { return (T*)h_; }
+	T* operator->() const { return (T*)h_; }
+};
+/// pinned host memory, read as a T*
+template <typename T>
+struct Pinned : Owner<void*, hipHostFree> {
+	hipError_t alloc(size_t bytes)
+	{
+		reset();
+		return hipHostMalloc(&h_, bytes ? bytes : 1, hipHostMallocDefault);
+	}
+	T* get() const { return (T*)h_; }
+	operator T*() const { return (T*)h_; }
+};
+struct Event : Owner<hipEvent_t, hipEventDestroy> {
+	hipError_t create(unsigned flags = hipEventDefault) { return h_ ? hipSuccess : hipEventCreateWithFlags(&h_, flags); }
+	operator hipEvent_t() const { return h_; }
+};
+/// non-blocking streams (all of this library's are)
+struct Stream : Owner<hipStream_t, hipStreamDestroy> {
+	hipError_t create() { return h_ ? hipSuccess : hipStreamCreateWithFlags(&h_, hipStreamNonBlocking); }
+	hipError_t create(int priority) { return h_ ? hipSuccess : hipStreamCreateWithPriority(&h_, hipStreamNonBlocking, priority); }
+	operator hipStream_t() const { return h_; }
+};
+
 constexpr int kMaxPrimitives = 128;
 struct PrimTable {
 	int n;
@@ -73,13 +134,6 @@ int wavefront_resident_blocks();
 /// one empty dispatch of the wavefront kernel (no goal to take): makes the stream's queue allocate the kernel's scratch now;
 /// ctlDev: >= 8 zeroed bytes of device memory (error flag, goal counter)
 hipError_t warm_up_wavefront(hipStream_t s, const ppd::MapView& m, int32_t* ctlDev);
-/// Runs nGoals wavefronts; goalCells[g] = row*cols+col or -1 (goal outside the map -> field stays +inf).
-/// orderStartsDev / orderOutDev / doneCounterDev / orderKeysDev[nGoals] (optional, nGoals <= 4096): the last workgroup writes the goal indices ordered by
-/// decreasing field value at the start pose (x, y, theta triples) -- the planner's hand-out order; *doneCounterDev must be 0.
-/// goalPosesDev (optional): (x, y, theta) triples from which the kernel derives the goal cells itself (goalCellsDev unused);
-/// countersZeroed: the caller has already cleared errorFlagDev[0..1] on the stream.
-/// tiledOut: costDev is [nGoals][field_tiled_elems] in the 8 x 8-tiled layout of pp_device.hpp (what the search kernel
-/// reads); otherwise [nGoals][rows*cols] row-major (the public a8 entry points).
 /// Pipeline use of the wavefront kernel (pp_pipeline.hpp): entry i of a launch works on field slot slotList[i] (goal pose and output
 /// field are indexed by the slot), and every finished slot is appended to the ready ring the search grid consumes.
 constexpr int kSlotBits = 20;                 // pipeline list / ring entries: field slot in the low bits, the slot's generation above
@@ -131,15 +185,32 @@ int wavefront_tiles_resident_blocks(int rows, int cols);
 /// words of global memory per wave of a launch for the tile queue (0: the map is small enough for the queue to stay in LDS)
 size_t wavefront_tiles_queue_words(int rows, int cols);
 hipError_t warm_up_wavefront_tiles(hipStream_t s, const ppd::MapView& m, int* ctlDev);
-hipError_t launch_wavefront_tiles(hipStream_t s, const ppd::MapView& m, int nGoals, const int32_t* goalCellsDev, float* costDev, bool tiledOut, const double* goalPosesDev,
-	const double* orderStartsDev, float* orderKeysDev, const WavefrontPublish& pub);
+/// What launch_wavefront runs: nGoals wavefronts.  Every pointer is device memory unless it says otherwise; a caller names the fields it sets.
+struct WavefrontLaunch {
+	int nGoals = 0;
+	const int32_t* goalCells = nullptr; // [nGoals] row * cols + col, or -1 (goal outside the map -> field stays +inf)
+	const double* goalPoses = nullptr;  // instead: (x, y, theta) triples from which the kernel derives the goal cells itself (goalCells unused)
+	float* cost = nullptr;              // [nGoals][rows * cols] row-major (the public a8 entry points), or ...
+	bool tiledOut = false;              // ... [nGoals][field_tiled_elems] in the 8 x 8-tiled layout of pp_device.hpp (what the search kernel reads)
+	void* workspace = nullptr;          // nSlots x workspaceBytesPerSlot (wavefront_workspace_bytes)
+	int64_t workspaceBytesPerSlot = 0;
+	int nSlots = 0;
+	int32_t* errorFlag = nullptr;       // {overflow flag, next-goal counter (unless pub.goalCounter)}
+	bool countersZeroed = false;        // the caller has already cleared errorFlag[0..1] on the stream
+	unsigned long long* prof = nullptr; // optional: 20 counters per goal (the profiling build of the ordered kernel, no tile form)
+	// optional (nGoals <= 4096): the last workgroup writes the goal indices ordered by decreasing field value at the start pose (x, y, theta
+	// triples) to orderOut -- the planner's hand-out order; orderKeys[nGoals] is its scratch, *doneCounter must be 0
+	const double* orderStarts = nullptr;
+	int32_t* orderOut = nullptr;
+	int* doneCounter = nullptr;
+	float* orderKeys = nullptr;
+	WavefrontPublish pub;
+};
+hipError_t launch_wavefront_tiles(hipStream_t s, const ppd::MapView& m, const WavefrontLaunch& L);
 hipError_t launch_order_by_key(hipStream_t s, int n, const float* keysDev, int32_t* orderOutDev);
 /// is the tile form in use (PP_WF_TILES=0 switches it off: every goal through the ordered kernel)
 bool wavefront_tiles_enabled();
-hipError_t launch_wavefront(hipStream_t s, const ppd::MapView& m, int nGoals, const int32_t* goalCellsDev, float* costDev, void* workspaceDev,
-	int64_t workspaceBytesPerSlot, int nSlots, int32_t* errorFlagDev, unsigned long long* profDev = nullptr, bool tiledOut = false,
-	const double* goalPosesDev = nullptr, bool countersZeroed = false, const double* orderStartsDev = nullptr, int32_t* orderOutDev = nullptr,
-	int* doneCounterDev = nullptr, float* orderKeysDev = nullptr, const WavefrontPublish& pub = WavefrontPublish());
+hipError_t launch_wavefront(hipStream_t s, const ppd::MapView& m, const WavefrontLaunch& L);
 
 } // namespace pph
 
@@ -158,13 +229,14 @@ void dist_changed(pp_map* map);
 
 // Lifetimes: a map keeps its context alive and a planner its map (reference counts), so the handles may be destroyed
 // in any order -- e.g. by a garbage collector that finalises a reference cycle in arbitrary order.  pp_*_destroy drops
-// the caller's reference; the object goes when the last dependent has gone.
+// the caller's reference; the object goes when the last dependent has gone.  Device memory, events and streams are held by the
+// owners above and go with their handle: the *_release functions only count references and wait for the stream.
 struct pp_ctx {
 	int refs = 1;
 	int device = 0;
-	hipStream_t stream = nullptr;
-	bool ownsStream = false;
-	hipEvent_t ev0 = nullptr, ev1 = nullptr;
+	hipStream_t stream = nullptr; // not owned: the caller's stream, or `ownStream` below
+	pph::Stream ownStream;        // empty when the caller brought a stream
+	pph::Event ev0, ev1;
 };
 
 struct pp_map {
@@ -172,21 +244,21 @@ struct pp_map {
 	pp_ctx* ctx = nullptr;
 	pp_map_desc desc {};
 	float minSafeRadius = 1.0f, minInterp = 0.1f;
-	int32_t* d2 = nullptr;
-	float* dist = nullptr;
-	float* pathcost = nullptr;
-	uint8_t* occ8 = nullptr;
-	uint32_t* validBits = nullptr; // one bit per cell: dist >= minSafeRadius
+	pph::Dev<int32_t> d2;
+	pph::Dev<float> dist;
+	pph::Dev<float> pathcost;
+	pph::Dev<uint8_t> occ8;
+	pph::Dev<uint32_t> validBits; // one bit per cell: dist >= minSafeRadius
 	uint64_t distVersion = 0;      // counts the writes of `dist` (pph::dist_changed): a footprint rebuilds its bitmaps when it lags behind
-	uint64_t* occBits = nullptr;   // occupancy as padded bit rows (WavefrontPublish::occBits), rebuilt whenever occ8 is
+	pph::Dev<uint64_t> occBits;    // occupancy as padded bit rows (WavefrontPublish::occBits), rebuilt whenever occ8 is
 	// map authoring / field construction on the device (pp_gvd.hip)
-	int32_t* occ32 = nullptr;      // occupancy ids as the reference holds them (-1 free)
-	uint32_t* obstLabel[2] = { nullptr, nullptr }; // nearest obstacle cell (row << 16 | col), ping-pong
-	uint32_t* voroLabel[2] = { nullptr, nullptr }; // nearest Voronoi-edge cell
+	pph::Dev<int32_t> occ32;       // occupancy ids as the reference holds them (-1 free)
+	pph::Dev<uint32_t> obstLabel[2]; // nearest obstacle cell (row << 16 | col), ping-pong
+	pph::Dev<uint32_t> voroLabel[2]; // nearest Voronoi-edge cell
 	int obstResult = 0, voroResult = 0;            // which of the two holds the fixed point
-	int32_t* voroD2 = nullptr;
-	uint8_t* voroEdge = nullptr;
-	int32_t* gvdFlag = nullptr;
+	pph::Dev<int32_t> voroD2;
+	pph::Dev<uint8_t> voroEdge;
+	pph::Dev<int32_t> gvdFlag;
 	// reference-order field construction (pp_brushfire_host.hpp): the host brushfire's persistent state and the ordered cell
 	// edits (cell, value pairs) made since it last ran.  journalReset: the grid was replaced as a whole before the recorded
 	// edits (pp_map_upload_occupancy); journalLost: edits were dropped, the next run re-seeds from the device grid.
@@ -205,7 +277,7 @@ struct pp_footprint {
 	ppd::Footprint fp {};
 	int nRadii = 0;
 	float radii[ppd::kFootprintMaxDiscs] = {};
-	uint32_t* bits = nullptr;  // nRadii bitmaps, wordsPer 32-bit words apart
+	pph::Dev<uint32_t> bits;   // nRadii bitmaps, wordsPer 32-bit words apart
 	uint32_t wordsPer = 0;
 	uint64_t bitsVersion = 0;  // the map's distVersion the bitmaps were built from
 	bool bitsBuilt = false;

@@ -131,18 +131,6 @@ __global__ void __launch_bounds__(kBlock) k_check_se2_paths(MapView m, int64_t n
 	}
 }
 
-struct Scratch { // device buffers of the host-pointer entry points
-	void* p = nullptr;
-	~Scratch()
-	{
-		if (p)
-			(void)hipFree(p);
-	}
-	hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-	template <typename T>
-	T* as() { return (T*)p; }
-};
-
 using pph::set_error;
 
 int need_ctx(pp_ctx* ctx, int64_t n, bool argsOk)
@@ -179,16 +167,16 @@ int pp_rs_connect(pp_ctx* ctx, int64_t n, const double* from_host, const double*
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->stream;
-	Scratch df, dt, dp;
+	pph::DeviceMem df, dt, dp;
 	PP_HIP_TRY(df.alloc((size_t)n * 24));
 	PP_HIP_TRY(dt.alloc((size_t)n * 24));
 	PP_HIP_TRY(dp.alloc((size_t)n * sizeof(pp_rs_path)));
-	PP_HIP_TRY(hipMemcpyAsync(df.p, from_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
-	PP_HIP_TRY(hipMemcpyAsync(dt.p, to_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(df.get(), from_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(dt.get(), to_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
 	hipLaunchKernelGGL(k_rs_connect, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, df.as<double>(), dt.as<double>(), min_turning_radius, reverse_cost, forward_cost, switch_cost,
 		dp.as<pp_rs_path>());
 	PP_HIP_TRY(hipGetLastError());
-	PP_HIP_TRY(hipMemcpyAsync(paths_host, dp.p, (size_t)n * sizeof(pp_rs_path), hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(paths_host, dp.get(), (size_t)n * sizeof(pp_rs_path), hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	return PP_OK;
 }
@@ -198,12 +186,12 @@ static int rs_path_op(pp_ctx* ctx, int op, int64_t n, pp_rs_path* paths_host, bo
 {
 	PP_HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->stream;
-	Scratch dp, dr, dpose, ddir, dcr, dcc;
+	pph::DeviceMem dp, dr, dpose, ddir, dcr, dcc;
 	PP_HIP_TRY(dp.alloc((size_t)n * sizeof(pp_rs_path)));
-	PP_HIP_TRY(hipMemcpyAsync(dp.p, paths_host, (size_t)n * sizeof(pp_rs_path), hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(dp.get(), paths_host, (size_t)n * sizeof(pp_rs_path), hipMemcpyHostToDevice, s));
 	if (ratio_host) {
 		PP_HIP_TRY(dr.alloc((size_t)n * 8));
-		PP_HIP_TRY(hipMemcpyAsync(dr.p, ratio_host, (size_t)n * 8, hipMemcpyHostToDevice, s));
+		PP_HIP_TRY(hipMemcpyAsync(dr.get(), ratio_host, (size_t)n * 8, hipMemcpyHostToDevice, s));
 	}
 	if (pose_host)
 		PP_HIP_TRY(dpose.alloc((size_t)n * 24));
@@ -217,14 +205,14 @@ static int rs_path_op(pp_ctx* ctx, int op, int64_t n, pp_rs_path* paths_host, bo
 		dcr.as<double>(), dcc.as<int32_t>());
 	PP_HIP_TRY(hipGetLastError());
 	if (writeBack)
-		PP_HIP_TRY(hipMemcpyAsync(paths_host, dp.p, (size_t)n * sizeof(pp_rs_path), hipMemcpyDeviceToHost, s));
+		PP_HIP_TRY(hipMemcpyAsync(paths_host, dp.get(), (size_t)n * sizeof(pp_rs_path), hipMemcpyDeviceToHost, s));
 	if (pose_host)
-		PP_HIP_TRY(hipMemcpyAsync(pose_host, dpose.p, (size_t)n * 24, hipMemcpyDeviceToHost, s));
+		PP_HIP_TRY(hipMemcpyAsync(pose_host, dpose.get(), (size_t)n * 24, hipMemcpyDeviceToHost, s));
 	if (direction_host)
-		PP_HIP_TRY(hipMemcpyAsync(direction_host, ddir.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+		PP_HIP_TRY(hipMemcpyAsync(direction_host, ddir.get(), (size_t)n * 4, hipMemcpyDeviceToHost, s));
 	if (cusp_host) {
-		PP_HIP_TRY(hipMemcpyAsync(cusp_host, dcr.p, (size_t)n * 32, hipMemcpyDeviceToHost, s));
-		PP_HIP_TRY(hipMemcpyAsync(count_host, dcc.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+		PP_HIP_TRY(hipMemcpyAsync(cusp_host, dcr.get(), (size_t)n * 32, hipMemcpyDeviceToHost, s));
+		PP_HIP_TRY(hipMemcpyAsync(count_host, dcc.get(), (size_t)n * 4, hipMemcpyDeviceToHost, s));
 	}
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	return PP_OK;
@@ -277,16 +265,16 @@ int pp_check_rs_paths(pp_map* map, int64_t n, const pp_rs_path* paths_host, uint
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
 	hipStream_t s = map->ctx->stream;
-	Scratch dp, dv, dl;
+	pph::DeviceMem dp, dv, dl;
 	PP_HIP_TRY(dp.alloc((size_t)n * sizeof(pp_rs_path)));
 	PP_HIP_TRY(dv.alloc((size_t)n));
 	PP_HIP_TRY(dl.alloc((size_t)n * 4));
-	PP_HIP_TRY(hipMemcpyAsync(dp.p, paths_host, (size_t)n * sizeof(pp_rs_path), hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(dp.get(), paths_host, (size_t)n * sizeof(pp_rs_path), hipMemcpyHostToDevice, s));
 	hipLaunchKernelGGL(k_check_rs_paths, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, map->view(), n, dp.as<pp_rs_path>(), dv.as<uint8_t>(), dl.as<float>());
 	PP_HIP_TRY(hipGetLastError());
-	PP_HIP_TRY(hipMemcpyAsync(valid_host, dv.p, (size_t)n, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(valid_host, dv.get(), (size_t)n, hipMemcpyDeviceToHost, s));
 	if (last_ratio_host)
-		PP_HIP_TRY(hipMemcpyAsync(last_ratio_host, dl.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+		PP_HIP_TRY(hipMemcpyAsync(last_ratio_host, dl.get(), (size_t)n * 4, hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	return PP_OK;
 }
@@ -299,18 +287,18 @@ int pp_check_se2_paths(pp_map* map, int64_t n, const double* from_host, const do
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
 	hipStream_t s = map->ctx->stream;
-	Scratch df, dt, dv, dl;
+	pph::DeviceMem df, dt, dv, dl;
 	PP_HIP_TRY(df.alloc((size_t)n * 24));
 	PP_HIP_TRY(dt.alloc((size_t)n * 24));
 	PP_HIP_TRY(dv.alloc((size_t)n));
 	PP_HIP_TRY(dl.alloc((size_t)n * 4));
-	PP_HIP_TRY(hipMemcpyAsync(df.p, from_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
-	PP_HIP_TRY(hipMemcpyAsync(dt.p, to_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(df.get(), from_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(hipMemcpyAsync(dt.get(), to_host, (size_t)n * 24, hipMemcpyHostToDevice, s));
 	hipLaunchKernelGGL(k_check_se2_paths, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, map->view(), n, df.as<double>(), dt.as<double>(), dv.as<uint8_t>(), dl.as<float>());
 	PP_HIP_TRY(hipGetLastError());
-	PP_HIP_TRY(hipMemcpyAsync(valid_host, dv.p, (size_t)n, hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(valid_host, dv.get(), (size_t)n, hipMemcpyDeviceToHost, s));
 	if (last_ratio_host)
-		PP_HIP_TRY(hipMemcpyAsync(last_ratio_host, dl.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+		PP_HIP_TRY(hipMemcpyAsync(last_ratio_host, dl.get(), (size_t)n * 4, hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	return PP_OK;
 }
@@ -324,11 +312,9 @@ int pp_map_upload_distance(pp_map* map, const float* distance_host)
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
 	const size_t n = map->cells();
 	hipStream_t s = map->ctx->stream;
-	if (!map->dist)
-		PP_HIP_TRY(hipMalloc((void**)&map->dist, n * sizeof(float)));
+	PP_HIP_TRY(map->dist.ensure(n * sizeof(float)));
 	PP_HIP_TRY(hipMemcpyAsync(map->dist, distance_host, n * sizeof(float), hipMemcpyHostToDevice, s));
-	if (!map->validBits)
-		PP_HIP_TRY(hipMalloc((void**)&map->validBits, ((n + 63) / 64) * 8));
+	PP_HIP_TRY(map->validBits.ensure(((n + 63) / 64) * 8));
 	PP_HIP_TRY(pph::launch_valid_bits(s, map->dist, (int64_t)n, map->minSafeRadius, map->validBits));
 	pph::dist_changed(map);
 	PP_HIP_TRY(hipStreamSynchronize(s));

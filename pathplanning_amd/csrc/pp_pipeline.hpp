@@ -123,61 +123,66 @@ constexpr int kPipeWavefrontStreams = 4; // at most; pp_pipeline::nWf of them ar
 
 } // namespace
 
+// Device and pinned memory, events and streams are held by owners (pp_internal.hpp) and go with the struct.  Their order of destruction does
+// not matter: pp_pipeline_destroy has stopped the grid and synchronised every stream before, and a pipeline that failed half-way through its
+// creation has nothing in flight.  The one order that does matter -- the planner's buffers outlive the pipeline's streams -- is spelled out
+// in free_pipeline.
 struct pp_pipeline {
 	pp_planner* pl = nullptr; // the buffer set: fields, per-slot inputs / paths / logs, the rows' node / heap / key-map buffers
 	int capacity = 0;
 	int waves = 0; // waves of the search grid (= rows / 4)
 	// device
-	PipeCtl* ctl = nullptr;
-	unsigned long long* ready = nullptr;
+	pph::Dev<PipeCtl> ctl;
+	pph::Dev<unsigned long long> ready;
 	unsigned long long readyMask = 0;
-	int* waveAlive = nullptr;
-	unsigned long long* urgent = nullptr; // ring of urgent slots (k_pipe_scatter -> any running wavefront launch), same size as the ready ring
-	int* claimed = nullptr;               // [capacity] 0 -> 1 by the workgroup that builds the slot's field
+	pph::Dev<int> waveAlive;
+	pph::Dev<unsigned long long> urgent; // ring of urgent slots (k_pipe_scatter -> any running wavefront launch), same size as the ready ring
+	pph::Dev<int> claimed;                // [capacity] 0 -> 1 by the workgroup that builds the slot's field
 	float urgentClearance = -1.0f;        // [m] queries with a start or goal pose closer than this to an obstacle (or the edge) go through the urgent
 	                                      // ring; 0 = none; < 0 = twice the validator's minimum safe radius (2 m with the reference's default)
-	int32_t* slotLists = nullptr; // ring of slot lists, one segment per wavefront launch in flight
+	pph::Dev<int32_t> slotLists; // ring of slot lists, one segment per wavefront launch in flight
 	size_t slotListCap = 0, slotListPos = 0;
 	// the segments of the launches that may not have finished, oldest first, each with an event recorded behind its launch: a segment is
 	// not written again before its launch is done (a launch queued behind long ones reads its list late, and with the urgent ring a slot
 	// can be built, searched, polled and refilled many times meanwhile -- capacity alone does not bound the entries submitted since)
 	struct Segment {
 		size_t begin = 0, end = 0;
-		hipEvent_t done = nullptr;
+		hipEvent_t done = nullptr; // not owned: one of pooledEvents
 	};
 	std::deque<Segment> segments;
-	std::vector<hipEvent_t> segmentEvents; // spare events
+	std::vector<hipEvent_t> segmentEvents; // spare events (handles into pooledEvents)
+	std::deque<pph::Event> pooledEvents;   // owns every event of the segment pool above and of the timing pool below, which pass plain handles around
 	long long segmentWaits = 0;            // times a submission had to wait for a launch before reusing its segment (diagnostic)
-	void* wfWorkspace[kPipeWavefrontStreams] = {};
-	uint32_t* tilesQueue[kPipeWavefrontStreams] = {}; // per wavefront stream: the tile queues of a launch's waves in global memory (large maps: pph::wavefront_tiles_queue_words)
+	pph::DeviceMem wfWorkspace[kPipeWavefrontStreams];
+	pph::Dev<uint32_t> tilesQueue[kPipeWavefrontStreams]; // per wavefront stream: the tile queues of a launch's waves in global memory (large maps: pph::wavefront_tiles_queue_words)
 	int tilesQueueWaves = 0;
-	int32_t* wfCtl[kPipeWavefrontStreams] = {}; // per wavefront stream: {error flag, goal counter, exit counter, ...}
+	pph::Dev<int32_t> wfCtl[kPipeWavefrontStreams]; // per wavefront stream: {error flag, goal counter, exit counter, ...}
 	// The tile form's control words and hand-over lists, one SET per launch in flight: the ordered kernel's launch over a tile launch's
 	// handed-over goals runs on `fbStream`, behind the tile launch and beside the wavefront stream's next one, and reads its set until it ends
 	// (fbDone[i], recorded behind it; a set is reused only after that).
 	static constexpr int kFbSets = 8;
-	int32_t* fbCtl[kFbSets] = {};  // 16 ints each, zero at allocation (the kernels set them back)
-	int32_t* fbList[kFbSets] = {}; // [capacity]
-	hipEvent_t fbDone[kFbSets] = {}, fbAfterTiles[kFbSets] = {};
+	pph::Dev<int32_t> fbCtl[kFbSets];  // 16 ints each, zero at allocation (the kernels set them back)
+	pph::Dev<int32_t> fbList[kFbSets]; // [capacity]
+	pph::Event fbDone[kFbSets], fbAfterTiles[kFbSets];
 	bool fbUsed[kFbSets] = {};
 	int nextFbSet = 0;
-	hipStream_t fbStream = nullptr;
+	pph::Stream fbStream;
 	// pinned host
-	PipeDone* done = nullptr;
+	pph::Pinned<PipeDone> done;
 	unsigned long long doneMask = 0;
-	int32_t* slotStage = nullptr;             // staging of the slot lists (same ring positions as slotLists)
-	unsigned long long* submittedStage = nullptr; // ring of submission counts on their way to ctl->nSubmitted
+	pph::Pinned<int32_t> slotStage;           // staging of the slot lists (same ring positions as slotLists)
+	pph::Pinned<unsigned long long> submittedStage; // ring of submission counts on their way to ctl->nSubmitted
 	int submittedStagePos = 0;
-	int32_t* errFlags = nullptr; // [streams] the wavefront kernels' error flags, in pinned host memory: written by the device, read by poll
-	double* pathHost = nullptr;  // [capacity][pathHostCap][3]: the poses of every finished query's solution path, goal first, written by the row that finished it
+	pph::Pinned<int32_t> errFlags; // [streams] the wavefront kernels' error flags, in pinned host memory: written by the device, read by poll
+	pph::Pinned<double> pathHost; // [capacity][pathHostCap][3]: the poses of every finished query's solution path, goal first, written by the row that finished it
 	int pathHostCap = 192;       // poses per slot in that ring (longer paths: the rest is fetched from the device records); PP_PIPE_PATH_POSES
 	unsigned long long lingerTicks = 0; // PP_PIPE_LINGER_MS: how long an idle search wave stays after everything submitted has been claimed (default: the idle time-out)
 	unsigned long long quiesced = 0;    // the submission count last written to PipeCtl::quiesce
 	bool dead = false;           // a submission failed half way: the pipeline's accounting is no longer trustworthy (every later call fails)
 	unsigned long long lastTail = 0, lastHead = 0; // the ready queue's counters as the latest completion record saw them
 	// streams
-	hipStream_t wfStream[kPipeWavefrontStreams] = {}, searchStream[kPipeSearchStreams] = {}, ctlStream = nullptr;
-	hipEvent_t evIngest = nullptr, evCtl = nullptr;
+	pph::Stream wfStream[kPipeWavefrontStreams], searchStream[kPipeSearchStreams], ctlStream;
+	pph::Event evIngest, evCtl;
 	int nextWf = 0, nextSearch = 0;
 	// host bookkeeping
 	std::vector<int32_t> freeSlots;
@@ -189,7 +194,7 @@ struct pp_pipeline {
 	std::chrono::steady_clock::time_point lastLaunch {};
 	// launch durations (HIP events on the streams the kernels are launched on), harvested by pp_pipeline_poll
 	struct Timed {
-		hipEvent_t a = nullptr, b = nullptr;
+		hipEvent_t a = nullptr, b = nullptr; // not owned: two of pooledEvents
 		int kind = 0; // 0 wavefront, 1 search grid
 		long long units = 0; // goals of a wavefront launch
 	};
@@ -211,50 +216,22 @@ void free_pipeline(pp_pipeline* P)
 {
 	if (!P)
 		return;
-	for (hipStream_t s : P->wfStream)
-		if (s)
-			(void)hipStreamDestroy(s);
-	for (hipStream_t s : P->searchStream)
-		if (s)
-			(void)hipStreamDestroy(s);
-	if (P->ctlStream)
-		(void)hipStreamDestroy(P->ctlStream);
-	if (P->fbStream)
-		(void)hipStreamDestroy(P->fbStream);
-	for (hipEvent_t ev : P->fbDone)
-		if (ev)
-			(void)hipEventDestroy(ev);
-	for (hipEvent_t ev : P->fbAfterTiles)
-		if (ev)
-			(void)hipEventDestroy(ev);
-	if (P->evIngest)
-		(void)hipEventDestroy(P->evIngest);
-	if (P->evCtl)
-		(void)hipEventDestroy(P->evCtl);
-	for (auto& sg : P->segments)
-		if (sg.done)
-			(void)hipEventDestroy(sg.done);
-	for (hipEvent_t ev : P->segmentEvents)
-		(void)hipEventDestroy(ev);
-	for (auto* v : { &P->timedFree, &P->timedBusy })
-		for (auto& t : *v) {
-			if (t.a)
-				(void)hipEventDestroy(t.a);
-			if (t.b)
-				(void)hipEventDestroy(t.b);
-		}
-	void* dev[] = { P->ctl, P->ready, P->waveAlive, P->urgent, P->claimed, P->slotLists, P->wfWorkspace[0], P->wfWorkspace[1], P->wfWorkspace[2], P->wfWorkspace[3], P->tilesQueue[0], P->tilesQueue[1], P->tilesQueue[2], P->tilesQueue[3], P->wfCtl[0], P->wfCtl[1], P->wfCtl[2], P->wfCtl[3], P->fbCtl[0], P->fbCtl[1], P->fbCtl[2], P->fbCtl[3], P->fbCtl[4], P->fbCtl[5], P->fbCtl[6], P->fbCtl[7],
-		P->fbList[0], P->fbList[1], P->fbList[2], P->fbList[3], P->fbList[4], P->fbList[5], P->fbList[6], P->fbList[7] };
-	for (void* q : dev)
-		if (q)
-			(void)hipFree(q);
-	void* host[] = { P->done, P->slotStage, P->submittedStage, P->errFlags, P->pathHost };
-	for (void* q : host)
-		if (q)
-			(void)hipHostFree(q);
-	if (P->pl)
-		free_planner(P->pl);
-	delete P;
+	pp_planner* const pl = P->pl;
+	delete P; // the streams, events and rings of the pipeline's launches go first ...
+	if (pl)
+		free_planner(pl); // ... then the buffer set those launches worked on
+}
+
+/// a new event owned by the pipeline's pool
+hipError_t pooled_event(pp_pipeline* P, unsigned flags, hipEvent_t* out)
+{
+	pph::Event ev;
+	const hipError_t e = ev.create(flags);
+	if (e == hipSuccess) {
+		*out = ev;
+		P->pooledEvents.push_back(std::move(ev));
+	}
+	return e;
 }
 
 /// an event pair around a launch on stream s: take() before the launch, done() after it
@@ -264,7 +241,7 @@ pp_pipeline::Timed timed_take(pp_pipeline* P, hipStream_t s, int kind, long long
 	if (!P->timedFree.empty()) {
 		t = P->timedFree.back();
 		P->timedFree.pop_back();
-	} else if (hipEventCreate(&t.a) != hipSuccess || hipEventCreate(&t.b) != hipSuccess) {
+	} else if (pooled_event(P, hipEventDefault, &t.a) != hipSuccess || pooled_event(P, hipEventDefault, &t.b) != hipSuccess) {
 		t.a = t.b = nullptr;
 	}
 	t.kind = kind;
@@ -351,14 +328,10 @@ int pipe_launch_search(pp_pipeline* P)
 		return PP_OK;
 	}
 	PP_HIP_TRY(hipStreamWaitEvent(s, P->evCtl, 0));
-	constexpr int kWg = 1; // (single-wave workgroups: see k_hybrid_search_rows)
 	pl->args.rowsWaves = P->waves;
 	pl->args.m = pl->map->view(); // validator tunables may have changed
 	const pp_pipeline::Timed tm = timed_take(P, s, 1, 0);
-	hipLaunchKernelGGL(k_hybrid_search_rows<true>, dim3((P->waves + kWg - 1) / kWg), dim3(64 * kWg), 0, s, pl->args, 0, pl->dStarts, pl->dGoals, pl->dSeeds, pl->costFields, pl->nodes, pl->heaps,
-		pl->keymaps, pl->expanded, pl->rsLogs, pl->paths, pl->mtStates, pl->results, (int*)nullptr, (SuspendRec*)nullptr, (const int32_t*)nullptr, 0, (int*)nullptr, (int*)nullptr,
-		pl->bands, pl->bandInvW, pl->bandMeta, pipe_view(P));
-	PP_HIP_TRY(hipGetLastError());
+	PP_HIP_TRY(launch_search_rows<true>(pl, s, pl->args, Queries { 0, pl->dStarts, pl->dGoals, pl->dSeeds }, nullptr, pipe_view(P))); // (the slots' inputs: no query count)
 	timed_done(P, s, tm);
 	P->lastLaunch = std::chrono::steady_clock::now();
 	return PP_OK;
@@ -380,7 +353,7 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 	if (search_rows == 0)
 		search_rows = 4096; // measured optimum on MI355X with the tile form of the wavefront (profiles/r04_pipeline_sweeps.txt; 2560 with the ordered kernel, round 3)
 	if (int rc = create_planner(map, params, capacity, max_nodes_per_query, search_rows, log_expansions ? PlannerUse::PipelineLogged : PlannerUse::Pipeline, &P->pl)) {
-		delete P;
+		free_pipeline(P);
 		return rc;
 	}
 	pp_planner* pl = P->pl;
@@ -390,17 +363,17 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 		ring <<= 1;
 	P->readyMask = P->doneMask = ring - 1;
 	P->slotListCap = (size_t)capacity * 4;
-	hipError_t e = hipMalloc((void**)&P->ctl, sizeof(PipeCtl));
+	hipError_t e = P->ctl.alloc(sizeof(PipeCtl));
 	if (e == hipSuccess)
-		e = hipMalloc((void**)&P->ready, ring * 8);
+		e = P->ready.alloc(ring * 8);
 	if (e == hipSuccess)
-		e = hipMalloc((void**)&P->waveAlive, (size_t)P->waves * 4);
+		e = P->waveAlive.alloc((size_t)P->waves * 4);
 	if (e == hipSuccess)
-		e = hipMalloc((void**)&P->slotLists, P->slotListCap * 4);
+		e = P->slotLists.alloc(P->slotListCap * 4);
 	if (e == hipSuccess)
-		e = hipMalloc((void**)&P->urgent, ring * 8);
+		e = P->urgent.alloc(ring * 8);
 	if (e == hipSuccess)
-		e = hipMalloc((void**)&P->claimed, (size_t)capacity * 4);
+		e = P->claimed.alloc((size_t)capacity * 4);
 	if (const char* v = getenv("PP_PIPE_URGENT_CLEARANCE")) { // [m]; 0 switches the urgent ring off
 		const double x = strtod(v, nullptr);
 		if (x >= 0.0 && x < 1.0e6)
@@ -412,33 +385,33 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 			P->nWf = (int)x;
 	}
 	for (int i = 0; i < P->nWf && e == hipSuccess; i++) {
-		e = hipMalloc(&P->wfWorkspace[i], (size_t)pl->wfBytesPerSlot * pl->wfSlots);
+		e = P->wfWorkspace[i].alloc((size_t)pl->wfBytesPerSlot * pl->wfSlots);
 		if (const size_t qw = pph::wavefront_tiles_queue_words(pl->map->desc.rows, pl->map->desc.cols)) {
 			P->tilesQueueWaves = 2048; // (256 CUs x 8 waves of a pack)
 			if (e == hipSuccess)
-				e = hipMalloc((void**)&P->tilesQueue[i], qw * 4 * (size_t)P->tilesQueueWaves);
+				e = P->tilesQueue[i].alloc(qw * 4 * (size_t)P->tilesQueueWaves);
 		}
 		if (e == hipSuccess)
-			e = hipMalloc((void**)&P->wfCtl[i], 64);
+			e = P->wfCtl[i].alloc(64);
 		if (e == hipSuccess)
 			e = hipMemset(P->wfCtl[i], 0, 64);
 
 		if (e == hipSuccess)
-			e = hipStreamCreateWithFlags(&P->wfStream[i], hipStreamNonBlocking);
+			e = P->wfStream[i].create();
 	}
 	for (int i = 0; i < pp_pipeline::kFbSets && e == hipSuccess; i++) {
-		e = hipMalloc((void**)&P->fbCtl[i], 64);
+		e = P->fbCtl[i].alloc(64);
 		if (e == hipSuccess)
 			e = hipMemset(P->fbCtl[i], 0, 64);
 		if (e == hipSuccess)
-			e = hipMalloc((void**)&P->fbList[i], (size_t)capacity * 4);
+			e = P->fbList[i].alloc((size_t)capacity * 4);
 		if (e == hipSuccess)
-			e = hipEventCreateWithFlags(&P->fbDone[i], hipEventDisableTiming);
+			e = P->fbDone[i].create(hipEventDisableTiming);
 		if (e == hipSuccess)
-			e = hipEventCreateWithFlags(&P->fbAfterTiles[i], hipEventDisableTiming);
+			e = P->fbAfterTiles[i].create(hipEventDisableTiming);
 	}
 	if (e == hipSuccess)
-		e = hipStreamCreateWithFlags(&P->fbStream, hipStreamNonBlocking);
+		e = P->fbStream.create();
 	// The wavefront workgroups of a launch in flight stay until its list AND the urgent ring are empty, and launches queue: room on the chip
 	// frees rarely and in bursts.  When it does, the waves that top up the search grid and the scatter kernel of a new submission should get
 	// it before the next wavefront launch's pending workgroups refill the chip: their streams have the highest priority.  A safeguard, not a
@@ -450,21 +423,21 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 	if (flatPriority)
 		prioHigh = 0;
 	for (int i = 0; i < kPipeSearchStreams && e == hipSuccess; i++)
-		e = hipStreamCreateWithPriority(&P->searchStream[i], hipStreamNonBlocking, prioHigh);
+		e = P->searchStream[i].create(prioHigh);
 	if (e == hipSuccess)
-		e = hipStreamCreateWithPriority(&P->ctlStream, hipStreamNonBlocking, prioHigh);
+		e = P->ctlStream.create(prioHigh);
 	if (e == hipSuccess)
-		e = hipEventCreateWithFlags(&P->evIngest, hipEventDisableTiming);
+		e = P->evIngest.create(hipEventDisableTiming);
 	if (e == hipSuccess)
-		e = hipEventCreateWithFlags(&P->evCtl, hipEventDisableTiming);
+		e = P->evCtl.create(hipEventDisableTiming);
 	if (e == hipSuccess)
-		e = hipHostMalloc((void**)&P->done, ring * sizeof(PipeDone), hipHostMallocDefault);
+		e = P->done.alloc(ring * sizeof(PipeDone));
 	if (e == hipSuccess)
-		e = hipHostMalloc((void**)&P->slotStage, P->slotListCap * 4, hipHostMallocDefault);
+		e = P->slotStage.alloc(P->slotListCap * 4);
 	if (e == hipSuccess)
-		e = hipHostMalloc((void**)&P->submittedStage, 64 * 8, hipHostMallocDefault);
+		e = P->submittedStage.alloc(64 * 8);
 	if (e == hipSuccess)
-		e = hipHostMalloc((void**)&P->errFlags, 64, hipHostMallocDefault);
+		e = P->errFlags.alloc(64);
 	if (const char* v = getenv("PP_PIPE_PATH_POSES")) {
 		const long x = strtol(v, nullptr, 10);
 		if (x >= 0 && x <= 2048)
@@ -473,7 +446,7 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 	if (P->pathHostCap > pl->maxPath)
 		P->pathHostCap = pl->maxPath;
 	if (e == hipSuccess && P->pathHostCap > 0)
-		e = hipHostMalloc((void**)&P->pathHost, (size_t)capacity * (size_t)P->pathHostCap * 24, hipHostMallocDefault);
+		e = P->pathHost.alloc((size_t)capacity * (size_t)P->pathHostCap * 24);
 	if (e == hipSuccess)
 		e = hipMemset(P->ctl, 0, sizeof(PipeCtl));
 	if (e == hipSuccess)
@@ -500,8 +473,9 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 		all.push_back(P->fbStream);
 		const size_t nLong = all.size(); // the streams that carry launches which may wait for room
 		all.push_back(P->ctlStream);
-		unsigned int* probe = nullptr; // {setter bits, "the hog gave up" flag, the hog's start stamp (2 words)}
-		e = hipMalloc((void**)&probe, 16);
+		pph::Dev<unsigned int> probeMem; // {setter bits, "the hog gave up" flag, the hog's start stamp (2 words)}
+		e = probeMem.alloc(16);
+		unsigned int* const probe = probeMem;
 		// (a stream gets its hardware queue at its first launch, which takes milliseconds: every stream runs one kernel before the clock matters)
 		for (size_t j = 0; j < all.size() && e == hipSuccess; j++)
 			hipLaunchKernelGGL(k_queue_probe_set, dim3(1), dim3(64), 0, all[j], probe, 1u << j);
@@ -539,8 +513,6 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 				blockedMask = flags[1] & 0x7FFFFFFFu;
 			}
 		}
-		if (probe)
-			(void)hipFree(probe);
 		if (e != hipSuccess) {
 			free_pipeline(P);
 			return pph::hip_fail(e, "pipeline queue probe");
@@ -680,7 +652,7 @@ int pp_pipeline_submit_dev(pp_pipeline* P, int32_t n_queries, const double* star
 		seg.done = P->segmentEvents.back();
 		P->segmentEvents.pop_back();
 	} else {
-		PP_HIP_TRY(hipEventCreateWithFlags(&seg.done, hipEventDisableTiming));
+		PP_HIP_TRY(pooled_event(P, hipEventDisableTiming, &seg.done));
 	}
 	// from here on a failure leaves slots taken and work half queued: the pipeline is marked dead instead of pretending to account for it
 	struct DeadGuard {
@@ -692,7 +664,7 @@ int pp_pipeline_submit_dev(pp_pipeline* P, int32_t n_queries, const double* star
 				P->dead = true;
 		}
 	} guard { P };
-	P->segmentEvents.push_back(seg.done); // (owned by the pool until the launch below has been recorded)
+	P->segmentEvents.push_back(seg.done); // (a spare of the pool until the launch below has been recorded)
 	int32_t* const stage = P->slotStage + P->slotListPos;
 	int32_t* const listDev = P->slotLists + P->slotListPos;
 	P->slotListPos += (size_t)k;
@@ -721,7 +693,7 @@ int pp_pipeline_submit_dev(pp_pipeline* P, int32_t n_queries, const double* star
 	// (with the tile form the ordered kernel's launches all run on fbStream, one after the other: one workspace; without it they are the
 	// wavefront streams' own launches)
 	const bool tilesOn = pl->map->occBits && pph::wavefront_tiles_enabled() && pph::wavefront_tiles_supported(pl->map->desc.rows, pl->map->desc.cols);
-	void* const wws = P->wfWorkspace[tilesOn ? 0 : P->nextWf];
+	void* const wws = P->wfWorkspace[tilesOn ? 0 : P->nextWf].get();
 	P->nextWf = (P->nextWf + 1) % P->nWf;
 	PP_HIP_TRY(hipMemcpyAsync(listDev, stage, (size_t)k * 4, hipMemcpyHostToDevice, P->ctlStream));
 	pl->args.m = pl->map->view();
@@ -733,7 +705,17 @@ int pp_pipeline_submit_dev(pp_pipeline* P, int32_t n_queries, const double* star
 	// ---- ObstaclesHeuristic::Update for every goal (hybrid_a_star.cpp:249); each finished slot is appended to the ready ring
 	PP_HIP_TRY(hipStreamWaitEvent(w, P->evIngest, 0));
 	pl->args.m = pl->map->view();
-	pph::WavefrontPublish pub;
+	pph::WavefrontLaunch L;
+	L.nGoals = k;
+	L.goalPoses = pl->dGoals; // (indexed by the slot, as the fields are)
+	L.cost = pl->costFields;
+	L.tiledOut = true;
+	L.workspace = wws;
+	L.workspaceBytesPerSlot = pl->wfBytesPerSlot;
+	L.nSlots = P->wfBlocks;
+	L.errorFlag = werr;
+	L.countersZeroed = true;
+	pph::WavefrontPublish& pub = L.pub;
 	pub.slotList = listDev;
 	pub.readyTail = &P->ctl->readyTail;
 	pub.ready = P->ready;
@@ -754,8 +736,7 @@ int pp_pipeline_submit_dev(pp_pipeline* P, int32_t n_queries, const double* star
 		pub.urgentMask = P->readyMask;
 	}
 	const pp_pipeline::Timed tm = timed_take(P, w, 0, k);
-	PP_HIP_TRY(pph::launch_wavefront(w, pl->args.m, k, nullptr, pl->costFields, wws, pl->wfBytesPerSlot, P->wfBlocks, werr, nullptr, /*tiledOut=*/true, /*goalPoses=*/pl->dGoals,
-		/*countersZeroed=*/true, nullptr, nullptr, nullptr, nullptr, pub));
+	PP_HIP_TRY(pph::launch_wavefront(w, pl->args.m, L));
 	timed_done(P, w, tm);
 	PP_HIP_TRY(hipEventRecord(P->fbDone[fbSet], P->fbStream));
 	P->fbUsed[fbSet] = true;
@@ -780,24 +761,15 @@ int pp_pipeline_submit(pp_pipeline* P, int32_t n_queries, const double* starts_h
 	if (k == 0)
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(P->pl->map->ctx->device));
-	double *ds = nullptr, *dg = nullptr;
-	uint64_t* dz = nullptr;
-	hipError_t e = hipMalloc((void**)&ds, (size_t)k * 24);
-	if (e == hipSuccess)
-		e = hipMalloc((void**)&dg, (size_t)k * 24);
-	if (e == hipSuccess)
-		e = hipMalloc((void**)&dz, (size_t)k * 8);
-	if (e == hipSuccess)
-		e = hipMemcpy(ds, starts_host, (size_t)k * 24, hipMemcpyHostToDevice);
-	if (e == hipSuccess)
-		e = hipMemcpy(dg, goals_host, (size_t)k * 24, hipMemcpyHostToDevice);
-	if (e == hipSuccess)
-		e = hipMemcpy(dz, seeds_host, (size_t)k * 8, hipMemcpyHostToDevice);
-	int rc = e == hipSuccess ? pp_pipeline_submit_dev(P, k, ds, dg, dz, tickets_out, n_accepted) : pph::hip_fail(e, "pp_pipeline_submit");
-	for (void* q : { (void*)ds, (void*)dg, (void*)dz })
-		if (q)
-			(void)hipFree(q);
-	return rc;
+	pph::Dev<double> ds, dg;
+	pph::Dev<uint64_t> dz;
+	PP_HIP_TRY(ds.alloc((size_t)k * 24));
+	PP_HIP_TRY(dg.alloc((size_t)k * 24));
+	PP_HIP_TRY(dz.alloc((size_t)k * 8));
+	PP_HIP_TRY(hipMemcpy(ds, starts_host, (size_t)k * 24, hipMemcpyHostToDevice));
+	PP_HIP_TRY(hipMemcpy(dg, goals_host, (size_t)k * 24, hipMemcpyHostToDevice));
+	PP_HIP_TRY(hipMemcpy(dz, seeds_host, (size_t)k * 8, hipMemcpyHostToDevice));
+	return pp_pipeline_submit_dev(P, k, ds, dg, dz, tickets_out, n_accepted);
 }
 
 int pp_pipeline_poll(pp_pipeline* P, int32_t max_results, uint64_t* tickets_out, pp_query_result* results_out, int32_t release, int32_t* n_out)

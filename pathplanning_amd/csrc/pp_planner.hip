@@ -295,50 +295,53 @@ struct pp_planner {
 	pph::NonHoloDesc nh {};
 	std::vector<double> deltas;
 	// device
-	double* table = nullptr;
+	// (pph::Dev / pph::Event own what they hold and release it with the planner; the kernels get raw pointers)
+	pph::Dev<double> table;
 	bool tableReady = false;
-	float* costFields = nullptr;
-	void* wfWorkspace = nullptr;
+	pph::Dev<float> costFields;
+	pph::DeviceMem wfWorkspace;
 	int64_t wfBytesPerSlot = 0;
 	int wfSlots = 0;
-	int32_t* wfError = nullptr;
-	int* tilesCtl = nullptr;          // control words of the tile form of the wavefront (pp_wavefront_tiles.hip; zero at allocation, set back by its kernels)
-	int32_t* tilesFallback = nullptr; // [maxBatch] goals it hands to the ordered kernel
-	Node* nodes = nullptr;
-	HeapEntry* heaps = nullptr;
-	uint32_t* keymaps = nullptr;
-	uint32_t* expanded = nullptr;
-	RsLogEntry* rsLogs = nullptr;
-	DevResult* results = nullptr;
-	unsigned long long* prof = nullptr; // diagnostic phase cycles, [maxBatch][PH_COUNT]
+	pph::Dev<int32_t> wfError;
+	pph::Dev<int> tilesCtl;               // control words of the tile form of the wavefront (pp_wavefront_tiles.hip; zero at allocation, set back by its kernels)
+	pph::Dev<int32_t> tilesFallback;      // [maxBatch] goals it hands to the ordered kernel
+	pph::Dev<Node> nodes;
+	pph::Dev<HeapEntry> heaps;
+	pph::Dev<uint32_t> keymaps;
+	pph::Dev<uint32_t> expanded;
+	pph::Dev<RsLogEntry> rsLogs;
+	pph::Dev<DevResult> results;
+	pph::Dev<unsigned long long> prof;    // diagnostic phase cycles, [maxBatch][PH_COUNT]
 	bool profile = false;
-	unsigned long long* mtStates = nullptr; // [searchRows][312] mt19937_64 engine state per row (rows kernel)
-	int* nextQuery = nullptr;               // = wfError + 2: {query counter of the persistent rows kernel, set-aside count}
-	SuspendRec* suspended = nullptr;        // [listCap] queries set aside by the rows kernel
-	int32_t* order = nullptr;               // [maxBatch] query indices, probable longest first (rows kernel)
-	float* orderKeys = nullptr;             // [maxBatch] field value at each query's start pose (the sort key)
-	HeapEntry* bands = nullptr;             // [slots][kBands * kBandCap] f-bands of the open list
-	uint8_t* bandMeta = nullptr;            // [slots][kBands] slot fill counts of set-aside queries
+	pph::Dev<unsigned long long> mtStates; // [searchRows][312] mt19937_64 engine state per row (rows kernel)
+	int* nextQuery = nullptr;               // not owned: wfError + 2, {query counter of the persistent rows kernel, set-aside count}
+	pph::Dev<SuspendRec> suspended;         // [listCap] queries set aside by the rows kernel
+	pph::Dev<int32_t> order;                // [maxBatch] query indices, probable longest first (rows kernel)
+	pph::Dev<float> orderKeys;              // [maxBatch] field value at each query's start pose (the sort key)
+	pph::Dev<HeapEntry> bands;              // [slots][kBands * kBandCap] f-bands of the open list
+	pph::Dev<uint8_t> bandMeta;             // [slots][kBands] slot fill counts of set-aside queries
 	double bandInvW = 64.0;                 // bands are 1 / bandInvW wide in total cost
 	int searchWaves = 0;                    // resident waves of k_hybrid_search_rows on this device
 	int searchRows = 0;                     // rows (= search buffer slots) this planner runs with
 	bool rowsKernel = false;                // four-queries-per-wave kernel (throughput) vs one query per wave (latency)
-	GuardRec* guardLog = nullptr;           // [maxBatch][kGuardLogCap] lattice-line children (one-query-per-wave planners only)
-	int* guardCount = nullptr;              // [maxBatch]
-	PathRec* paths = nullptr;               // [maxBatch][maxPath] solution paths, goal first
+	pph::Dev<GuardRec> guardLog;            // [maxBatch][kGuardLogCap] lattice-line children (one-query-per-wave planners only)
+	pph::Dev<int> guardCount;               // [maxBatch]
+	pph::Dev<PathRec> paths;                // [maxBatch][maxPath] solution paths, goal first
 	int maxPath = 0;
-	double *dStarts = nullptr, *dGoals = nullptr;
-	uint64_t* dSeeds = nullptr;
-	hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-	hipEvent_t startAfter = nullptr; // one-shot: the next batch waits for this event (pp_planner_start_after_fields_of)
+	pph::Dev<double> dStarts, dGoals;
+	pph::Dev<uint64_t> dSeeds;
+	pph::Event e0, e1, e2;
+	hipEvent_t startAfter = nullptr; // not owned: another planner's e1; one-shot, the next batch waits for it (pp_planner_start_after_fields_of)
 	float wavefrontMs = 0, searchMs = 0;
 	int lastBatch = 0;
-	pp_pipeline* owner = nullptr; // (set with pipelineOwned)
+	pp_pipeline* owner = nullptr; // not owned: the pipeline this planner is the buffer set of (set with pipelineOwned)
 	pp_footprint* footprint = nullptr; // pp_planner_set_footprint (a reference is held): the search asks the footprint, not the point validator
 	bool pipelineOwned = false; // the buffer set of a pp_pipeline (pp_pipeline_planner()): its rows and field slots belong to the pipeline's kernels
 	std::vector<DevResult> hostResults;
-	// post-processing (pp_postprocess.hpp), allocated at the first pp_planner_postprocess
-	PostBuffers post {};
+	// post-processing (pp_postprocess.hpp), allocated at the first pp_planner_postprocess (the kernel takes them as a PostBuffers)
+	pph::Dev<double> postRatios, postResampled, postSmoothed, postEdgeEnd;
+	pph::Dev<uint8_t> postCusp, postOptimise;
+	pph::Dev<pp_post_result> postOut;
 	int postMaxPoints = 0, postDone = 0; // capacity of the buffers per query; queries of the last call
 	int postPoints = 0; // the last call's max_points: its sample limit and the buffers' per-query stride
 	std::vector<pp_post_result> hostPost;
@@ -354,34 +357,68 @@ using pph::set_error;
 constexpr size_t kMaxPrivateBytes = 1024;
 constexpr size_t kReserveQueues = 16;
 
+// One launch function per search kernel: every launch site -- batch, continuation, pipeline, warm-up -- goes through these, so a
+// kernel argument is added in one place.  A warm-up is nQueries = 0 on a grid of one: the kernels leave before they dereference
+// anything, which is what lets warm_up_kernels run them while the planner's buffers are still null.
+struct Queries { // device arrays
+	int n;
+	const double *starts, *goals;
+	const uint64_t* seeds;
+};
+
+/// k_hybrid_search<kProfile> on `grid` waves; resume: the continuation of the queries the rows kernel set aside (their records, the
+/// count behind the rows' query counter, the rows' engine states) instead of a batch of its own
+template <bool kProfile>
+hipError_t launch_search(pp_planner* p, hipStream_t s, int grid, const Queries& q, bool resume = false)
+{
+	hipLaunchKernelGGL(k_hybrid_search<kProfile>, dim3(grid), dim3(64), 0, s, p->args, q.n, q.starts, q.goals, q.seeds, p->costFields.get(), p->nodes.get(), p->heaps.get(),
+		p->keymaps.get(), p->expanded.get(), p->rsLogs.get(), p->paths.get(), p->results.get(), p->prof.get(), resume ? p->suspended.get() : nullptr,
+		resume ? p->nextQuery + 1 : nullptr, resume ? p->mtStates.get() : nullptr, p->bands.get(), p->bandInvW, p->bandMeta.get());
+	return hipGetLastError();
+}
+
+hipError_t launch_search_footprint(pp_planner* p, hipStream_t s, int grid, const Footprint& foot, const Queries& q)
+{
+	hipLaunchKernelGGL(k_hybrid_search_footprint, dim3(grid), dim3(64), 0, s, p->args, foot, q.n, q.starts, q.goals, q.seeds, p->costFields.get(), p->nodes.get(), p->heaps.get(),
+		p->keymaps.get(), p->expanded.get(), p->rsLogs.get(), p->paths.get(), p->results.get(), p->bands.get(), p->bandInvW, p->bandMeta.get());
+	return hipGetLastError();
+}
+
+/// k_hybrid_search_rows<kPiped> on args.rowsWaves waves (at least one workgroup).  Batch form: q.n queries handed out through the planner's
+/// counters, in `order` if given, set aside after args.suspendAfter expansions; pipeline form: the rows take field slots through `pipe`.
+template <bool kPiped>
+hipError_t launch_search_rows(pp_planner* p, hipStream_t s, const SearchArgs& args, const Queries& q, const int32_t* order, const PipeView& pipe)
+{
+	constexpr int kWg = kPiped ? 1 : PP_ROWS_WAVES_PER_WG; // waves per workgroup (see k_hybrid_search_rows)
+	const int waves = args.rowsWaves > 0 ? args.rowsWaves : 1;
+	int* const ctl = kPiped ? nullptr : p->nextQuery; // {query counter, set-aside count}, spare slots handed out at wfError + 7; null in a warm-up
+	hipLaunchKernelGGL(k_hybrid_search_rows<kPiped>, dim3((waves + kWg - 1) / kWg), dim3(64 * kWg), 0, s, args, q.n, q.starts, q.goals, q.seeds, p->costFields.get(), p->nodes.get(),
+		p->heaps.get(), p->keymaps.get(), p->expanded.get(), p->rsLogs.get(), p->paths.get(), p->mtStates.get(), p->results.get(), ctl, kPiped ? nullptr : p->suspended.get(), order,
+		args.suspendAfter, ctl ? ctl + 1 : nullptr, ctl ? ctl + 5 : nullptr, p->bands.get(), p->bandInvW, p->bandMeta.get(), pipe);
+	return hipGetLastError();
+}
+
 /// Empty dispatches of the three kernels a batch launches, on the planner's stream, then a synchronisation: the queue
 /// allocates their scratch here, where a failure is an error code, not at the first batch, where it is an abort.
 int warm_up_kernels(pp_planner* p, pp_map* map)
 {
 	hipStream_t s = map->ctx->stream;
-	int32_t* ctl = nullptr;
-	PP_HIP_TRY(hipMalloc((void**)&ctl, 64));
+	pph::Dev<int32_t> ctl;
+	PP_HIP_TRY(ctl.alloc(64));
 	hipError_t e = hipMemsetAsync(ctl, 0, 64, s);
 	if (e == hipSuccess)
 		e = pph::warm_up_wavefront(s, map->view(), ctl);
 	if (e == hipSuccess && map->occBits && pph::wavefront_tiles_supported(map->desc.rows, map->desc.cols))
-		e = pph::warm_up_wavefront_tiles(s, map->view(), (int*)ctl + 8);
+		e = pph::warm_up_wavefront_tiles(s, map->view(), (int*)ctl.get() + 8);
+	const Queries noQueries {};
 	if (e == hipSuccess) {
 		SearchArgs none = p->args;
 		none.rowsWaves = 0; // every wave of the rows kernel leaves at once
 		none.listCap = 0;
-		hipLaunchKernelGGL(k_hybrid_search_rows<false>, dim3(1), dim3(64 * PP_ROWS_WAVES_PER_WG), 0, s, none, 0, (const double*)nullptr, (const double*)nullptr, (const uint64_t*)nullptr,
-			(const float*)nullptr, (Node*)nullptr, (HeapEntry*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (RsLogEntry*)nullptr, (PathRec*)nullptr, (unsigned long long*)nullptr,
-			(DevResult*)nullptr, (int*)nullptr, (SuspendRec*)nullptr, (const int32_t*)nullptr, 0, (int*)nullptr, (int*)nullptr, (HeapEntry*)nullptr, 0.0, (uint8_t*)nullptr,
-			PipeView {});
-		e = hipGetLastError();
+		e = launch_search_rows<false>(p, s, none, noQueries, nullptr, PipeView {});
 	}
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_hybrid_search<false>, dim3(1), dim3(64), 0, s, p->args, 0, (const double*)nullptr, (const double*)nullptr, (const uint64_t*)nullptr, (const float*)nullptr,
-			(Node*)nullptr, (HeapEntry*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (RsLogEntry*)nullptr, (PathRec*)nullptr, (DevResult*)nullptr, (unsigned long long*)nullptr,
-			(const SuspendRec*)nullptr, (const int*)nullptr, (const unsigned long long*)nullptr, (HeapEntry*)nullptr, 0.0, (uint8_t*)nullptr);
-		e = hipGetLastError();
-	}
+	if (e == hipSuccess)
+		e = launch_search<false>(p, s, 1, noQueries);
 	if (e == hipSuccess) {
 		hipLaunchKernelGGL(k_postprocess, dim3(1), dim3(kPostThreads), 64, s, p->args, PostParams {}, 0, (const PathRec*)nullptr, (const RsLogEntry*)nullptr, (const DevResult*)nullptr,
 			(const uint32_t*)nullptr, (const uint32_t*)nullptr, PostBuffers {});
@@ -389,7 +426,6 @@ int warm_up_kernels(pp_planner* p, pp_map* map)
 	}
 	if (e == hipSuccess)
 		e = hipStreamSynchronize(s);
-	(void)hipFree(ctl);
 	if (e != hipSuccess)
 		return pph::hip_fail(e, "planner kernel warm-up (scratch allocation)");
 	return PP_OK;
@@ -440,21 +476,6 @@ void free_planner(pp_planner* p)
 		}
 	}
 #endif
-	void* postPtrs[] = { p->post.ratios, p->post.resampled, p->post.smoothed, p->post.cusp, p->post.optimise, p->post.edgeEnd, p->post.out };
-	for (void* q : postPtrs)
-		if (q)
-			(void)hipFree(q);
-	void* ptrs[] = { p->guardLog, p->guardCount, p->bandMeta, p->bands, p->orderKeys, p->order, p->suspended, p->paths, p->mtStates, p->table, p->costFields, p->wfWorkspace, p->wfError, p->tilesCtl, p->tilesFallback, p->nodes, p->heaps, p->keymaps, p->expanded, p->rsLogs, p->results, p->prof, p->dStarts,
-		p->dGoals, p->dSeeds };
-	for (void* q : ptrs)
-		if (q)
-			(void)hipFree(q);
-	if (p->e0)
-		(void)hipEventDestroy(p->e0);
-	if (p->e1)
-		(void)hipEventDestroy(p->e1);
-	if (p->e2)
-		(void)hipEventDestroy(p->e2);
 	pp_map* map = p->map;
 	pph::footprint_release(p->footprint);
 	delete p;
@@ -629,43 +650,43 @@ static int create_planner(pp_map* map, const pp_hybrid_params* params, int32_t m
 	// allocations, which makes this stream's queue allocate its scratch now, and (ii) the planner refuses to take memory
 	// beyond free - reserve, where the reserve covers the same scratch for the other hardware queues a process may use.
 	size_t planned = 0;
-	std::vector<std::pair<void**, size_t>> wanted;
-	auto alloc = [&](void** ptr, size_t bytes) {
+	std::vector<std::pair<pph::DeviceMem*, size_t>> wanted; // taken below, after the warm-up and the headroom check
+	auto alloc = [&](pph::DeviceMem& mem, size_t bytes) {
 		bytes = bytes ? bytes : 1;
-		wanted.push_back({ ptr, bytes });
+		wanted.push_back({ &mem, bytes });
 		planned += (bytes + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1); // the allocator works in 2 MiB granules
 	};
-	alloc((void**)&p->table, tableBytes);
-	alloc((void**)&p->costFields, B * (size_t)A.fieldElems * sizeof(float));
-	alloc((void**)&p->wfWorkspace, (size_t)p->wfBytesPerSlot * p->wfSlots);
-	alloc((void**)&p->tilesCtl, 64);
-	alloc((void**)&p->tilesFallback, B * 4);
-	alloc((void**)&p->wfError, 32); // control block: {wavefront error flag, wavefront goal counter, rows query counter, set-aside count, (unused),
+	alloc(p->table, tableBytes);
+	alloc(p->costFields, B * (size_t)A.fieldElems * sizeof(float));
+	alloc(p->wfWorkspace, (size_t)p->wfBytesPerSlot * p->wfSlots);
+	alloc(p->tilesCtl, 64);
+	alloc(p->tilesFallback, B * 4);
+	alloc(p->wfError, 32); // control block: {wavefront error flag, wavefront goal counter, rows query counter, set-aside count, (unused),
 	                                // (unused), wavefront done counter, spare slots handed out}
 	// search buffers: one set per resident row (rows kernel) or per query (one-query-per-wave kernel)
 	const size_t S = p->rowsKernel ? (size_t)p->searchRows + (size_t)A.extraSlots : B;
-	alloc((void**)&p->suspended, (size_t)(A.listCap > 0 ? A.listCap : 1) * sizeof(SuspendRec));
-	alloc((void**)&p->mtStates, (p->rowsKernel ? S : 1) * Mt64::N * sizeof(unsigned long long));
-	alloc((void**)&p->nodes, S * N * sizeof(Node));
-	alloc((void**)&p->bands, S * (size_t)(kBands * kBandCap) * sizeof(HeapEntry));
-	alloc((void**)&p->bandMeta, S * (size_t)kBands);
-	alloc((void**)&p->heaps, S * N * sizeof(HeapEntry));
-	alloc((void**)&p->keymaps, S * A.ks.size() * 4);
+	alloc(p->suspended, (size_t)(A.listCap > 0 ? A.listCap : 1) * sizeof(SuspendRec));
+	alloc(p->mtStates, (p->rowsKernel ? S : 1) * Mt64::N * sizeof(unsigned long long));
+	alloc(p->nodes, S * N * sizeof(Node));
+	alloc(p->bands, S * (size_t)(kBands * kBandCap) * sizeof(HeapEntry));
+	alloc(p->bandMeta, S * (size_t)kBands);
+	alloc(p->heaps, S * N * sizeof(HeapEntry));
+	alloc(p->keymaps, S * A.ks.size() * 4);
 	if (use != PlannerUse::Pipeline) // (a pipeline keeps the expansion log only for parity tests: 4 B x max_nodes per field slot)
-		alloc((void**)&p->expanded, B * N * 4);
-	alloc((void**)&p->order, B * 4);
-	alloc((void**)&p->orderKeys, B * 4);
-	alloc((void**)&p->paths, B * (size_t)A.maxPath * sizeof(PathRec));
-	alloc((void**)&p->rsLogs, B * kRsLogCap * sizeof(RsLogEntry));
-	alloc((void**)&p->results, B * sizeof(DevResult));
+		alloc(p->expanded, B * N * 4);
+	alloc(p->order, B * 4);
+	alloc(p->orderKeys, B * 4);
+	alloc(p->paths, B * (size_t)A.maxPath * sizeof(PathRec));
+	alloc(p->rsLogs, B * kRsLogCap * sizeof(RsLogEntry));
+	alloc(p->results, B * sizeof(DevResult));
 	if (!p->rowsKernel) { // the lattice-line log of pp_planner_certify_lattice: planners that keep the tree per query
-		alloc((void**)&p->guardLog, B * (size_t)kGuardLogCap * sizeof(GuardRec));
-		alloc((void**)&p->guardCount, B * 4);
+		alloc(p->guardLog, B * (size_t)kGuardLogCap * sizeof(GuardRec));
+		alloc(p->guardCount, B * 4);
 	}
-	alloc((void**)&p->prof, (forPipeline ? 1 : B) * PH_COUNT * sizeof(unsigned long long));
-	alloc((void**)&p->dStarts, B * 24);
-	alloc((void**)&p->dGoals, B * 24);
-	alloc((void**)&p->dSeeds, B * 8);
+	alloc(p->prof, (forPipeline ? 1 : B) * PH_COUNT * sizeof(unsigned long long));
+	alloc(p->dStarts, B * 24);
+	alloc(p->dGoals, B * 24);
+	alloc(p->dSeeds, B * 8);
 	{
 		if (int rc = warm_up_kernels(p, map)) {
 			free_planner(p);
@@ -688,16 +709,16 @@ static int create_planner(pp_map* map, const pp_hybrid_params* params, int32_t m
 		}
 		for (auto& w : wanted)
 			if (e == hipSuccess)
-				e = hipMalloc(w.first, w.second);
+				e = w.first->alloc(w.second);
 	}
 	if (e == hipSuccess)
 		e = hipMemset(p->tilesCtl, 0, 64);
 	if (e == hipSuccess)
-		e = hipEventCreate(&p->e0);
+		e = p->e0.create();
 	if (e == hipSuccess)
-		e = hipEventCreate(&p->e1);
+		e = p->e1.create();
 	if (e == hipSuccess)
-		e = hipEventCreate(&p->e2);
+		e = p->e2.create();
 	if (e != hipSuccess) {
 		free_planner(p);
 		return pph::hip_fail(e, "planner allocation");
@@ -749,10 +770,7 @@ int pp_planner_set_footprint(pp_planner* planner, pp_footprint* fp)
 	PP_HIP_TRY(hipStreamSynchronize(s)); // a batch in flight keeps the footprint it was launched with
 	if (fp) {
 		// an empty dispatch: the queue allocates the kernel's scratch here, where a failure is an error code (see warm_up_kernels)
-		hipLaunchKernelGGL(k_hybrid_search_footprint, dim3(1), dim3(64), 0, s, planner->args, fp->fp, 0, (const double*)nullptr, (const double*)nullptr, (const uint64_t*)nullptr,
-			(const float*)nullptr, (Node*)nullptr, (HeapEntry*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (RsLogEntry*)nullptr, (PathRec*)nullptr, (DevResult*)nullptr,
-			(HeapEntry*)nullptr, planner->bandInvW, (uint8_t*)nullptr);
-		PP_HIP_TRY(hipGetLastError());
+		PP_HIP_TRY(launch_search_footprint(planner, s, 1, fp->fp, Queries {}));
 		PP_HIP_TRY(hipStreamSynchronize(s));
 		__atomic_add_fetch(&fp->refs, 1, __ATOMIC_RELAXED);
 	}
@@ -872,45 +890,45 @@ int pp_planner_search_batch_dev(pp_planner* planner, int32_t n_queries, const do
 	constexpr int dbgSkip = 0;
 #endif
 	if (dbgSkip != 1) {
-		pph::WavefrontPublish pub;
-		pub.tilesCtl = planner->tilesCtl;
-		pub.tilesFallback = planner->tilesFallback;
-		pub.occBits = planner->map->occBits;
-		PP_HIP_TRY(pph::launch_wavefront(s, m, n_queries, nullptr, planner->costFields, planner->wfWorkspace, planner->wfBytesPerSlot, planner->wfSlots,
-			planner->wfError, nullptr, /*tiledOut=*/true, /*goalPoses=*/goals_dev, /*countersZeroed=*/true, ordered ? starts_dev : nullptr, ordered ? planner->order : nullptr,
-			planner->wfError + 6, planner->orderKeys, pub));
+		pph::WavefrontLaunch L;
+		L.nGoals = n_queries;
+		L.goalPoses = goals_dev;
+		L.cost = planner->costFields;
+		L.tiledOut = true;
+		L.workspace = planner->wfWorkspace.get();
+		L.workspaceBytesPerSlot = planner->wfBytesPerSlot;
+		L.nSlots = planner->wfSlots;
+		L.errorFlag = planner->wfError;
+		L.countersZeroed = true;
+		if (ordered) {
+			L.orderStarts = starts_dev;
+			L.orderOut = planner->order;
+		}
+		L.doneCounter = planner->wfError + 6;
+		L.orderKeys = planner->orderKeys;
+		L.pub.tilesCtl = planner->tilesCtl;
+		L.pub.tilesFallback = planner->tilesFallback;
+		L.pub.occBits = planner->map->occBits;
+		PP_HIP_TRY(pph::launch_wavefront(s, m, L));
 	}
 	PP_HIP_TRY(hipEventRecord(planner->e1, s));
+	const Queries batch { n_queries, starts_dev, goals_dev, seeds_dev };
 	if (dbgSkip == 2) {
 	} else if (planner->rowsKernel) {
 		// four queries per wave, taken from a counter by a persistent grid (pp_planner_rows.hpp)
 		const int wavesWanted = (n_queries + kRowsPerWave - 1) / kRowsPerWave;
 		const int wavesMax = planner->searchRows / kRowsPerWave;
 		const int grid = wavesWanted < wavesMax ? wavesWanted : wavesMax;
-		int* const ctl = planner->nextQuery; // {query counter, set-aside count}
-		int* const spare = planner->wfError + 7;
-		const int cap = planner->args.suspendAfter;
-		constexpr int kWg = PP_ROWS_WAVES_PER_WG;
 		planner->args.rowsWaves = grid;
-		hipLaunchKernelGGL(k_hybrid_search_rows<false>, dim3((grid + kWg - 1) / kWg), dim3(64 * kWg), 0, s, planner->args, n_queries, starts_dev, goals_dev, seeds_dev, planner->costFields, planner->nodes,
-			planner->heaps, planner->keymaps, planner->expanded, planner->rsLogs, planner->paths, planner->mtStates, planner->results, ctl, planner->suspended,
-			ordered ? planner->order : nullptr, cap, ctl + 1, spare, planner->bands, planner->bandInvW, planner->bandMeta, PipeView {});
-		PP_HIP_TRY(hipGetLastError());
-		if (cap > 0 && dbgSkip != 3) // whatever was set aside: one wave per query (the block count is read on the device)
-			hipLaunchKernelGGL(k_hybrid_search<false>, dim3(planner->args.listCap), dim3(64), 0, s, planner->args, n_queries, starts_dev, goals_dev, seeds_dev,
-				planner->costFields, planner->nodes, planner->heaps, planner->keymaps, planner->expanded, planner->rsLogs, planner->paths, planner->results, planner->prof,
-				planner->suspended, ctl + 1, planner->mtStates, planner->bands, planner->bandInvW, planner->bandMeta);
+		PP_HIP_TRY(launch_search_rows<false>(planner, s, planner->args, batch, ordered ? planner->order.get() : nullptr, PipeView {}));
+		if (planner->args.suspendAfter > 0 && dbgSkip != 3) // whatever was set aside: one wave per query (the block count is read on the device)
+			PP_HIP_TRY(launch_search<false>(planner, s, planner->args.listCap, batch, /*resume=*/true));
 	} else if (planner->footprint)
-		hipLaunchKernelGGL(k_hybrid_search_footprint, dim3(n_queries), dim3(64), 0, s, planner->args, planner->footprint->fp, n_queries, starts_dev, goals_dev, seeds_dev,
-			planner->costFields, planner->nodes, planner->heaps, planner->keymaps, planner->expanded, planner->rsLogs, planner->paths, planner->results, planner->bands,
-			planner->bandInvW, planner->bandMeta);
+		PP_HIP_TRY(launch_search_footprint(planner, s, n_queries, planner->footprint->fp, batch));
 	else if (planner->profile)
-		hipLaunchKernelGGL(k_hybrid_search<true>, dim3(n_queries), dim3(64), 0, s, planner->args, n_queries, starts_dev, goals_dev, seeds_dev, planner->costFields,
-			planner->nodes, planner->heaps, planner->keymaps, planner->expanded, planner->rsLogs, planner->paths, planner->results, planner->prof, nullptr, nullptr, nullptr, planner->bands, planner->bandInvW, planner->bandMeta);
+		PP_HIP_TRY(launch_search<true>(planner, s, n_queries, batch));
 	else
-		hipLaunchKernelGGL(k_hybrid_search<false>, dim3(n_queries), dim3(64), 0, s, planner->args, n_queries, starts_dev, goals_dev, seeds_dev, planner->costFields,
-			planner->nodes, planner->heaps, planner->keymaps, planner->expanded, planner->rsLogs, planner->paths, planner->results, planner->prof, nullptr, nullptr, nullptr, planner->bands, planner->bandInvW, planner->bandMeta);
-	PP_HIP_TRY(hipGetLastError());
+		PP_HIP_TRY(launch_search<false>(planner, s, n_queries, batch));
 	PP_HIP_TRY(hipEventRecord(planner->e2, s));
 	planner->lastBatch = n_queries;
 	return PP_OK;
@@ -1188,24 +1206,17 @@ int pp_planner_postprocess(pp_planner* planner, int32_t n_queries, float path_in
 	hipStream_t s = map->ctx->stream;
 	const size_t B = (size_t)planner->maxBatch;
 	if (planner->postMaxPoints < max_points) {
-		void* old[] = { planner->post.ratios, planner->post.resampled, planner->post.smoothed, planner->post.cusp, planner->post.optimise };
-		planner->postMaxPoints = 0; // until every buffer below exists again: a failed allocation must not leave a stale capacity behind
-		for (void* q : old)
-			if (q)
-				(void)hipFree(q);
-		planner->post.ratios = planner->post.resampled = planner->post.smoothed = nullptr;
-		planner->post.cusp = planner->post.optimise = nullptr;
-		PP_HIP_TRY(hipMalloc((void**)&planner->post.ratios, B * max_points * 8));
-		PP_HIP_TRY(hipMalloc((void**)&planner->post.resampled, B * max_points * 24));
-		PP_HIP_TRY(hipMalloc((void**)&planner->post.smoothed, B * max_points * 24));
-		PP_HIP_TRY(hipMalloc((void**)&planner->post.cusp, B * max_points));
-		PP_HIP_TRY(hipMalloc((void**)&planner->post.optimise, B * max_points));
+		planner->postMaxPoints = planner->postDone = 0; // until every buffer below exists again: a failed allocation must not leave a stale capacity behind
+		PP_HIP_TRY(planner->postRatios.alloc(B * max_points * 8));
+		PP_HIP_TRY(planner->postResampled.alloc(B * max_points * 24));
+		PP_HIP_TRY(planner->postSmoothed.alloc(B * max_points * 24));
+		PP_HIP_TRY(planner->postCusp.alloc(B * max_points));
+		PP_HIP_TRY(planner->postOptimise.alloc(B * max_points));
 		planner->postMaxPoints = max_points;
 	}
-	if (!planner->post.edgeEnd)
-		PP_HIP_TRY(hipMalloc((void**)&planner->post.edgeEnd, B * (size_t)(planner->maxPath + 1) * 8));
-	if (!planner->post.out)
-		PP_HIP_TRY(hipMalloc((void**)&planner->post.out, B * sizeof(pp_post_result)));
+	PP_HIP_TRY(planner->postEdgeEnd.ensure(B * (size_t)(planner->maxPath + 1) * 8));
+	PP_HIP_TRY(planner->postOut.ensure(B * sizeof(pp_post_result)));
+	const PostBuffers post { planner->postRatios, planner->postResampled, planner->postSmoothed, planner->postCusp, planner->postOptimise, planner->postEdgeEnd, planner->postOut };
 	PostParams P {};
 	P.pathInterpolation = path_interpolation;
 	pp_smoother_params sp { 1e-3f, 2000, 0.01f, 0.0f, 0.4f, 0.02f, 0.2f, 0.4f, 0.2f, (float)(1.0 / planner->params.min_turning_radius) }; // smoother.h:28-60, hybrid_a_star.cpp:214
@@ -1227,10 +1238,10 @@ int pp_planner_postprocess(pp_planner* planner, int32_t n_queries, float path_in
 	planner->args.m = map->view();
 	const size_t lds = (size_t)max_points * 16;
 	hipLaunchKernelGGL(k_postprocess, dim3(n_queries), dim3(kPostThreads), lds, s, planner->args, P, n_queries, planner->paths, planner->rsLogs, planner->results,
-		map->obstLabel[map->obstResult], map->voroLabel[map->voroResult], planner->post);
+		map->obstLabel[map->obstResult].get(), map->voroLabel[map->voroResult].get(), post);
 	PP_HIP_TRY(hipGetLastError());
 	planner->hostPost.resize(n_queries);
-	PP_HIP_TRY(hipMemcpyAsync(planner->hostPost.data(), planner->post.out, (size_t)n_queries * sizeof(pp_post_result), hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipMemcpyAsync(planner->hostPost.data(), planner->postOut, (size_t)n_queries * sizeof(pp_post_result), hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	planner->postDone = n_queries;
 	planner->postPoints = max_points;
@@ -1251,11 +1262,11 @@ int pp_planner_get_processed_path(pp_planner* planner, int32_t q, double* sample
 	if (n == 0)
 		return PP_OK;
 	if (sampled_host)
-		PP_HIP_TRY(hipMemcpy(sampled_host, planner->post.resampled + (size_t)q * cap * 3, n * 24, hipMemcpyDeviceToHost));
+		PP_HIP_TRY(hipMemcpy(sampled_host, planner->postResampled + (size_t)q * cap * 3, n * 24, hipMemcpyDeviceToHost));
 	if (cusp_host)
-		PP_HIP_TRY(hipMemcpy(cusp_host, planner->post.cusp + (size_t)q * cap, n, hipMemcpyDeviceToHost));
+		PP_HIP_TRY(hipMemcpy(cusp_host, planner->postCusp + (size_t)q * cap, n, hipMemcpyDeviceToHost));
 	if (smoothed_host)
-		PP_HIP_TRY(hipMemcpy(smoothed_host, planner->post.smoothed + (size_t)q * cap * 3, n * 24, hipMemcpyDeviceToHost));
+		PP_HIP_TRY(hipMemcpy(smoothed_host, planner->postSmoothed + (size_t)q * cap * 3, n * 24, hipMemcpyDeviceToHost));
 	return PP_OK;
 }
 

@@ -678,77 +678,46 @@ int pp_rrt_run_batch(pp_ctx* ctx, pp_map* map, const double lower[2], const doub
 		probs[i].goaly = goals_xy[2 * i + 1];
 		probs[i].seed = seeds[i];
 	}
-	RrtProblem* dprob = nullptr;
-	double2* pts = nullptr;
-	int32_t *parent = nullptr, *cellHead = nullptr, *cellNext = nullptr;
-	double* cost = nullptr;
-	RrtOut* dout = nullptr;
-	int32_t *child = nullptr, *queue = nullptr;
-	double* edgeLen = nullptr;
+	pph::Dev<RrtProblem> dprob;
+	pph::Dev<double2> pts;
+	pph::Dev<int32_t> parent, cellHead, cellNext;
+	pph::Dev<double> cost;
+	pph::Dev<RrtOut> dout;
+	pph::Dev<int32_t> child, queue; // children lists, ...
+	pph::Dev<double> edgeLen;       // ... edge lengths and the subtree-walk queues of the rewire modes (null otherwise)
 	const size_t cells = (size_t)A.G * A.G;
-	hipError_t e = hipMalloc((void**)&pts, np * cap * sizeof(double2));
-	if (e == hipSuccess)
-		e = hipMalloc((void**)&parent, np * cap * 4);
-	if (e == hipSuccess)
-		e = hipMalloc((void**)&cost, np * cap * 8);
-	if (e == hipSuccess)
-		e = hipMalloc((void**)&cellNext, np * cap * 4);
-	if (e == hipSuccess)
-		e = hipMalloc((void**)&cellHead, np * cells * 4);
-	if (e == hipSuccess)
-		e = hipMalloc((void**)&dout, np * sizeof(RrtOut));
-	if (e == hipSuccess)
-		e = hipMalloc((void**)&dprob, np * sizeof(RrtProblem));
-	if (star >= 2) { // children lists, edge lengths and the subtree-walk queues of the rewire modes
-		if (e == hipSuccess)
-			e = hipMalloc((void**)&child, np * cap * 3 * 4);
-		if (e == hipSuccess)
-			e = hipMalloc((void**)&edgeLen, np * cap * 8);
-		if (e == hipSuccess)
-			e = hipMalloc((void**)&queue, np * cap * 2 * 4);
+	PP_HIP_TRY(pts.alloc(np * cap * sizeof(double2)));
+	PP_HIP_TRY(parent.alloc(np * cap * 4));
+	PP_HIP_TRY(cost.alloc(np * cap * 8));
+	PP_HIP_TRY(cellNext.alloc(np * cap * 4));
+	PP_HIP_TRY(cellHead.alloc(np * cells * 4));
+	PP_HIP_TRY(dout.alloc(np * sizeof(RrtOut)));
+	PP_HIP_TRY(dprob.alloc(np * sizeof(RrtProblem)));
+	if (star >= 2) {
+		PP_HIP_TRY(child.alloc(np * cap * 3 * 4));
+		PP_HIP_TRY(edgeLen.alloc(np * cap * 8));
+		PP_HIP_TRY(queue.alloc(np * cap * 2 * 4));
 	}
 	std::vector<RrtOut> ho(np);
 	std::vector<std::unique_ptr<pp_rrt>> rs(np);
-	if (e == hipSuccess)
-		e = hipMemsetAsync(cellHead, 0xFF, np * cells * 4, ctx->stream); // -1 = empty cell
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(dprob, probs.data(), np * sizeof(RrtProblem), hipMemcpyHostToDevice, ctx->stream);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_rrt, dim3(n_problems), dim3(RT), 0, ctx->stream, A, dprob, pts, parent, cost, cellHead, cellNext, dout, child, edgeLen, queue);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(ho.data(), dout, np * sizeof(RrtOut), hipMemcpyDeviceToHost, ctx->stream);
-	if (e == hipSuccess)
-		e = hipStreamSynchronize(ctx->stream);
-	for (size_t i = 0; i < np && e == hipSuccess; i++) {
+	PP_HIP_TRY(hipMemsetAsync(cellHead, 0xFF, np * cells * 4, ctx->stream)); // -1 = empty cell
+	PP_HIP_TRY(hipMemcpyAsync(dprob, probs.data(), np * sizeof(RrtProblem), hipMemcpyHostToDevice, ctx->stream));
+	hipLaunchKernelGGL(k_rrt, dim3(n_problems), dim3(RT), 0, ctx->stream, A, dprob.get(), pts.get(), parent.get(), cost.get(), cellHead.get(), cellNext.get(), dout.get(), child.get(),
+		edgeLen.get(), queue.get());
+	PP_HIP_TRY(hipGetLastError());
+	PP_HIP_TRY(hipMemcpyAsync(ho.data(), dout, np * sizeof(RrtOut), hipMemcpyDeviceToHost, ctx->stream));
+	PP_HIP_TRY(hipStreamSynchronize(ctx->stream));
+	for (size_t i = 0; i < np; i++) {
 		rs[i] = std::make_unique<pp_rrt>();
 		pp_rrt* r = rs[i].get();
 		const int n = ho[i].nNodes;
 		r->nodes.resize((size_t)n * 2);
 		r->parents.resize(n);
 		r->costs.resize(n);
-		e = hipMemcpy(r->nodes.data(), pts + i * cap, (size_t)n * 16, hipMemcpyDeviceToHost);
-		if (e == hipSuccess)
-			e = hipMemcpy(r->parents.data(), parent + i * cap, (size_t)n * 4, hipMemcpyDeviceToHost);
-		if (e == hipSuccess)
-			e = hipMemcpy(r->costs.data(), cost + i * cap, (size_t)n * 8, hipMemcpyDeviceToHost);
+		PP_HIP_TRY(hipMemcpy(r->nodes.data(), pts + i * cap, (size_t)n * 16, hipMemcpyDeviceToHost));
+		PP_HIP_TRY(hipMemcpy(r->parents.data(), parent + i * cap, (size_t)n * 4, hipMemcpyDeviceToHost));
+		PP_HIP_TRY(hipMemcpy(r->costs.data(), cost + i * cap, (size_t)n * 8, hipMemcpyDeviceToHost));
 	}
-	(void)hipFree(pts);
-	(void)hipFree(parent);
-	(void)hipFree(cost);
-	(void)hipFree(cellNext);
-	(void)hipFree(cellHead);
-	(void)hipFree(dout);
-	(void)hipFree(dprob);
-	if (child)
-		(void)hipFree(child);
-	if (edgeLen)
-		(void)hipFree(edgeLen);
-	if (queue)
-		(void)hipFree(queue);
-	if (e != hipSuccess)
-		return pph::hip_fail(e, "pp_rrt_run_batch");
 	for (size_t i = 0; i < np; i++) {
 		pp_rrt* r = rs[i].get();
 		// GetPath, rrt.h:97-115: states from the root to the solution node

@@ -1366,28 +1366,39 @@ int wavefront_resident_blocks()
 	return perCu * prop.multiProcessorCount;
 }
 
-hipError_t warm_up_wavefront(hipStream_t s, const MapView& m, int32_t* ctlDev)
+/// one launch of the ordered kernel: L's arrays, `pub` as the kernel sees it (the goal counter is pub's, or the word behind the error flag)
+template <bool kProfile>
+static hipError_t launch_ordered(hipStream_t s, int grid, const MapView& m, const WavefrontLaunch& L, const WavefrontPublish& pub)
 {
-	// nGoals = 0: the workgroup reads the goal counter, finds nothing to do and leaves; no other pointer is dereferenced
-	hipLaunchKernelGGL(k_wavefront<false>, dim3(1), dim3(WF_T), 0, s, m, 0, nullptr, nullptr, nullptr, (int64_t)0, 0u, 0u, ctlDev, nullptr, (int*)(ctlDev + 1), 0, nullptr, nullptr,
-		nullptr, nullptr, nullptr, WavefrontPublish {});
+	uint32_t fcap = 0, gcap = 0;
+	if (L.nGoals > 0)
+		wf_caps(m.rows, m.cols, fcap, gcap);
+	hipLaunchKernelGGL(k_wavefront<kProfile>, dim3(grid), dim3(WF_T), 0, s, m, L.nGoals, L.goalCells, L.cost, L.workspace, L.workspaceBytesPerSlot, fcap, gcap, L.errorFlag, L.prof,
+		pub.goalCounter ? pub.goalCounter : (int*)(L.errorFlag + 1), L.tiledOut ? 1 : 0, L.goalPoses, L.orderStarts, L.orderOut, L.doneCounter, L.orderKeys, pub);
 	return hipGetLastError();
 }
 
-hipError_t launch_wavefront(hipStream_t s, const MapView& m, int nGoals, const int32_t* goalCellsDev, float* costDev, void* workspaceDev,
-	int64_t workspaceBytesPerSlot, int nSlots, int32_t* errorFlagDev, unsigned long long* profDev, bool tiledOut, const double* goalPosesDev, bool countersZeroed,
-	const double* orderStartsDev, int32_t* orderOutDev, int* doneCounterDev, float* orderKeysDev, const WavefrontPublish& pub)
+hipError_t warm_up_wavefront(hipStream_t s, const MapView& m, int32_t* ctlDev)
 {
-	if (nGoals > WF_LCAP)
-		orderOutDev = nullptr; // the epilogue sorts in the LDS sort buffer
-	if (nGoals <= 0)
+	// nGoals = 0: the workgroup reads the goal counter, finds nothing to do and leaves; no other pointer is dereferenced
+	WavefrontLaunch none;
+	none.errorFlag = ctlDev;
+	return launch_ordered<false>(s, 1, m, none, none.pub);
+}
+
+hipError_t launch_wavefront(hipStream_t s, const MapView& m, const WavefrontLaunch& launch)
+{
+	if (launch.nGoals <= 0)
 		return hipSuccess;
-	uint32_t fcap, gcap;
-	wf_caps(m.rows, m.cols, fcap, gcap);
-	if (pub.tilesCtl && pub.tilesFallback && !profDev && pub.occBits && wavefront_tiles_enabled() && wavefront_tiles_supported(m.rows, m.cols)) {
+	WavefrontLaunch L = launch;
+	const WavefrontPublish& pub = launch.pub;
+	const int nGoals = L.nGoals;
+	if (nGoals > WF_LCAP)
+		L.orderOut = nullptr; // the epilogue sorts in the LDS sort buffer
+	if (pub.tilesCtl && pub.tilesFallback && !L.prof && pub.occBits && wavefront_tiles_enabled() && wavefront_tiles_supported(m.rows, m.cols)) {
 		// The tile form (pp_wavefront_tiles.hip) builds the fields; behind it, on the same stream, the ordered kernel takes the goals it handed
 		// over (their number is a device word: normally 0, and its few workgroups leave at once), then the hand-out order if the planner wants one.
-		hipError_t e = launch_wavefront_tiles(s, m, nGoals, goalCellsDev, costDev, tiledOut, goalPosesDev, orderStartsDev, orderKeysDev, pub);
+		hipError_t e = launch_wavefront_tiles(s, m, L);
 		if (e != hipSuccess)
 			return e;
 		WavefrontPublish fb = pub;
@@ -1401,7 +1412,7 @@ hipError_t launch_wavefront(hipStream_t s, const MapView& m, int nGoals, const i
 		fb.resetOnExit = pub.tilesCtl + 2;
 		fb.agentPoseLoads = pub.claimed != nullptr;
 		fb.tilesCtl = nullptr;
-		const int fgrid = nSlots < 16 ? (nSlots < nGoals ? nSlots : nGoals) : (nGoals < 16 ? nGoals : 16);
+		const int fgrid = L.nSlots < 16 ? (L.nSlots < nGoals ? L.nSlots : nGoals) : (nGoals < 16 ? nGoals : 16);
 		hipStream_t fs = s;
 		if (pub.fallbackStream && pub.fallbackEvent) {
 			e = hipEventRecord(pub.fallbackEvent, s);
@@ -1413,34 +1424,30 @@ hipError_t launch_wavefront(hipStream_t s, const MapView& m, int nGoals, const i
 		}
 		fb.fallbackStream = nullptr;
 		fb.fallbackEvent = nullptr;
-		hipLaunchKernelGGL(k_wavefront<false>, dim3(fgrid), dim3(WF_T), 0, fs, m, nGoals, goalCellsDev, costDev, workspaceDev, workspaceBytesPerSlot, fcap, gcap, errorFlagDev,
-			(unsigned long long*)nullptr, fb.goalCounter, tiledOut ? 1 : 0, goalPosesDev, orderStartsDev, (int32_t*)nullptr, (int*)nullptr, orderStartsDev ? orderKeysDev : nullptr, fb);
-		e = hipGetLastError();
+		WavefrontLaunch F = L; // the ordered kernel over the handed-over goals: keys only, the order is sorted below
+		F.orderOut = nullptr;
+		F.doneCounter = nullptr;
+		F.orderKeys = L.orderStarts ? L.orderKeys : nullptr;
+		e = launch_ordered<false>(fs, fgrid, m, F, fb);
 		if (e != hipSuccess)
 			return e;
-		if (orderOutDev && orderStartsDev)
-			e = launch_order_by_key(s, nGoals, orderKeysDev, orderOutDev);
+		if (L.orderOut && L.orderStarts)
+			e = launch_order_by_key(s, nGoals, L.orderKeys, L.orderOut);
 		return e;
 	}
-	int grid = nGoals < nSlots ? nGoals : nSlots;
+	int grid = nGoals < L.nSlots ? nGoals : L.nSlots;
 	if (const char* e = getenv("PP_WF_GRID")) { // diagnostic: fewer resident workgroups (is a goal's latency independent of its neighbours on the CU?)
 		const int g = atoi(e);
 		if (g > 0 && g < grid)
 			grid = g;
 	}
-	// errorFlagDev[0] = overflow flag, errorFlagDev[1] = next-goal counter
-	if (!countersZeroed) {
-		hipError_t e = hipMemsetAsync(pub.goalCounter ? (void*)pub.goalCounter : (void*)(errorFlagDev + 1), 0, sizeof(int), s);
+	// errorFlag[0] = overflow flag, errorFlag[1] = next-goal counter
+	if (!L.countersZeroed) {
+		hipError_t e = hipMemsetAsync(pub.goalCounter ? (void*)pub.goalCounter : (void*)(L.errorFlag + 1), 0, sizeof(int), s);
 		if (e != hipSuccess)
 			return e;
 	}
-	if (profDev)
-		hipLaunchKernelGGL(k_wavefront<true>, dim3(grid), dim3(WF_T), 0, s, m, nGoals, goalCellsDev, costDev, workspaceDev, workspaceBytesPerSlot, fcap, gcap, errorFlagDev,
-			profDev, pub.goalCounter ? pub.goalCounter : (int*)(errorFlagDev + 1), tiledOut ? 1 : 0, goalPosesDev, orderStartsDev, orderOutDev, doneCounterDev, orderKeysDev, pub);
-	else
-		hipLaunchKernelGGL(k_wavefront<false>, dim3(grid), dim3(WF_T), 0, s, m, nGoals, goalCellsDev, costDev, workspaceDev, workspaceBytesPerSlot, fcap, gcap, errorFlagDev,
-			profDev, pub.goalCounter ? pub.goalCounter : (int*)(errorFlagDev + 1), tiledOut ? 1 : 0, goalPosesDev, orderStartsDev, orderOutDev, doneCounterDev, orderKeysDev, pub);
-	return hipGetLastError();
+	return L.prof ? launch_ordered<true>(s, grid, m, L, pub) : launch_ordered<false>(s, grid, m, L, pub);
 }
 
 } // namespace pph

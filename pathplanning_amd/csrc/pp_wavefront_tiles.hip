@@ -870,20 +870,21 @@ hipError_t warm_up_wavefront_tiles(hipStream_t s, const MapView& m, int* ctlDev)
 	return hipGetLastError();
 }
 
-hipError_t launch_wavefront_tiles(hipStream_t s, const MapView& m, int nGoals, const int32_t* goalCellsDev, float* costDev, bool tiledOut, const double* goalPosesDev,
-	const double* orderStartsDev, float* orderKeysDev, const WavefrontPublish& pub)
+hipError_t launch_wavefront_tiles(hipStream_t s, const MapView& m, const WavefrontLaunch& L)
 {
+	const WavefrontPublish& pub = L.pub;
+	const int nGoals = L.nGoals;
 	TilesArgs A {};
 	A.m = m;
 	A.nGoals = nGoals;
-	A.goalCells = goalCellsDev;
-	A.goalPoses = goalPosesDev;
-	A.costOut = costDev;
-	A.tiledOut = tiledOut ? 1 : 0;
+	A.goalCells = L.goalCells;
+	A.goalPoses = L.goalPoses;
+	A.costOut = L.cost;
+	A.tiledOut = L.tiledOut ? 1 : 0;
 	A.ctl = pub.tilesCtl;
 	A.fbList = pub.tilesFallback;
-	A.orderStarts = orderStartsDev;
-	A.orderKeys = orderStartsDev ? orderKeysDev : nullptr;
+	A.orderStarts = L.orderStarts;
+	A.orderKeys = L.orderStarts ? L.orderKeys : nullptr;
 	A.stats = pub.tilesStats;
 	A.pub = pub;
 	static const int forceEvery = [] {
