@@ -322,8 +322,8 @@ int pp_planner_num_primitives(pp_planner* planner);
  * -- the start pose, each child's own pose, the arc march and its truncation, the analytic expansion -- goes through the footprint;
  * heuristics, costs, open list, RNG gate and discretisation are untouched.  fp == NULL: back to the point validator.  The planner holds
  * a reference to the footprint.  One-query-per-wave planners only: a planner that runs the rows kernel (pp_planner_search_rows() > 0;
- * create it with max_batch <= 64, or with PP_SEARCH_ROWS=0 in the environment) or is a pipeline's buffer set, and a footprint of
- * another map, are PP_ERR_INVALID. */
+ * create it with max_batch <= 64, or with PP_SEARCH_ROWS=0 in the environment) or is a pipeline's buffer set (a pipeline takes its footprint through
+ * pp_pipeline_set_footprint), and a footprint of another map, are PP_ERR_INVALID. */
 int pp_planner_set_footprint(pp_planner* planner, pp_footprint* fp);
 /* Replaces StatePropagator::m_deltas (algo/hybrid_a_star.cpp:21-28 generates {0, +-0.5 dMax, +-1.0 dMax, ...} from num_generated_motion,
  * which can only give 2 * odd primitives): any list of steering angles [rad]; every angle gives a forward and a backward primitive,
@@ -449,6 +449,19 @@ int pp_pipeline_capacity(pp_pipeline* pipeline);
 int pp_pipeline_search_rows(pp_pipeline* pipeline);
 int pp_pipeline_in_flight(pp_pipeline* pipeline);  /* submitted and not yet polled */
 int pp_pipeline_free_slots(pp_pipeline* pipeline);
+/* Vehicle footprint for the pipeline's search grid (see "vehicle footprint" above and pp_planner_set_footprint: the same sites ask the
+ * footprint, everything else is untouched).  With a footprint the grid is launched as k_hybrid_search_rows_footprint<true>, without one as
+ * k_hybrid_search_rows<true>, exactly as before this entry existed.  fp == NULL clears it.  The pipeline holds a reference: the caller
+ * may destroy its handle while the footprint is set.
+ *  - The waves of the persistent grid keep the kernel and footprint they were launched with, so the call is refused (PP_ERR_INVALID,
+ *    "in flight") while pp_pipeline_in_flight() > 0: poll everything first.  Held slots do not count.  An accepted call waits for the old
+ *    grid's waves on the pipeline's own streams, then makes one empty dispatch of the new kernel so that a scratch-allocation failure
+ *    is an error code.
+ *  - A footprint of another map is PP_ERR_INVALID ("another map").
+ *  - pp_planner_set_footprint on pp_pipeline_planner() stays refused; the batch planner of the rows kernel takes no footprint either.
+ * The search reads the map's float distance grid through the map view, not the footprint's validity bitmaps: a rebuilt distance grid is
+ * caught by the view guard of pp_pipeline_submit_dev.  pp_planner_postprocess on a held slot still smooths against the point validator. */
+int pp_pipeline_set_footprint(pp_pipeline* pipeline, pp_footprint* fp);
 /* Where the queries in flight are, as the row that announced the latest polled result saw the queue's counters (they ride in every
  * completion record): ready = fields built, waiting for a search row; searching = claimed by a row, not yet polled.  A ready queue near 0 = the wavefront stage is the bottleneck, a long one = the search grid is. */
 int pp_pipeline_backlog(pp_pipeline* pipeline, int64_t* ready, int64_t* searching);

@@ -158,6 +158,7 @@ def load():
     L.pp_check_rs_paths_footprint_dev.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
     L.pp_check_se2_paths_footprint.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp]
     L.pp_planner_set_footprint.argtypes = [vp, vp]
+    L.pp_pipeline_set_footprint.argtypes = [vp, vp]
     L.pp_rs_solve.argtypes = [vp, C.c_int64, vp, vp, C.c_double, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp]
     L.pp_rs_solve_dev.argtypes = [vp, C.c_int64, vp, vp, C.c_double, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp]
     L.pp_nonholo_dims.argtypes = [vp, vp, C.POINTER(HybridParams), vp, vp]

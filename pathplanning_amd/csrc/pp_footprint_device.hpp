@@ -88,6 +88,46 @@ PPD_INLINE bool fp_state_valid_sc(const MapView& m, const Footprint& fp, double 
 	return true;
 }
 
+/// fp_state_valid_sc in two halves (see is_state_valid_issue), so that the caller can put other work between the loads and their first
+/// use: `issue` does every bounds test and starts the discs' distance loads (raw[i] for disc i < fp.n; a centre that fails its tests reads
+/// cell 0 instead, so every load is in range), `finish` is the comparisons and the clearance.  Same verdict and, for a valid pose, the same
+/// clearance as fp_state_valid_sc (a minimum in another order over the same floats); no border.  The loops are unrolled so that raw[]
+/// stays in registers; fp.n is wave-uniform.
+PPD_INLINE bool fp_state_valid_issue_sc(const MapView& m, const Footprint& fp, double x, double y, double theta, double s, double c, float (&raw)[kFootprintMaxDiscs])
+{
+	const double lx = x - m.lox, ly = y - m.loy;
+	const double lt = wrap_theta(theta);
+	int row, col;
+	world_to_cell(m, x, y, row, col);
+	bool in = !(lx < m.lbx || lx > m.ubx) && !(ly < m.lby || ly > m.uby) && !(lt < m.lbt || lt > m.ubt) && inside_map(m, row, col);
+#pragma unroll
+	for (int i = 0; i < kFootprintMaxDiscs; i++) {
+		raw[i] = 0.0f;
+		if (i < fp.n) {
+			double cx, cy;
+			disc_centre(fp, i, x, y, s, c, cx, cy);
+			const double lcx = cx - m.lox, lcy = cy - m.loy;
+			world_to_cell(m, cx, cy, row, col);
+			const bool inside = lcx >= m.lbx && lcx <= m.ubx && lcy >= m.lby && lcy <= m.uby && inside_map(m, row, col);
+			in = in && inside;
+			raw[i] = m.dist[inside ? (size_t)row * m.cols + col : (size_t)0];
+		}
+	}
+	return in;
+}
+PPD_INLINE bool fp_state_valid_finish(const Footprint& fp, bool inBounds, const float (&raw)[kFootprintMaxDiscs], float& clearance)
+{
+	float clear = __builtin_huge_valf();
+#pragma unroll
+	for (int i = 0; i < kFootprintMaxDiscs; i++)
+		if (i < fp.n) {
+			inBounds = inBounds && raw[i] >= fp.r[i];
+			clear = fminf(clear, raw[i] - fp.r[i]);
+		}
+	clearance = clear;
+	return inBounds;
+}
+
 /// the same with one sincos of the unwrapped heading, and none when every disc sits on the reference point
 PPD_INLINE bool fp_state_valid(const MapView& m, const Footprint& fp, double x, double y, double theta, float& clearance, float& border)
 {

@@ -203,6 +203,7 @@ struct pp_pipeline {
 	long long wfLaunches = 0, wfGoals = 0, searchLaunches = 0;
 	ppd::MapView lastView {}; // the map view of the last submission (see pp_pipeline_submit_dev)
 	bool viewValid = false;
+	pp_footprint* footprint = nullptr; // pp_pipeline_set_footprint (a reference is held): the grid is launched as k_hybrid_search_rows_footprint<true> with it
 	unsigned long long idleTicks = 250000ull; // idle loop passes of ~4 us: about 1 s.  (50 ms until round 4: shorter than the ~100 ms the first fields of a run take, so the
 	                                         // grid's waves left before their first work arrived and came back by the luck of the top-up launches.)  Idle waves leave at once when
 	                                         // the host has polled every result (PipeCtl::quiesce), so the time-out only matters when a producer really cannot run.
@@ -217,6 +218,7 @@ void free_pipeline(pp_pipeline* P)
 	if (!P)
 		return;
 	pp_planner* const pl = P->pl;
+	pph::footprint_release(P->footprint);
 	delete P; // the streams, events and rings of the pipeline's launches go first ...
 	if (pl)
 		free_planner(pl); // ... then the buffer set those launches worked on
@@ -299,6 +301,17 @@ PipeView pipe_view(const pp_pipeline* P)
 	return v;
 }
 
+/// The one place the search grid's kernel is dispatched from: k_hybrid_search_rows_footprint<true> with the pipeline's footprint when it has one,
+/// k_hybrid_search_rows<true> otherwise.  args.rowsWaves = 0 makes it a warm-up (every wave leaves before it touches anything).
+hipError_t pipe_dispatch_search(pp_pipeline* P, hipStream_t s, const SearchArgs& args)
+{
+	pp_planner* pl = P->pl;
+	const Queries slots { 0, pl->dStarts, pl->dGoals, pl->dSeeds }; // (the slots' inputs: no query count)
+	if (P->footprint)
+		return launch_search_rows_footprint(pl, s, args, P->footprint->fp, slots, pipe_view(P));
+	return launch_search_rows<true>(pl, s, args, slots, nullptr, pipe_view(P));
+}
+
 /// the submission count goes to the device on the control stream, then a launch of the whole grid behind it: waves whose index is
 /// free start working, the others leave at once
 int pipe_launch_search(pp_pipeline* P)
@@ -331,7 +344,7 @@ int pipe_launch_search(pp_pipeline* P)
 	pl->args.rowsWaves = P->waves;
 	pl->args.m = pl->map->view(); // validator tunables may have changed
 	const pp_pipeline::Timed tm = timed_take(P, s, 1, 0);
-	PP_HIP_TRY(launch_search_rows<true>(pl, s, pl->args, Queries { 0, pl->dStarts, pl->dGoals, pl->dSeeds }, nullptr, pipe_view(P))); // (the slots' inputs: no query count)
+	PP_HIP_TRY(pipe_dispatch_search(P, s, pl->args));
 	timed_done(P, s, tm);
 	P->lastLaunch = std::chrono::steady_clock::now();
 	return PP_OK;
@@ -589,6 +602,54 @@ int pp_pipeline_search_rows(pp_pipeline* P) { return P ? P->pl->searchRows : 0; 
 int pp_pipeline_in_flight(pp_pipeline* P) { return P ? (int)(P->nSubmitted - P->doneHead) : 0; }
 int pp_pipeline_free_slots(pp_pipeline* P) { return P ? (int)P->freeSlots.size() : 0; }
 pp_planner* pp_pipeline_planner(pp_pipeline* P) { return P ? P->pl : nullptr; }
+
+int pp_pipeline_set_footprint(pp_pipeline* P, pp_footprint* fp)
+{
+	if (!P) {
+		set_error("null pipeline");
+		return PP_ERR_INVALID;
+	}
+	if (P->dead) {
+		set_error("the pipeline failed in an earlier submission and must be destroyed");
+		return PP_ERR_HIP;
+	}
+	if (fp && fp->map != P->pl->map) {
+		set_error("the footprint belongs to another map than the pipeline's: create one for the pipeline's map with pp_footprint_create");
+		return PP_ERR_INVALID;
+	}
+	if (P->nSubmitted != P->doneHead) {
+		// the waves of the persistent grid keep the kernel and the footprint they were launched with: waves of later launches would run the
+		// other kernel, and a query's result would depend on which wave claims it (the rule of pp_planner_set_primitives and of the map's view)
+		set_error("the pipeline has " + std::to_string(P->nSubmitted - P->doneHead) + " queries in flight: poll them all before changing the footprint");
+		return PP_ERR_INVALID;
+	}
+	if (fp == P->footprint)
+		return PP_OK;
+	PP_HIP_TRY(hipSetDevice(P->pl->map->ctx->device));
+	// the old grid's waves leave as soon as they have seen that everything was polled (PipeCtl::quiesce, written by the poll that took the
+	// last result): they are waited for on the pipeline's own streams, so that the next launch finds every wave index free
+	PP_HIP_TRY(hipStreamSynchronize(P->ctlStream));
+	for (int i = 0; i < kPipeSearchStreams; i++)
+		PP_HIP_TRY(hipStreamSynchronize(P->searchStream[i]));
+	pp_footprint* const old = P->footprint;
+	if (fp) {
+		// an empty dispatch of the footprint kernel: the queue allocates its scratch here, where a failure is an error code (see warm_up_kernels)
+		P->footprint = fp;
+		SearchArgs none = P->pl->args;
+		none.rowsWaves = 0; // every wave leaves at once
+		hipError_t e = pipe_dispatch_search(P, P->searchStream[0], none);
+		if (e == hipSuccess)
+			e = hipStreamSynchronize(P->searchStream[0]);
+		if (e != hipSuccess) {
+			P->footprint = old;
+			return pph::hip_fail(e, "footprint search kernel warm-up (scratch allocation)");
+		}
+		__atomic_add_fetch(&fp->refs, 1, __ATOMIC_RELAXED);
+	}
+	P->footprint = fp;
+	pph::footprint_release(old);
+	return PP_OK;
+}
 
 int pp_pipeline_submit_dev(pp_pipeline* P, int32_t n_queries, const double* starts_dev, const double* goals_dev, const uint64_t* seeds_dev, uint64_t* tickets_out, int32_t* n_accepted)
 {

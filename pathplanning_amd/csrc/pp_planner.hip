@@ -281,7 +281,14 @@ struct PipeView {
 	unsigned long long idleTicks = 0; // loop passes (~4 us each: a sleep and three polls) a wave waits without work before it leaves on its own
 };
 
+// The rows kernel's text is compiled twice (see the head of pp_planner_rows.hpp): k_hybrid_search_rows<kPiped>, then
+// k_hybrid_search_rows_footprint<kPiped>, of which only the pipeline form is instantiated (pp_pipeline_set_footprint).
+#define PP_ROWS_FOOTPRINT 0
 #include "pp_planner_rows.hpp"
+#undef PP_ROWS_FOOTPRINT
+#define PP_ROWS_FOOTPRINT 1
+#include "pp_planner_rows.hpp"
+#undef PP_ROWS_FOOTPRINT
 #include "pp_postprocess.hpp"
 
 } // namespace
@@ -395,6 +402,17 @@ hipError_t launch_search_rows(pp_planner* p, hipStream_t s, const SearchArgs& ar
 	hipLaunchKernelGGL(k_hybrid_search_rows<kPiped>, dim3((waves + kWg - 1) / kWg), dim3(64 * kWg), 0, s, args, q.n, q.starts, q.goals, q.seeds, p->costFields.get(), p->nodes.get(),
 		p->heaps.get(), p->keymaps.get(), p->expanded.get(), p->rsLogs.get(), p->paths.get(), p->mtStates.get(), p->results.get(), ctl, kPiped ? nullptr : p->suspended.get(), order,
 		args.suspendAfter, ctl ? ctl + 1 : nullptr, ctl ? ctl + 5 : nullptr, p->bands.get(), p->bandInvW, p->bandMeta.get(), pipe);
+	return hipGetLastError();
+}
+
+/// k_hybrid_search_rows_footprint<true>: the pipeline form of the rows kernel with a vehicle footprint (pp_pipeline_set_footprint).  The same
+/// grid and arguments as launch_search_rows<true>, plus the footprint by value.
+hipError_t launch_search_rows_footprint(pp_planner* p, hipStream_t s, const SearchArgs& args, const Footprint& foot, const Queries& q, const PipeView& pipe)
+{
+	const int waves = args.rowsWaves > 0 ? args.rowsWaves : 1;
+	hipLaunchKernelGGL(k_hybrid_search_rows_footprint<true>, dim3(waves), dim3(64), 0, s, args, foot, q.n, q.starts, q.goals, q.seeds, p->costFields.get(), p->nodes.get(),
+		p->heaps.get(), p->keymaps.get(), p->expanded.get(), p->rsLogs.get(), p->paths.get(), p->mtStates.get(), p->results.get(), (int*)nullptr, (SuspendRec*)nullptr,
+		(const int32_t*)nullptr, args.suspendAfter, (int*)nullptr, (int*)nullptr, p->bands.get(), p->bandInvW, p->bandMeta.get(), pipe);
 	return hipGetLastError();
 }
 
@@ -752,7 +770,7 @@ int pp_planner_set_footprint(pp_planner* planner, pp_footprint* fp)
 	}
 	if (fp) {
 		if (planner->pipelineOwned) {
-			set_error("this planner is a pipeline's buffer set: the streaming pipeline takes no footprint; plan footprint queries with a pp_planner of max_batch <= 64");
+			set_error("this planner is a pipeline's buffer set: the pipeline's search grid gets its footprint from pp_pipeline_set_footprint, not from its planner");
 			return PP_ERR_INVALID;
 		}
 		if (planner->rowsKernel) {

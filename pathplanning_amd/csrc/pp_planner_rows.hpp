@@ -17,8 +17,18 @@
 //   * the Mersenne-Twister state of a query lives in HBM (2.5 KB per query, one 8-byte read per expansion).
 // Pop order, node numbering, RNG draws and every counter are identical to the one-query-per-wave kernel and to the
 // oracle (tests/test_gpu_hybrid.py checks the expanded sequence).
-#pragma once
+//
+// Included TWICE by pp_planner.hip, which sets PP_ROWS_FOOTPRINT: 0 gives k_hybrid_search_rows<kPiped> (the reference's point validator),
+// 1 gives k_hybrid_search_rows_footprint<kPiped> -- the same text with one more by-value argument, `foot`, and every "is this pose / arc /
+// Reeds-Shepp path valid" routed through it (pp_footprint_device.hpp; Node::dist0 and c_d0 then hold the footprint's clearance instead of
+// the obstacle distance).  The two differ in preprocessor branches only, so the point kernels' text is what it was before the second
+// kernel existed (a shared __device__ function template moved their spills: DESIGN.md section 4.8b).
+#ifndef PP_ROWS_FOOTPRINT
+#error "pp_planner_rows.hpp is the body of the rows kernels of pp_planner.hip, which defines PP_ROWS_FOOTPRINT before each include"
+#endif
 
+#ifndef PP_ROWS_PREAMBLE_DONE
+#define PP_ROWS_PREAMBLE_DONE 1
 #ifndef PP_ROWS_STATS
 #define PP_ROWS_STATS 0 // diagnostic build: histogram of busy rows per wave iteration, printed when a planner is destroyed
 #endif
@@ -41,9 +51,17 @@ __device__ unsigned long long g_rowsStats[24];
 #define PP_PIPE_POLL_EVERY 8
 #endif
 constexpr int kPollEvery = PP_PIPE_POLL_EVERY; // pipeline: an idle row that found the ring empty looks again every kPollEvery-th pass of its wave
+#endif // PP_ROWS_PREAMBLE_DONE
 
+#if PP_ROWS_FOOTPRINT
+#define PP_ROWS_KERNEL k_hybrid_search_rows_footprint
+#define PP_ROWS_FOOT_ARG Footprint foot, // (by value and wave-uniform: the disc loops are uniform control flow)
+#else
+#define PP_ROWS_KERNEL k_hybrid_search_rows
+#define PP_ROWS_FOOT_ARG
+#endif
 template <bool kPiped>
-__global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER_SIMD) k_hybrid_search_rows(SearchArgs A, int nQueries, const double* __restrict__ starts,
+__global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER_SIMD) PP_ROWS_KERNEL(SearchArgs A, PP_ROWS_FOOT_ARG int nQueries, const double* __restrict__ starts,
 	const double* __restrict__ goals, const uint64_t* __restrict__ seeds, const float* __restrict__ costFields, Node* __restrict__ nodesBase,
 	HeapEntry* __restrict__ heapBase, uint32_t* __restrict__ keymapBase, uint32_t* __restrict__ expandedBase, RsLogEntry* __restrict__ rsLogBase,
 	PathRec* __restrict__ pathBase, unsigned long long* __restrict__ mtBase, DevResult* __restrict__ results, int* __restrict__ nextQuery,
@@ -495,10 +513,17 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 					root.key = ok ? key : kNoKey;
 					root.action = -1;
 					root.dead = 0;
+#if PP_ROWS_FOOTPRINT
+					{
+						float cl, bd;
+						root.dist0 = fp_state_valid_sc(m, foot, start.x, start.y, start.t, rs_, rc_, cl, bd) ? cl : -1.0f;
+					}
+#else
 					{
 						float d0;
 						root.dist0 = is_state_valid(m, start.x, start.y, start.t, d0) ? d0 : -1.0f;
 					}
+#endif
 					nodes[0] = root;
 					if (ok)
 						keymap[key] = kExplored; // the root is inserted in the explored set at init (a_star.h:361)
@@ -758,14 +783,28 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 				lanePathChecks++;
 				// validity / distance of the child's own pose: the first march sample of ITS children (not a counted check)
 				float cd0;
+#if PP_ROWS_FOOTPRINT
+				float cRaw[kFootprintMaxDiscs]; // the discs' obstacle distances at the child's pose, in flight under the march
+				const bool cIn = fp_state_valid_issue_sc(m, foot, child.x, child.y, child.t, cs, cc, cRaw);
+#else
 				const bool cIn = is_state_valid_issue(m, child.x, child.y, child.t, cd0);
+#endif
 				ROWS_STAMP(4) // child's own validity
+#if PP_ROWS_FOOTPRINT
+				// the footprint's march from the parent's stored clearance; a disc centre moves up to 1 + |kappa| rho faster than the reference point
+				const bool pathValid = is_arc_valid_fp_from(m, foot, fp_gain(foot, fabs(a.kappa)), a, pDist0, lastValidRatio, checks);
+#else
 				const bool pathValid = is_path_valid_from(m, a, a.init, pDist0, lastValidRatio, checks);
+#endif
 				ROWS_STAMP(5) // validity march
 				// the values the look-ups above fetched (loaded under the march)
 				hh = combined_heuristic_finish(A.heur, hl);
 				const double voroFull = voronoi_cost_finish(voroRaw, A.rp.voroDiagRes, A.rp.voronoiMult);
+#if PP_ROWS_FOOTPRINT
+				d0 = fp_state_valid_finish(foot, cIn, cRaw, cd0) ? cd0 : -1.0f;
+#else
 				d0 = is_state_valid_finish(m, cIn, cd0) ? cd0 : -1.0f;
+#endif
 				if (!pathValid) {
 					// PathConstantSteer::Truncate, paths/path_constant_steer.cpp:16-20
 					child = a.interpolate_sc((double)lastValidRatio, cs, cc);
@@ -778,7 +817,12 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 						if (packed)
 							st = keymap[key];
 						hh = combined_heuristic_sc(A.heur, m, field, goal, child, cs, cc);
+#if PP_ROWS_FOOTPRINT
+						float cb;
+						d0 = fp_state_valid_sc(m, foot, child.x, child.y, child.t, cs, cc, cd0, cb) ? cd0 : -1.0f;
+#else
 						d0 = is_state_valid(m, child.x, child.y, child.t, cd0) ? cd0 : -1.0f;
+#endif
 					}
 				}
 				laneStateChecks += checks;
@@ -1028,7 +1072,11 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 					double* const pre = W.rsPre[lane >> 4];
 					path.make_prefix(pre);
 					const rs::PrefixedPath ppath = { path, pre, path.length };
+#if PP_ROWS_FOOTPRINT
+					const bool valid = is_path_valid_fp(m, foot, fp_gain(foot, 1.0 / A.rmin), ppath, path.init, lastRatio, checks);
+#else
 					const bool valid = is_path_valid(m, ppath, path.init, lastRatio, checks);
+#endif
 					c_valid[sb + kRowRs] = 0;
 					s_rsChecks[lane >> 4] = checks;
 					if (valid) {
@@ -1054,10 +1102,17 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 							c_h[sb + kRowRs] = hh;
 							c_sin[sb + kRowRs] = s_;
 							c_cos[sb + kRowRs] = c_;
+#if PP_ROWS_FOOTPRINT
+							{
+								float rd0, rb;
+								c_d0[sb + kRowRs] = fp_state_valid_sc(m, foot, child.x, child.y, child.t, s_, c_, rd0, rb) ? rd0 : -1.0f;
+							}
+#else
 							{
 								float rd0;
 								c_d0[sb + kRowRs] = is_state_valid(m, child.x, child.y, child.t, rd0) ? rd0 : -1.0f;
 							}
+#endif
 							c_state[sb + kRowRs] = keymap[key];
 							c_action[sb + kRowRs] = (int16_t)(1000 + word);
 						}
@@ -1160,3 +1215,5 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 #undef ROW_MT
 #undef ROW_BANDS
 }
+#undef PP_ROWS_KERNEL
+#undef PP_ROWS_FOOT_ARG

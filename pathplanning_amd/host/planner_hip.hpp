@@ -1014,7 +1014,16 @@ public:
 		}
 		if (pp_pipeline_create(validator->Device(), &hp, m_capacity, m_maxNodes, m_searchRows, 0, &m_pipe))
 			return false;
-		return pp_planner_set_nonholo_table(pp_pipeline_planner(m_pipe), nullptr) == 0;
+		m_pipeFootprint = nullptr;
+		if (pp_planner_set_nonholo_table(pp_pipeline_planner(m_pipe), nullptr))
+			return false;
+		try {
+			SyncFootprint(); // the validator's footprint goes to the pipeline's search grid
+		} catch (const std::exception& e) {
+			std::fprintf(stderr, "[pathplanning_amd] HybridAStarPipeline::Initialize: %s\n", e.what());
+			return false;
+		}
+		return true;
 	}
 	/// takes a prefix of the queries (as many as there are free slots) and returns how many; `tickets` (optional) gets their ids
 	int Submit(const std::vector<Pose2d>& starts, const std::vector<Pose2d>& goals, const std::vector<uint64_t>& seeds, std::vector<uint64_t>* tickets = nullptr)
@@ -1024,6 +1033,7 @@ public:
 		if (!m_pipe || n == 0)
 			return 0;
 		m_validator->Device(); // pushes map edits / tunables
+		SyncFootprint();       // a footprint set, changed or cleared since the last submission; throws while queries are in flight
 		std::vector<uint64_t> t((size_t)n);
 		int32_t taken = 0;
 		ppCheck(pp_pipeline_submit(m_pipe, n, &starts[0].position.v[0], &goals[0].position.v[0], seeds.data(), t.data(), &taken));
@@ -1057,10 +1067,21 @@ public:
 	int FreeSlots() const { return m_pipe ? pp_pipeline_free_slots(m_pipe) : 0; }
 
 private:
+	/// hands the validator's footprint as it is now to the pipeline (HybridAStar::SyncFootprint); the grid's waves keep the footprint they were
+	/// launched with, so a change with queries in flight throws with the library's message: poll everything first
+	void SyncFootprint()
+	{
+		pp_footprint* want = m_validator->DeviceFootprint();
+		if (want == m_pipeFootprint)
+			return;
+		ppCheck(pp_pipeline_set_footprint(m_pipe, want));
+		m_pipeFootprint = want; // (the pipeline holds a reference: the address stays taken while it is set)
+	}
 	HybridAStar::SearchParameters m_param;
 	int m_capacity, m_maxNodes, m_searchRows;
 	Ref<StateValidatorOccupancyMap> m_validator;
 	pp_pipeline* m_pipe = nullptr;
+	pp_footprint* m_pipeFootprint = nullptr;
 };
 
 /// RRT<Point2d, 2> / RRTStar<Point2d, 2> with PathConnectionR2; validator == nullptr is StateValidatorFree.

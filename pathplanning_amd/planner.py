@@ -725,6 +725,20 @@ class HybridAStarPipeline:
         self.search_rows = self.lib.pp_pipeline_search_rows(self.h)
         self.num_primitives = self.lib.pp_planner_num_primitives(self.planner_h)
         self._held = {}  # ticket -> QueryResult of completed queries polled with release=False
+        self._footprint = None  # set_footprint
+
+    def set_footprint(self, footprint):
+        """Every validity question of the pipeline's search grid goes through `footprint` (class Footprint; see HybridAStarBatch.set_footprint)
+        instead of the point validator; None restores the point validator, and the grid then runs the kernel it ran before.  The grid's waves
+        keep the footprint they were launched with, so the call raises PPError ("in flight") unless every submitted query has been polled;
+        an accepted call waits for the old grid's waves.  The pipeline holds its own reference: the Footprint object may be closed afterwards."""
+        check(self.lib.pp_pipeline_set_footprint(self.h, footprint.h if footprint is not None else None))
+        self._footprint = footprint
+
+    @property
+    def footprint(self):
+        """the Footprint last accepted by set_footprint, or None"""
+        return self._footprint
 
     def initialize(self, nonholo_table=None):
         t = None if nonholo_table is None else np.ascontiguousarray(nonholo_table, dtype=np.float64)
@@ -848,7 +862,8 @@ class HybridAStarPipeline:
     def postprocess_held(self, n_slots=None, path_interpolation=0.1, smoother=None, max_points=2048):
         """HybridAStar::SearchPath's post-processing (hybrid_a_star.cpp:260-304) over the field slots 0 .. n_slots-1 of the pipeline's buffer
         set (pp_planner_postprocess on pp_pipeline_planner()): meaningful for slots whose queries are completed and HELD (polled with
-        release=False); read a query's processed path with get_processed_path_of(ticket)."""
+        release=False); read a query's processed path with get_processed_path_of(ticket).  The smoother knows the point validator only:
+        with a footprint set (set_footprint) the search's plans respect it, the smoothed paths are checked against the reference point alone."""
         n = self.capacity if n_slots is None else int(n_slots)
         sp = None
         if smoother is not None:
