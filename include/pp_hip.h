@@ -278,6 +278,27 @@ int pp_nonholo_build(pp_ctx* ctx, const double lower[3], const double upper[3], 
  * when PP_WF_TILES=0 is in the environment.  goal_xy: world positions. */
 int pp_obstacle_heuristic_dev(pp_map* map, int32_t n_goals, const double* goal_xy_host, float* cost_dev);
 int pp_obstacle_heuristic(pp_map* map, int32_t n_goals, const double* goal_xy_host, float* cost_host);
+/* ---- heuristic clearance ---------------------------------------------------
+ * The validator refuses every pose whose reference point has dist < min_safe_radius; the reference's obstacle heuristic floods over every
+ * cell that is merely unoccupied.  A heuristic clearance is a float radius, finite and >= 0.  FOR THE HEURISTIC ONLY a cell is then
+ * blocked iff
+ *     occupied[cell]  ||  !(dist[cell] >= radius)
+ * with the float comparison of the validator (IsStateValid) on the map's distance grid.  Everything else of a8 is untouched: the diagonal
+ * rule, the goal cell costing 0 even when blocked, a goal outside the map giving a field of +inf, blocked cells keeping +inf.  radius == 0
+ * switches it off: the launch is the one of pp_obstacle_heuristic, same kernels, same arguments.  Validity, costs, the Voronoi term, the
+ * non-holonomic table, open list and RNG are never affected.  The field is the reference's field of the map whose occupancy grid has the
+ * blocked cells added.
+ * Admissibility: with radius <= min_safe_radius the heuristic stays a lower bound wherever the reference's was (no valid pose lies in a
+ * cell it blocks); the same holds with a vehicle footprint when radius is at most the radius of a disc that sits on the reference point.
+ * A larger radius is the caller's choice and is not refused: the field then overestimates, and may be +inf where a plan exists.
+ * The two occupancy views the field kernels read (bytes, padded bit rows) are built from the distance and occupancy grids in one pass on
+ * the map's stream, lazily, and rebuilt whenever either grid has been written since.  A map without a distance grid: PP_ERR_INVALID. */
+/* pp_obstacle_heuristic[_dev] under the rule above (radius 0: exactly those entries).  Negative or non-finite radius: PP_ERR_INVALID. */
+int pp_obstacle_heuristic_clearance_dev(pp_map* map, float radius, int32_t n_goals, const double* goal_xy_host, float* cost_dev);
+int pp_obstacle_heuristic_clearance(pp_map* map, float radius, int32_t n_goals, const double* goal_xy_host, float* cost_host);
+/* Diagnostics: what building the two occupancy views of a clearance costs on this map -- the mean of `reps` launches of the view kernel
+ * into buffers of the call's own, between HIP events on the context's stream, in ms (allocation and a first build are not timed). */
+int pp_heuristic_clearance_build_ms(pp_map* map, float radius, int32_t reps, float* ms_out);
 /* Diagnostics of the tile form (a stamped instantiation of its kernel): the same fields into cost_dev ([n_goals][rows*cols]), plus 16 words
  * {goals built, tile visits, bucket rounds, candidate passes, cells settled, goals handed to the ordered kernel,
  * summed wave cycles, tiles per goal, then shader-clock sums of a tile visit's phases: loads + LDS set-up, the rounds' masks,
@@ -325,6 +346,14 @@ int pp_planner_num_primitives(pp_planner* planner);
  * create it with max_batch <= 64, or with PP_SEARCH_ROWS=0 in the environment) or is a pipeline's buffer set (a pipeline takes its footprint through
  * pp_pipeline_set_footprint), and a footprint of another map, are PP_ERR_INVALID. */
 int pp_planner_set_footprint(pp_planner* planner, pp_footprint* fp);
+/* Heuristic clearance of the planner's obstacle heuristic (see "heuristic clearance" above): for the fields of every later
+ * pp_planner_search_batch[_dev] a cell is blocked iff occupied[cell] || !(dist[cell] >= radius); the search itself (validity, costs, the
+ * other heuristics, open list, RNG) is untouched.  One-query-per-wave and rows planners alike: the field launch is shared.  radius == 0
+ * (the default) is the reference's rule.  Each planner keeps occupancy views of its own, so planners with different radii share a map.
+ * Waits for the planner's stream.  Negative or non-finite radius: PP_ERR_INVALID; so is a pipeline's buffer set (a pipeline takes its
+ * radius through pp_pipeline_set_heuristic_clearance).  radius > min_safe_radius is accepted: see the admissibility note. */
+int pp_planner_set_heuristic_clearance(pp_planner* planner, float radius);
+int pp_planner_heuristic_clearance(pp_planner* planner, float* radius);
 /* Replaces StatePropagator::m_deltas (algo/hybrid_a_star.cpp:21-28 generates {0, +-0.5 dMax, +-1.0 dMax, ...} from num_generated_motion,
  * which can only give 2 * odd primitives): any list of steering angles [rad]; every angle gives a forward and a backward primitive,
  * children in list order, forward first (hybrid_a_star.cpp:65-77).  36 angles = the "72 motion primitives" of BASELINE config 2.
@@ -366,6 +395,10 @@ int pp_planner_start_after_fields_of(pp_planner* planner, pp_planner* predecesso
 int pp_planner_get_path(pp_planner* planner, int32_t q, double* poses_host, int32_t* kind_host, int32_t* prim_host, double* length_host,
 	double* tuv_host);
 int pp_planner_get_expanded(pp_planner* planner, int32_t q, int32_t* cells_host);
+/* Diagnostics: the obstacle-heuristic field the search of query q read ([rows*cols] floats, row-major, +inf where unexplored), as the
+ * planner's last batch built it -- the field of pp_obstacle_heuristic (or, with a heuristic clearance, pp_obstacle_heuristic_clearance)
+ * for that query's goal.  On pp_pipeline_planner() q is a field slot (pp_pipeline_slot_of of a completed, held ticket). */
+int pp_planner_get_obstacle_field(pp_planner* planner, int32_t q, float* cost_host);
 /* ---- after the graph search: HybridAStar::SearchPath's post-processing, batched -----------------
  * (algo/hybrid_a_star.cpp:260-304: composite path of the solution's edges, sampling every path_interpolation metres with
  * cusp snapping, then Smoother::Smooth, algo/smoother.cpp:33-226) for the first n_queries queries of the last batch, one
@@ -462,6 +495,16 @@ int pp_pipeline_free_slots(pp_pipeline* pipeline);
  * The search reads the map's float distance grid through the map view, not the footprint's validity bitmaps: a rebuilt distance grid is
  * caught by the view guard of pp_pipeline_submit_dev.  pp_planner_postprocess on a held slot still smooths against the point validator. */
 int pp_pipeline_set_footprint(pp_pipeline* pipeline, pp_footprint* fp);
+/* Heuristic clearance of the pipeline's field launches (see "heuristic clearance" above): for every goal submitted afterwards a cell is
+ * blocked iff occupied[cell] || !(dist[cell] >= radius); the search grid is untouched.  radius == 0 (the default) is the reference's rule.
+ *  - Fields already built belong to the old rule, so the call is refused (PP_ERR_INVALID, "in flight") while pp_pipeline_in_flight() > 0:
+ *    poll everything first.  Held slots do not count.
+ *  - Negative or non-finite radius: PP_ERR_INVALID.
+ *  - The map-view guard of pp_pipeline_submit_dev covers the clearance's occupancy views: when the map's distance or occupancy grid has been
+ *    written since they were built, they are rebuilt and the wavefront streams are ordered behind the rebuild before the next field launch --
+ *    or, with queries in flight, the submission is refused as it is for the map's own view. */
+int pp_pipeline_set_heuristic_clearance(pp_pipeline* pipeline, float radius);
+int pp_pipeline_heuristic_clearance(pp_pipeline* pipeline, float* radius);
 /* Where the queries in flight are, as the row that announced the latest polled result saw the queue's counters (they ride in every
  * completion record): ready = fields built, waiting for a search row; searching = claimed by a row, not yet polled.  A ready queue near 0 = the wavefront stage is the bottleneck, a long one = the search grid is. */
 int pp_pipeline_backlog(pp_pipeline* pipeline, int64_t* ready, int64_t* searching);

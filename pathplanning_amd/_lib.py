@@ -166,6 +166,13 @@ def load():
     L.pp_nonholo_build_dev.argtypes = [vp, vp, vp, C.POINTER(HybridParams), vp]
     L.pp_obstacle_heuristic.argtypes = [vp, C.c_int32, vp, vp]
     L.pp_obstacle_heuristic_dev.argtypes = [vp, C.c_int32, vp, vp]
+    L.pp_obstacle_heuristic_clearance.argtypes = [vp, C.c_float, C.c_int32, vp, vp]
+    L.pp_obstacle_heuristic_clearance_dev.argtypes = [vp, C.c_float, C.c_int32, vp, vp]
+    L.pp_heuristic_clearance_build_ms.argtypes = [vp, C.c_float, C.c_int32, c_fp]
+    L.pp_planner_set_heuristic_clearance.argtypes = [vp, C.c_float]
+    L.pp_planner_heuristic_clearance.argtypes = [vp, c_fp]
+    L.pp_pipeline_set_heuristic_clearance.argtypes = [vp, C.c_float]
+    L.pp_pipeline_heuristic_clearance.argtypes = [vp, c_fp]
     L.pp_obstacle_heuristic_workspace_bytes.argtypes = [vp]
     L.pp_obstacle_heuristic_profile.argtypes = [vp, C.c_int32, vp, vp]
     L.pp_obstacle_heuristic_tiles_stats.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp]
@@ -185,6 +192,7 @@ def load():
     L.pp_planner_fetch_results.argtypes = [vp, C.c_int32, vp]
     L.pp_planner_get_path.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp]
     L.pp_planner_get_expanded.argtypes = [vp, C.c_int32, vp]
+    L.pp_planner_get_obstacle_field.argtypes = [vp, C.c_int32, vp]
     L.pp_pipeline_create.argtypes = [vp, C.POINTER(HybridParams), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
     L.pp_pipeline_destroy.argtypes = [vp]
     L.pp_pipeline_submit_dev.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp]

@@ -57,6 +57,47 @@ int pph::refresh_occupancy_views(pp_map* map, hipStream_t s)
 	PP_HIP_TRY(map->occBits.ensure((size_t)wpr * nWordRows * 8));
 	PP_HIP_TRY(pph::launch_occ_to_u8(s, map->occ32, map->occ8, (int64_t)n));
 	PP_HIP_TRY(pph::launch_occ_bits(s, map->occ8, map->desc.rows, map->desc.cols, map->occBits));
+	map->occVersion++;
+	return PP_OK;
+}
+
+int pph::clearance_check_radius(float radius)
+{
+	if (!std::isfinite(radius) || radius < 0.0f) {
+		set_error("the heuristic clearance is a finite radius >= 0 (0 switches it off)");
+		return PP_ERR_INVALID;
+	}
+	return PP_OK;
+}
+
+int pph::clearance_prepare(pp_map* map, ClearanceViews& cv, bool* rebuilt)
+{
+	if (rebuilt)
+		*rebuilt = false;
+	if (cv.radius == 0.0f)
+		return PP_OK;
+	if (!map->dist) {
+		set_error("a heuristic clearance needs the map's distance grid (pp_map_upload_dist2, pp_map_upload_distance or pp_map_update_gvd)");
+		return PP_ERR_INVALID;
+	}
+	if (!map->occ8) {
+		set_error("occupancy grid not uploaded (pp_map_upload_occupancy)");
+		return PP_ERR_INVALID;
+	}
+	if (!cv.stale(map))
+		return PP_OK;
+	PP_HIP_TRY(hipSetDevice(map->ctx->device));
+	int wpr = 0, nWordRows = 0;
+	pph::occ_bits_dims(map->desc.rows, map->desc.cols, wpr, nWordRows);
+	PP_HIP_TRY(cv.blocked8.ensure(map->cells()));
+	PP_HIP_TRY(cv.bits.ensure((size_t)wpr * nWordRows * 8));
+	PP_HIP_TRY(pph::launch_clearance_views(map->ctx->stream, map->dist, map->occ8, map->desc.rows, map->desc.cols, cv.radius, cv.blocked8, cv.bits));
+	cv.builtRadius = cv.radius;
+	cv.distVersion = map->distVersion;
+	cv.occVersion = map->occVersion;
+	cv.built = true;
+	if (rebuilt)
+		*rebuilt = true;
 	return PP_OK;
 }
 
@@ -660,7 +701,8 @@ static int goal_cells(pp_map* map, int32_t n_goals, const double* goal_xy_host, 
 	return PP_OK;
 }
 
-int pp_obstacle_heuristic_dev(pp_map* map, int32_t n_goals, const double* goal_xy_host, float* cost_dev)
+/// the body of pp_obstacle_heuristic_dev and pp_obstacle_heuristic_clearance_dev: cv == nullptr (or radius 0) is the map's own occupancy
+static int obstacle_heuristic_dev(pp_map* map, pph::ClearanceViews* cv, int32_t n_goals, const double* goal_xy_host, float* cost_dev)
 {
 	if (check_map(map, false) || !map->occ8) {
 		set_error("occupancy grid not uploaded (pp_map_upload_occupancy)");
@@ -674,6 +716,10 @@ int pp_obstacle_heuristic_dev(pp_map* map, int32_t n_goals, const double* goal_x
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
 	hipStream_t s = map->ctx->stream;
+	const bool inflated = cv && cv->radius != 0.0f;
+	if (inflated)
+		if (int rc = pph::clearance_prepare(map, *cv, nullptr))
+			return rc;
 	std::vector<int32_t> cells;
 	goal_cells(map, n_goals, goal_xy_host, cells);
 	const int resident = wavefront_resident_blocks();
@@ -701,9 +747,12 @@ int pp_obstacle_heuristic_dev(pp_map* map, int32_t n_goals, const double* goal_x
 	if (tiles) {
 		L.pub.tilesCtl = dtiles.as<int>();
 		L.pub.tilesFallback = dtiles.as<int32_t>() + 16;
-		L.pub.occBits = map->occBits;
+		L.pub.occBits = inflated ? cv->bits.get() : map->occBits.get();
 	}
-	PP_HIP_TRY(launch_wavefront(s, map->view(), L));
+	ppd::MapView m = map->view();
+	if (inflated)
+		m.occ8 = cv->blocked8; // (what the ordered kernel reads)
+	PP_HIP_TRY(launch_wavefront(s, m, L));
 	int32_t err = 0;
 	PP_HIP_TRY(hipMemcpyAsync(&err, derr.get(), 4, hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
@@ -711,6 +760,48 @@ int pp_obstacle_heuristic_dev(pp_map* map, int32_t n_goals, const double* goal_x
 		set_error("obstacle-heuristic open list exceeded its workspace");
 		return PP_ERR_CAPACITY;
 	}
+	return PP_OK;
+}
+
+int pp_obstacle_heuristic_dev(pp_map* map, int32_t n_goals, const double* goal_xy_host, float* cost_dev)
+{
+	return obstacle_heuristic_dev(map, nullptr, n_goals, goal_xy_host, cost_dev);
+}
+
+int pp_obstacle_heuristic_clearance_dev(pp_map* map, float radius, int32_t n_goals, const double* goal_xy_host, float* cost_dev)
+{
+	if (int rc = pph::clearance_check_radius(radius))
+		return rc;
+	if (check_map(map, radius != 0.0f)) // (a clearance needs the distance grid; radius 0 is pp_obstacle_heuristic_dev)
+		return PP_ERR_INVALID;
+	pph::ClearanceViews cv; // this call's own: released behind the synchronisation that ends the launch
+	cv.radius = radius;
+	return obstacle_heuristic_dev(map, &cv, n_goals, goal_xy_host, cost_dev);
+}
+
+int pp_heuristic_clearance_build_ms(pp_map* map, float radius, int32_t reps, float* ms_out)
+{
+	if (int rc = pph::clearance_check_radius(radius))
+		return rc;
+	if (int rc = check_map(map, true))
+		return rc;
+	if (radius == 0.0f || reps < 1 || !ms_out) {
+		set_error("invalid arguments (a radius > 0 and at least one repetition)");
+		return PP_ERR_INVALID;
+	}
+	pph::ClearanceViews cv; // this call's own
+	cv.radius = radius;
+	if (int rc = pph::clearance_prepare(map, cv, nullptr)) // allocation and a first, untimed build
+		return rc;
+	hipStream_t s = map->ctx->stream;
+	PP_HIP_TRY(hipEventRecord(map->ctx->ev0, s));
+	for (int i = 0; i < reps; i++)
+		PP_HIP_TRY(pph::launch_clearance_views(s, map->dist, map->occ8, map->desc.rows, map->desc.cols, radius, cv.blocked8, cv.bits));
+	PP_HIP_TRY(hipEventRecord(map->ctx->ev1, s));
+	PP_HIP_TRY(hipStreamSynchronize(s));
+	float ms = 0.0f;
+	PP_HIP_TRY(hipEventElapsedTime(&ms, map->ctx->ev0, map->ctx->ev1));
+	*ms_out = ms / (float)reps;
 	return PP_OK;
 }
 
@@ -822,6 +913,28 @@ int pp_obstacle_heuristic(pp_map* map, int32_t n_goals, const double* goal_xy_ho
 	const size_t bytes = (size_t)n_goals * map->cells() * sizeof(float);
 	PP_HIP_TRY(dcost.alloc(bytes));
 	if (int rc = pp_obstacle_heuristic_dev(map, n_goals, goal_xy_host, dcost.as<float>()))
+		return rc;
+	PP_HIP_TRY(hipMemcpy(cost_host, dcost.get(), bytes, hipMemcpyDeviceToHost));
+	return PP_OK;
+}
+
+int pp_obstacle_heuristic_clearance(pp_map* map, float radius, int32_t n_goals, const double* goal_xy_host, float* cost_host)
+{
+	if (int rc = pph::clearance_check_radius(radius))
+		return rc;
+	if (check_map(map, radius != 0.0f))
+		return PP_ERR_INVALID;
+	if (n_goals < 0 || (n_goals > 0 && (!goal_xy_host || !cost_host))) {
+		set_error("invalid arguments");
+		return PP_ERR_INVALID;
+	}
+	if (n_goals == 0)
+		return PP_OK;
+	PP_HIP_TRY(hipSetDevice(map->ctx->device));
+	DeviceMem dcost;
+	const size_t bytes = (size_t)n_goals * map->cells() * sizeof(float);
+	PP_HIP_TRY(dcost.alloc(bytes));
+	if (int rc = pp_obstacle_heuristic_clearance_dev(map, radius, n_goals, goal_xy_host, dcost.as<float>()))
 		return rc;
 	PP_HIP_TRY(hipMemcpy(cost_host, dcost.get(), bytes, hipMemcpyDeviceToHost));
 	return PP_OK;

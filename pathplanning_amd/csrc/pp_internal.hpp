@@ -180,6 +180,9 @@ struct WavefrontPublish {
 /// occupancy bits of the tile form (WavefrontPublish::occBits): words per row and rows of the padded word grid
 void occ_bits_dims(int rows, int cols, int& wpr, int& nWordRows);
 hipError_t launch_occ_bits(hipStream_t s, const uint8_t* occ8, int rows, int cols, uint64_t* bits);
+/// Both occupancy views of a heuristic clearance (include/pp_hip.h, "heuristic clearance") in one pass over dist + occ8: blocked8[cell] =
+/// occ8[cell] != 0 || !(dist[cell] >= radius), and the same as padded bit rows in the layout of launch_occ_bits
+hipError_t launch_clearance_views(hipStream_t s, const float* dist, const uint8_t* occ8, int rows, int cols, float radius, uint8_t* blocked8, uint64_t* bits);
 bool wavefront_tiles_supported(int rows, int cols);
 int wavefront_tiles_resident_blocks(int rows, int cols);
 /// words of global memory per wave of a launch for the tile queue (0: the map is small enough for the queue to stay in LDS)
@@ -250,6 +253,7 @@ struct pp_map {
 	pph::Dev<uint8_t> occ8;
 	pph::Dev<uint32_t> validBits; // one bit per cell: dist >= minSafeRadius
 	uint64_t distVersion = 0;      // counts the writes of `dist` (pph::dist_changed): a footprint rebuilds its bitmaps when it lags behind
+	uint64_t occVersion = 0;       // counts the writes of occ8 / occBits (pph::refresh_occupancy_views): with distVersion the stamp of a ClearanceViews
 	pph::Dev<uint64_t> occBits;    // occupancy as padded bit rows (WavefrontPublish::occBits), rebuilt whenever occ8 is
 	// map authoring / field construction on the device (pp_gvd.hip)
 	pph::Dev<int32_t> occ32;       // occupancy ids as the reference holds them (-1 free)
@@ -283,6 +287,24 @@ struct pp_footprint {
 	bool bitsBuilt = false;
 };
 namespace pph {
+/// The occupancy views of a heuristic clearance (include/pp_hip.h, "heuristic clearance"): what the wavefront kernels read in place of
+/// pp_map::occ8 / pp_map::occBits when the radius is > 0.  Owned by whoever launches the fields with it (a planner, a pipeline's planner, one
+/// call of pp_obstacle_heuristic_clearance), so two owners with different radii on one map never share a buffer.  Built lazily on the map's
+/// stream and stamped with the map's distVersion and occVersion: a writer of either grid makes them stale (the model: footprint_prepare).
+struct ClearanceViews {
+	float radius = 0.0f; // 0: off, the launch takes the map's own views
+	Dev<uint8_t> blocked8;
+	Dev<uint64_t> bits;
+	float builtRadius = 0.0f;
+	uint64_t distVersion = 0, occVersion = 0;
+	bool built = false;
+	bool stale(const pp_map* map) const { return !built || builtRadius != radius || distVersion != map->distVersion || occVersion != map->occVersion; }
+};
+/// PP_ERR_INVALID with a message unless radius is finite and >= 0
+int clearance_check_radius(float radius);
+/// radius 0: nothing.  Otherwise checks that the map has a distance and an occupancy grid (PP_ERR_INVALID with a message) and brings the views up
+/// to date on the map's stream; *rebuilt (optional) tells whether a kernel was enqueued.
+int clearance_prepare(pp_map* map, ClearanceViews& cv, bool* rebuilt);
 /// Checks that `fp` belongs to `map` and that the map has a distance grid (PP_ERR_INVALID with a message otherwise);
 /// needBits: also brings the footprint's bitmaps up to date with the map's distance grid, on the map's stream.
 int footprint_prepare(pp_map* map, pp_footprint* fp, bool needBits);

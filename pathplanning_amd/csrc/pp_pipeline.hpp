@@ -651,6 +651,38 @@ int pp_pipeline_set_footprint(pp_pipeline* P, pp_footprint* fp)
 	return PP_OK;
 }
 
+int pp_pipeline_set_heuristic_clearance(pp_pipeline* P, float radius)
+{
+	if (!P) {
+		set_error("null pipeline");
+		return PP_ERR_INVALID;
+	}
+	if (P->dead) {
+		set_error("the pipeline failed in an earlier submission and must be destroyed");
+		return PP_ERR_HIP;
+	}
+	if (int rc = pph::clearance_check_radius(radius))
+		return rc;
+	if (P->nSubmitted != P->doneHead) {
+		// the fields already built (and those being built) belong to the old rule: a query's result would depend on when its field was launched
+		// (the rule of pp_pipeline_set_footprint)
+		set_error("the pipeline has " + std::to_string(P->nSubmitted - P->doneHead) + " queries in flight: poll them all before changing the heuristic clearance");
+		return PP_ERR_INVALID;
+	}
+	P->pl->clearance.radius = radius; // (the views are built at the next submission: the map-view guard of pp_pipeline_submit_dev)
+	return PP_OK;
+}
+
+int pp_pipeline_heuristic_clearance(pp_pipeline* P, float* radius)
+{
+	if (!P || !radius) {
+		set_error("null argument");
+		return PP_ERR_INVALID;
+	}
+	*radius = P->pl->clearance.radius;
+	return PP_OK;
+}
+
 int pp_pipeline_submit_dev(pp_pipeline* P, int32_t n_queries, const double* starts_dev, const double* goals_dev, const uint64_t* seeds_dev, uint64_t* tickets_out, int32_t* n_accepted)
 {
 	if (!P || n_queries < 0 || !n_accepted || (n_queries > 0 && (!starts_dev || !goals_dev || !seeds_dev))) {
@@ -693,6 +725,25 @@ int pp_pipeline_submit_dev(pp_pipeline* P, int32_t n_queries, const double* star
 		}
 		P->lastView = now;
 		P->viewValid = true;
+	}
+	// ---- the same guard for the occupancy views of a heuristic clearance: stale when either of the map's grids was written since they were built
+	// (pp_map::distVersion, pp_map::occVersion) or the radius changed.  Fields in flight were built from the old views, so queries in flight refuse
+	// the submission; otherwise the launches that read the old views are waited for, the views are rebuilt on the map's stream, and that stream is
+	// waited for in turn: the next tile launch (and the ordered kernel's behind it) is ordered behind the rebuild.
+	if (pl->clearance.radius != 0.0f && pl->clearance.stale(pl->map)) {
+		if (P->nSubmitted != P->doneHead) {
+			set_error("the map's grids changed while " + std::to_string(P->nSubmitted - P->doneHead) +
+					  " queries of this pipeline are in flight (the heuristic clearance's occupancy views have to be rebuilt): poll them first");
+			return PP_ERR_INVALID;
+		}
+		for (hipStream_t ws : P->wfStream)
+			if (ws)
+				PP_HIP_TRY(hipStreamSynchronize(ws));
+		if (P->fbStream)
+			PP_HIP_TRY(hipStreamSynchronize(P->fbStream));
+		if (int rc = pph::clearance_prepare(pl->map, pl->clearance, nullptr))
+			return rc;
+		PP_HIP_TRY(hipStreamSynchronize(pl->map->ctx->stream));
 	}
 	// ---- slots and tickets
 	if (P->slotListPos + (size_t)k > P->slotListCap)
@@ -766,6 +817,10 @@ int pp_pipeline_submit_dev(pp_pipeline* P, int32_t n_queries, const double* star
 	// ---- ObstaclesHeuristic::Update for every goal (hybrid_a_star.cpp:249); each finished slot is appended to the ready ring
 	PP_HIP_TRY(hipStreamWaitEvent(w, P->evIngest, 0));
 	pl->args.m = pl->map->view();
+	const bool inflated = pl->clearance.radius != 0.0f;
+	ppd::MapView wm = pl->args.m;
+	if (inflated)
+		wm.occ8 = pl->clearance.blocked8; // (what the ordered kernel reads; the search grid never reads occupancy)
 	pph::WavefrontLaunch L;
 	L.nGoals = k;
 	L.goalPoses = pl->dGoals; // (indexed by the slot, as the fields are)
@@ -784,7 +839,7 @@ int pp_pipeline_submit_dev(pp_pipeline* P, int32_t n_queries, const double* star
 	pub.goalCounter = wctl + 1; // 0 at creation; the last workgroup of every launch sets it back
 	pub.exitCounter = wctl + 2;
 	pub.claimed = P->claimed;
-	pub.occBits = pl->map->occBits;
+	pub.occBits = inflated ? pl->clearance.bits.get() : pl->map->occBits.get();
 	pub.tilesCtl = P->fbCtl[fbSet];
 	pub.tilesFallback = P->fbList[fbSet];
 	pub.tilesQueue = P->tilesQueue[wfIdx];
@@ -797,7 +852,7 @@ int pp_pipeline_submit_dev(pp_pipeline* P, int32_t n_queries, const double* star
 		pub.urgentMask = P->readyMask;
 	}
 	const pp_pipeline::Timed tm = timed_take(P, w, 0, k);
-	PP_HIP_TRY(pph::launch_wavefront(w, pl->args.m, L));
+	PP_HIP_TRY(pph::launch_wavefront(w, wm, L));
 	timed_done(P, w, tm);
 	PP_HIP_TRY(hipEventRecord(P->fbDone[fbSet], P->fbStream));
 	P->fbUsed[fbSet] = true;

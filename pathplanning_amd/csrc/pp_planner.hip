@@ -343,6 +343,7 @@ struct pp_planner {
 	int lastBatch = 0;
 	pp_pipeline* owner = nullptr; // not owned: the pipeline this planner is the buffer set of (set with pipelineOwned)
 	pp_footprint* footprint = nullptr; // pp_planner_set_footprint (a reference is held): the search asks the footprint, not the point validator
+	pph::ClearanceViews clearance; // pp_planner_set_heuristic_clearance / pp_pipeline_set_heuristic_clearance: the occupancy the field launches read (radius 0: the map's own)
 	bool pipelineOwned = false; // the buffer set of a pp_pipeline (pp_pipeline_planner()): its rows and field slots belong to the pipeline's kernels
 	std::vector<DevResult> hostResults;
 	// post-processing (pp_postprocess.hpp), allocated at the first pp_planner_postprocess (the kernel takes them as a PostBuffers)
@@ -798,6 +799,36 @@ int pp_planner_set_footprint(pp_planner* planner, pp_footprint* fp)
 	return PP_OK;
 }
 
+int pp_planner_set_heuristic_clearance(pp_planner* planner, float radius)
+{
+	if (!planner) {
+		set_error("null planner");
+		return PP_ERR_INVALID;
+	}
+	if (int rc = pph::clearance_check_radius(radius))
+		return rc;
+	if (planner->pipelineOwned) {
+		set_error("this planner is a pipeline's buffer set: the pipeline's field launches get their clearance from pp_pipeline_set_heuristic_clearance, not from its planner");
+		return PP_ERR_INVALID;
+	}
+	if (radius == planner->clearance.radius)
+		return PP_OK;
+	PP_HIP_TRY(hipSetDevice(planner->map->ctx->device));
+	PP_HIP_TRY(hipStreamSynchronize(planner->map->ctx->stream)); // a batch in flight keeps the views it was launched with
+	planner->clearance.radius = radius; // (the views are built by the next batch, on the map's stream in front of its field launch)
+	return PP_OK;
+}
+
+int pp_planner_heuristic_clearance(pp_planner* planner, float* radius)
+{
+	if (!planner || !radius) {
+		set_error("null argument");
+		return PP_ERR_INVALID;
+	}
+	*radius = planner->clearance.radius;
+	return PP_OK;
+}
+
 int pp_planner_set_primitives(pp_planner* planner, int32_t n_steering_angles, const double* steering_angles)
 {
 	if (!planner || !steering_angles || n_steering_angles < 1) {
@@ -908,6 +939,14 @@ int pp_planner_search_batch_dev(pp_planner* planner, int32_t n_queries, const do
 	constexpr int dbgSkip = 0;
 #endif
 	if (dbgSkip != 1) {
+		// a heuristic clearance: the field kernels read the planner's views of the occupancy (brought up to date here, on this stream) instead of the map's
+		const bool inflated = planner->clearance.radius != 0.0f;
+		if (inflated)
+			if (int rc = pph::clearance_prepare(planner->map, planner->clearance, nullptr))
+				return rc;
+		MapView wm = m;
+		if (inflated)
+			wm.occ8 = planner->clearance.blocked8; // (what the ordered kernel reads; the search kernels never read occupancy)
 		pph::WavefrontLaunch L;
 		L.nGoals = n_queries;
 		L.goalPoses = goals_dev;
@@ -926,8 +965,8 @@ int pp_planner_search_batch_dev(pp_planner* planner, int32_t n_queries, const do
 		L.orderKeys = planner->orderKeys;
 		L.pub.tilesCtl = planner->tilesCtl;
 		L.pub.tilesFallback = planner->tilesFallback;
-		L.pub.occBits = planner->map->occBits;
-		PP_HIP_TRY(pph::launch_wavefront(s, m, L));
+		L.pub.occBits = inflated ? planner->clearance.bits.get() : planner->map->occBits.get();
+		PP_HIP_TRY(pph::launch_wavefront(s, wm, L));
 	}
 	PP_HIP_TRY(hipEventRecord(planner->e1, s));
 	const Queries batch { n_queries, starts_dev, goals_dev, seeds_dev };
@@ -1376,6 +1415,24 @@ int pp_planner_get_expanded(pp_planner* planner, int32_t q, int32_t* cells_host)
 		cells_host[3 * i + 1] = iy;
 		cells_host[3 * i + 2] = it;
 	}
+	return PP_OK;
+}
+
+int pp_planner_get_obstacle_field(pp_planner* planner, int32_t q, float* cost_host)
+{
+	if (!planner || q < 0 || q >= planner->maxBatch || !cost_host) {
+		set_error("invalid arguments (q is a query of the last batch, or a field slot of a pipeline)");
+		return PP_ERR_INVALID;
+	}
+	PP_HIP_TRY(hipSetDevice(planner->map->ctx->device));
+	if (!planner->pipelineOwned)
+		PP_HIP_TRY(hipStreamSynchronize(planner->map->ctx->stream));
+	const int rows = planner->map->desc.rows, cols = planner->map->desc.cols;
+	std::vector<float> tiled((size_t)planner->args.fieldElems);
+	PP_HIP_TRY(hipMemcpy(tiled.data(), planner->costFields + (size_t)q * (size_t)planner->args.fieldElems, tiled.size() * sizeof(float), hipMemcpyDeviceToHost));
+	for (int r = 0; r < rows; r++)
+		for (int c = 0; c < cols; c++)
+			cost_host[(size_t)r * cols + c] = tiled[field_tiled_index(cols, r, c)];
 	return PP_OK;
 }
 

@@ -129,6 +129,29 @@ __global__ void __launch_bounds__(256) k_occ_bits(const uint8_t* __restrict__ oc
 		bits[w] = b;
 }
 
+/// The two occupancy views of a heuristic clearance in one pass: a cell is blocked iff occ8 != 0 || !(dist >= radius) (the float comparison
+/// of k_valid_bits).  One wave per word of the padded bit grid of k_occ_bits, i.e. 64 consecutive columns of a row: every lane inside the map
+/// stores its byte, lane 0 the ballot.  Padding words, rows below the map and the columns beyond `cols` of a row's last word are blocked.
+__global__ void __launch_bounds__(256) k_clearance_views(const float* __restrict__ dist, const uint8_t* __restrict__ occ8, int rows, int cols, int wpr, int nWordRows,
+	float radius, uint8_t* __restrict__ blocked8, uint64_t* __restrict__ bits)
+{
+	const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); // one wave per word
+	const int lane = threadIdx.x & 63;
+	if (w >= (int64_t)nWordRows * wpr)
+		return;
+	const int pr = (int)(w / wpr), pw = (int)(w - (int64_t)pr * wpr);
+	const int r = pr - 1, c = (pw - 1) * 64 + lane;
+	bool o = true;
+	if (r >= 0 && r < rows && pw >= 1 && c < cols) {
+		const int64_t cell = (int64_t)r * cols + c;
+		o = occ8[cell] != 0 || !(dist[cell] >= radius);
+		blocked8[cell] = o ? 1 : 0;
+	}
+	const uint64_t b = __ballot(o);
+	if (lane == 0)
+		bits[w] = b;
+}
+
 struct TilesArgs {
 	MapView m;
 	int nGoals;
@@ -823,6 +846,15 @@ hipError_t launch_occ_bits(hipStream_t s, const uint8_t* occ8, int rows, int col
 	occ_bits_dims(rows, cols, wpr, nWordRows);
 	const int64_t words = (int64_t)wpr * nWordRows;
 	hipLaunchKernelGGL(k_occ_bits, dim3((unsigned)((words + 3) / 4)), dim3(256), 0, s, occ8, rows, cols, wpr, nWordRows, bits);
+	return hipGetLastError();
+}
+
+hipError_t launch_clearance_views(hipStream_t s, const float* dist, const uint8_t* occ8, int rows, int cols, float radius, uint8_t* blocked8, uint64_t* bits)
+{
+	int wpr, nWordRows;
+	occ_bits_dims(rows, cols, wpr, nWordRows);
+	const int64_t words = (int64_t)wpr * nWordRows;
+	hipLaunchKernelGGL(k_clearance_views, dim3((unsigned)((words + 3) / 4)), dim3(256), 0, s, dist, occ8, rows, cols, wpr, nWordRows, radius, blocked8, bits);
 	return hipGetLastError();
 }
 

@@ -742,6 +742,8 @@ public:
 		m_plannerFootprint = nullptr;
 		if (!SyncFootprint("Initialize")) // the validator's footprint goes to the planner (a planner sized for the rows kernel refuses it)
 			return isInitialized = false;
+		if (!SyncHeuristicClearance("Initialize"))
+			return isInitialized = false;
 		return isInitialized = true;
 	}
 	Status SearchPath() override
@@ -751,7 +753,7 @@ public:
 		if (m_validator->GetOccupancyMap()->FieldsOutdated())
 			m_validator->GetOccupancyMap()->BuildFields(20.0f, 30.0f); // m_gvd->Update(), hybrid_a_star.cpp:250 (GVD::alpha / dMax, gvd.h:181)
 		m_validator->Device(); // pushes map edits / tunables
-		if (!SyncFootprint("SearchPath"))
+		if (!SyncFootprint("SearchPath") || !SyncHeuristicClearance("SearchPath"))
 			return m_stats.graphSearchStatus = Status::Failure;
 		pp_query_result r {};
 		uint64_t seed = m_seed;
@@ -909,6 +911,17 @@ public:
 	Ref<StateValidatorOccupancyMap>& GetStateValidator() { return m_validator; }
 	/// the reference's process-global RNG becomes one stream per query
 	void SetSeed(uint64_t seed) { m_seed = seed; }
+	/// Extension (include/pp_hip.h, "heuristic clearance"): for the obstacle heuristic only, a cell is blocked iff it is occupied or
+	/// !(dist >= radius); validity, costs and the other heuristics are untouched.  0 (the default) is the reference's rule; a radius up to the
+	/// validator's minSafeRadius keeps the heuristic a lower bound, a larger one is the caller's choice.  Applies from the next search on.
+	/// A negative or non-finite radius throws std::invalid_argument and leaves the setting as it was.
+	void SetHeuristicClearance(float radius)
+	{
+		if (!std::isfinite(radius) || radius < 0.0f)
+			throw std::invalid_argument("the heuristic clearance is a finite radius >= 0");
+		m_heuristicClearance = radius;
+	}
+	float GetHeuristicClearance() const { return m_heuristicClearance; }
 	/// batch of independent queries (n <= maxBatch)
 	std::vector<pp_query_result> SearchBatch(const std::vector<Pose2d>& starts, const std::vector<Pose2d>& goals, const std::vector<uint64_t>& seeds)
 	{
@@ -917,7 +930,7 @@ public:
 		if (m_validator->GetOccupancyMap()->FieldsOutdated())
 			m_validator->GetOccupancyMap()->BuildFields(20.0f, 30.0f);
 		m_validator->Device();
-		if (!SyncFootprint("SearchBatch"))
+		if (!SyncFootprint("SearchBatch") || !SyncHeuristicClearance("SearchBatch"))
 			throw std::runtime_error(std::string("libpphip: ") + pp_last_error());
 		std::vector<pp_query_result> res(starts.size());
 		if (!starts.empty())
@@ -947,7 +960,17 @@ private:
 		m_plannerFootprint = want; // (the planner holds a reference: the address stays taken while it is set)
 		return true;
 	}
+	/// hands the heuristic clearance as it is now to the planner
+	bool SyncHeuristicClearance(const char* where)
+	{
+		if (pp_planner_set_heuristic_clearance(m_planner, m_heuristicClearance)) {
+			std::fprintf(stderr, "[pathplanning_amd] HybridAStar::%s: %s\n", where, pp_last_error());
+			return false;
+		}
+		return true;
+	}
 	pp_footprint* m_plannerFootprint = nullptr;
+	float m_heuristicClearance = 0.0f;
 	SearchParameters m_param;
 	int m_maxBatch, m_maxNodes;
 	bool isInitialized = false;
@@ -1019,6 +1042,7 @@ public:
 			return false;
 		try {
 			SyncFootprint(); // the validator's footprint goes to the pipeline's search grid
+			ppCheck(pp_pipeline_set_heuristic_clearance(m_pipe, m_heuristicClearance));
 		} catch (const std::exception& e) {
 			std::fprintf(stderr, "[pathplanning_amd] HybridAStarPipeline::Initialize: %s\n", e.what());
 			return false;
@@ -1034,6 +1058,7 @@ public:
 			return 0;
 		m_validator->Device(); // pushes map edits / tunables
 		SyncFootprint();       // a footprint set, changed or cleared since the last submission; throws while queries are in flight
+		SyncHeuristicClearance(); // the same rule
 		std::vector<uint64_t> t((size_t)n);
 		int32_t taken = 0;
 		ppCheck(pp_pipeline_submit(m_pipe, n, &starts[0].position.v[0], &goals[0].position.v[0], seeds.data(), t.data(), &taken));
@@ -1063,6 +1088,15 @@ public:
 		}
 		return n;
 	}
+	/// HybridAStar::SetHeuristicClearance for the pipeline's field launches: applies from the next Submit on, which throws with the library's
+	/// message while queries are in flight (fields already built belong to the old rule): poll everything first
+	void SetHeuristicClearance(float radius)
+	{
+		if (!std::isfinite(radius) || radius < 0.0f)
+			throw std::invalid_argument("the heuristic clearance is a finite radius >= 0");
+		m_heuristicClearance = radius;
+	}
+	float GetHeuristicClearance() const { return m_heuristicClearance; }
 	int InFlight() const { return m_pipe ? pp_pipeline_in_flight(m_pipe) : 0; }
 	int FreeSlots() const { return m_pipe ? pp_pipeline_free_slots(m_pipe) : 0; }
 
@@ -1077,6 +1111,14 @@ private:
 		ppCheck(pp_pipeline_set_footprint(m_pipe, want));
 		m_pipeFootprint = want; // (the pipeline holds a reference: the address stays taken while it is set)
 	}
+	void SyncHeuristicClearance()
+	{
+		float now = 0.0f;
+		ppCheck(pp_pipeline_heuristic_clearance(m_pipe, &now));
+		if (now != m_heuristicClearance)
+			ppCheck(pp_pipeline_set_heuristic_clearance(m_pipe, m_heuristicClearance));
+	}
+	float m_heuristicClearance = 0.0f;
 	HybridAStar::SearchParameters m_param;
 	int m_capacity, m_maxNodes, m_searchRows;
 	Ref<StateValidatorOccupancyMap> m_validator;

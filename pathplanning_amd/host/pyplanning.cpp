@@ -360,6 +360,9 @@ PYBIND11_MODULE(pyplanning, m)
 		.def_property("smoother_parameters", &HybridAStar::GetSmootherParameters, &HybridAStar::SetSmootherParameters)
 		.def("get_search_parameters", &HybridAStar::GetSearchParameters)
 		.def("set_seed", &HybridAStar::SetSeed)
+		// heuristic clearance (include/pp_hip.h): the obstacle heuristic also blocks cells with !(dist >= radius); 0 = the reference's rule
+		.def("set_heuristic_clearance", &HybridAStar::SetHeuristicClearance, py::arg("radius"))
+		.def_property_readonly("heuristic_clearance", &HybridAStar::GetHeuristicClearance)
 		.def("search_batch",
 			[](HybridAStar& h, py::array_t<double, py::array::c_style | py::array::forcecast> starts, py::array_t<double, py::array::c_style | py::array::forcecast> goals,
 				py::array_t<uint64_t, py::array::c_style | py::array::forcecast> seeds) {

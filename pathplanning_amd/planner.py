@@ -472,15 +472,29 @@ class ObstaclesHeuristic:
         self.map = map_set
         self.lib = map_set.lib
 
-    def update(self, goals_xy):
+    def update(self, goals_xy, clearance=0.0):
+        """clearance > 0 (include/pp_hip.h, "heuristic clearance"): a cell is also blocked where !(dist >= clearance); 0 is the
+        reference's rule."""
         g = _f64(goals_xy, 2)
         out = np.empty((len(g), self.map.rows, self.map.cols), dtype=np.float32)
-        check(self.lib.pp_obstacle_heuristic(self.map.h, len(g), ptr(g), ptr(out)))
+        if clearance == 0.0:
+            check(self.lib.pp_obstacle_heuristic(self.map.h, len(g), ptr(g), ptr(out)))
+        else:
+            check(self.lib.pp_obstacle_heuristic_clearance(self.map.h, float(clearance), len(g), ptr(g), ptr(out)))
         return out
 
-    def update_dev(self, goals_xy, cost_tensor):
+    def update_dev(self, goals_xy, cost_tensor, clearance=0.0):
         g = _f64(goals_xy, 2)
-        check(self.lib.pp_obstacle_heuristic_dev(self.map.h, len(g), ptr(g), _dev_ptr(cost_tensor)))
+        if clearance == 0.0:
+            check(self.lib.pp_obstacle_heuristic_dev(self.map.h, len(g), ptr(g), _dev_ptr(cost_tensor)))
+        else:
+            check(self.lib.pp_obstacle_heuristic_clearance_dev(self.map.h, float(clearance), len(g), ptr(g), _dev_ptr(cost_tensor)))
+
+    def clearance_views_build_ms(self, clearance, reps=20):
+        """pp_heuristic_clearance_build_ms: mean milliseconds of one build of the clearance's two occupancy views on this map (HIP events)"""
+        ms = C.c_float(0.0)
+        check(self.lib.pp_heuristic_clearance_build_ms(self.map.h, float(clearance), int(reps), C.byref(ms)))
+        return float(ms.value)
 
     TILE_STATS = ("goals", "tile_visits", "rounds", "candidate_passes", "cells", "handed_over", "wave_cycles", "tiles_per_goal",
                   "cycles_load", "cycles_masks", "cycles_passes", "cycles_requeue", "cycles_store")
@@ -554,6 +568,18 @@ class HybridAStarBatch:
         one-query-per-wave kernel only (max_batch <= 64, or PP_SEARCH_ROWS=0 in the environment): others raise PPError."""
         check(self.lib.pp_planner_set_footprint(self.h, footprint.h if footprint is not None else None))
         self.footprint = footprint  # (keeps it alive on this side too)
+
+    def set_heuristic_clearance(self, radius):
+        """Heuristic clearance (include/pp_hip.h): for the obstacle-heuristic fields of every later batch a cell is blocked iff it is
+        occupied or !(dist >= radius); the search itself is untouched.  0 (the default) is the reference's rule.  radius <= the
+        validator's min_safe_radius keeps the heuristic a lower bound; a larger one is the caller's choice."""
+        check(self.lib.pp_planner_set_heuristic_clearance(self.h, float(radius)))
+
+    @property
+    def heuristic_clearance(self):
+        r = C.c_float(0.0)
+        check(self.lib.pp_planner_heuristic_clearance(self.h, C.byref(r)))
+        return float(r.value)
 
     def initialize(self, nonholo_table=None):
         """HybridAStar::Initialize (hybrid_a_star.cpp:206-235): builds the non-holonomic table on the
@@ -669,6 +695,12 @@ class HybridAStarBatch:
             check(self.lib.pp_planner_get_expanded(self.h, q, ptr(cells)))
         return cells
 
+    def get_obstacle_field_of(self, q):
+        """the obstacle-heuristic field query q of the last batch was searched with: [rows, cols] float32, +inf where unexplored"""
+        out = np.empty((self.map.rows, self.map.cols), dtype=np.float32)
+        check(self.lib.pp_planner_get_obstacle_field(self.h, int(q), ptr(out)))
+        return out
+
     # -- PathPlannerSE2Base-shaped single query ---------------------------
     def set_init_state(self, pose):
         self._init = np.asarray(pose, dtype=np.float64)
@@ -739,6 +771,17 @@ class HybridAStarPipeline:
     def footprint(self):
         """the Footprint last accepted by set_footprint, or None"""
         return self._footprint
+
+    def set_heuristic_clearance(self, radius):
+        """Heuristic clearance of the fields of every goal submitted afterwards (see HybridAStarBatch.set_heuristic_clearance).  Fields
+        already built belong to the old rule, so the call raises PPError ("in flight") unless every submitted query has been polled."""
+        check(self.lib.pp_pipeline_set_heuristic_clearance(self.h, float(radius)))
+
+    @property
+    def heuristic_clearance(self):
+        r = C.c_float(0.0)
+        check(self.lib.pp_pipeline_heuristic_clearance(self.h, C.byref(r)))
+        return float(r.value)
 
     def initialize(self, nonholo_table=None):
         t = None if nonholo_table is None else np.ascontiguousarray(nonholo_table, dtype=np.float64)
@@ -899,6 +942,15 @@ class HybridAStarPipeline:
         if n:
             check(self.lib.pp_planner_get_expanded(self.planner_h, slot, ptr(cells)))
         return cells
+
+    def get_obstacle_field_of(self, ticket):
+        """the obstacle-heuristic field a completed query polled with release=False was searched with: [rows, cols] float32"""
+        slot = self.lib.pp_pipeline_slot_of(self.h, C.c_uint64(int(ticket)))
+        if slot < 0:
+            raise ValueError("ticket is not a completed, held query")
+        out = np.empty((self.map.rows, self.map.cols), dtype=np.float32)
+        check(self.lib.pp_planner_get_obstacle_field(self.planner_h, slot, ptr(out)))
+        return out
 
     def close(self):
         if self.h:
