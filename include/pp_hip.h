@@ -412,7 +412,8 @@ typedef struct pp_smoother_params { /* algo/smoother.h:28-60 */
 } pp_smoother_params;
 typedef struct pp_post_result {
 	int32_t n_points;         /* poses of the sampled path (0: the search failed) */
-	int32_t smoothing_status; /* Smoother::Status: 0 MaxIteration, 1 StepTolerance, 2 PathSize, -1 Failure; -4: more than max_points samples */
+	int32_t smoothing_status; /* Smoother::Status: 0 MaxIteration, 1 StepTolerance, 2 PathSize, -1 Failure; -4: more than max_points samples;
+	                           * -2: a smoothed sample fails the vehicle footprint; GetPath() is the sampled path (pp_pipeline_postprocess only) */
 	int32_t iterations;
 	int32_t reserved;
 	double length;            /* length of the composite path */
@@ -435,7 +436,8 @@ int pp_map_upload_nearest_cells(pp_map* map, const int32_t* nearest_obstacle_hos
  * keep the tree and the log; flagged queries of a throughput planner / pipeline are re-planned there first (identical results). */
 int pp_planner_certify_lattice(pp_planner* planner, int32_t q, int32_t* n_checked, int32_t* n_cell_mismatches, int32_t* n_unverified, double* max_pose_difference);
 
-/* ---- streaming form of HybridAStar::SearchPath's search stage (algo/hybrid_a_star.cpp:237-257) ------------------------------
+/* ---- streaming form of HybridAStar::SearchPath: its search stage (algo/hybrid_a_star.cpp:237-257), and by ticket its post-processing
+ * (pp_pipeline_postprocess, hybrid_a_star.cpp:260-304) ------------------------------
  * One pipeline per GPU: `capacity` queries in flight (a field slot each: the obstacle-heuristic field of its goal, start / goal /
  * seed, path and Reeds-Shepp log), ObstaclesHeuristic::Update by the wavefront kernel, which hands every finished field to ONE
  * persistent search grid of `search_rows` rows (0 = 4096) through a device-side queue; a row takes the next ready query as soon as
@@ -475,6 +477,34 @@ int pp_pipeline_release(pp_pipeline* pipeline, int32_t n, const uint64_t* ticket
  * path's remaining records are fetched from the device).  release != 0: the slots are returned like pp_pipeline_release. */
 int pp_pipeline_get_paths(pp_pipeline* pipeline, int32_t n, const uint64_t* tickets, int32_t max_poses, double* poses_host, int32_t* n_poses_host, int32_t release);
 int pp_pipeline_slot_of(pp_pipeline* pipeline, uint64_t ticket); /* -1 unless completed and held */
+/* HybridAStar::SearchPath's post-processing (hybrid_a_star.cpp:260-304) of n completed, HELD queries, in the order of `tickets`: what
+ * pp_planner_postprocess does for a batch, one workgroup per ticket (k_postprocess_tickets reads the plan of the ticket's field slot and writes at
+ * the ticket's position in the list).  results_host[i] (may be NULL) belongs to tickets[i].
+ *  - Legal with queries in flight: a held slot is not written until it is released.  The launch runs on the pipeline's control stream with
+ *    a copy of the search arguments and the map view of the last submission; only that stream is synchronised, and nothing the search grid
+ *    reads is written.
+ *  - Footprint: with one set (pp_pipeline_set_footprint) a path whose point checks passed (smoothing_status >= 0 so far) is checked once more
+ *    on the device, every sample as the pose (smoothed x, smoothed y, the sample's heading) against the footprint's state predicate; one that
+ *    fails gives smoothing_status -2.  The descent itself is unchanged (it knows the point validator only).
+ *  - PP_ERR_INVALID, nothing launched, the pipeline usable as before, the message naming the first offending ticket: n < 0 or n > capacity;
+ *    max_points outside 8 .. 2048; path_interpolation <= 0; nearest-cell grids missing on the map; a ticket that is unknown, released or still
+ *    in flight; a ticket given twice.  n == 0 is PP_OK.
+ *  - The pipeline owns the buffers: 58 bytes per sample (ratio 8, sampled pose 24, smoothed pose 24, cusp flag 1, optimise flag 1) x the
+ *    largest n x max_points asked so far -- sized by the calls, not by the capacity.  Freeing device memory waits for the whole device, so
+ *    a buffer that has to grow while queries are in flight is kept aside and freed by the first later call that finds none in flight (or with
+ *    the pipeline): a caller that wants no growth beside a running search makes its largest call first.
+ *  - The results stay readable per ticket (pp_pipeline_get_processed_paths) until the ticket is released, by any route, or the next
+ *    pp_pipeline_postprocess call that passes validation (one with n == 0 included).
+ * smoother == NULL: the defaults of pp_planner_postprocess. */
+int pp_pipeline_postprocess(pp_pipeline* pipeline, int32_t n, const uint64_t* tickets, float path_interpolation, const pp_smoother_params* smoother, int32_t max_points,
+	pp_post_result* results_host);
+/* max_points >= 1 is the stride of the caller's arrays (it need not be the max_points of the post-processing call).
+ * sampled / cusp / smoothed: [n][max_points][3] doubles / [n][max_points] bytes / [n][max_points][3] doubles, any may be NULL; n_points_host[i] as
+ * pp_post_result::n_points (it may exceed max_points, then only the first max_points are written; rows beyond it are unspecified).  Only tickets of
+ * the LAST pp_pipeline_postprocess call that are still held: any other is PP_ERR_INVALID.  HybridAStar::GetPath() is the smoothed path when
+ * smoothing_status >= 0, else the sampled one.  release != 0: as pp_pipeline_release. */
+int pp_pipeline_get_processed_paths(pp_pipeline* pipeline, int32_t n, const uint64_t* tickets, int32_t max_points, double* sampled_host, uint8_t* cusp_host,
+	double* smoothed_host, int32_t* n_points_host, int32_t release);
 /* Diagnostics: waves of the search grid that are alive right now (a blocking device-to-host copy; -1 on error). */
 int pp_pipeline_alive_waves(pp_pipeline* pipeline);
 pp_planner* pp_pipeline_planner(pp_pipeline* pipeline);           /* the buffer set: set_nonholo_table, set_primitives, get_path(slot), ... */
@@ -493,7 +523,8 @@ int pp_pipeline_free_slots(pp_pipeline* pipeline);
  *  - A footprint of another map is PP_ERR_INVALID ("another map").
  *  - pp_planner_set_footprint on pp_pipeline_planner() stays refused; the batch planner of the rows kernel takes no footprint either.
  * The search reads the map's float distance grid through the map view, not the footprint's validity bitmaps: a rebuilt distance grid is
- * caught by the view guard of pp_pipeline_submit_dev.  pp_planner_postprocess on a held slot still smooths against the point validator. */
+ * caught by the view guard of pp_pipeline_submit_dev.  pp_planner_postprocess on a held slot still smooths against the point validator;
+ * pp_pipeline_postprocess checks the smoothed samples against the footprint set here (which may be changed while slots are merely held). */
 int pp_pipeline_set_footprint(pp_pipeline* pipeline, pp_footprint* fp);
 /* Heuristic clearance of the pipeline's field launches (see "heuristic clearance" above): for every goal submitted afterwards a cell is
  * blocked iff occupied[cell] || !(dist[cell] >= radius); the search grid is untouched.  radius == 0 (the default) is the reference's rule.

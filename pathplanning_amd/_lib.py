@@ -201,6 +201,8 @@ def load():
     L.pp_pipeline_release.argtypes = [vp, C.c_int32, vp]
     L.pp_pipeline_get_paths.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32]
     L.pp_pipeline_slot_of.argtypes = [vp, C.c_uint64]
+    L.pp_pipeline_postprocess.argtypes = [vp, C.c_int32, vp, C.c_float, vp, C.c_int32, vp]
+    L.pp_pipeline_get_processed_paths.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, C.c_int32]
     L.pp_pipeline_timings.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.pp_pipeline_backlog.argtypes = [vp, vp, vp]
     L.pp_pipeline_planner.argtypes = [vp]

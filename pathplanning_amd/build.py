@@ -83,6 +83,18 @@ def build_pipeline_footprint_test(verbose=True):
     return out
 
 
+def build_pipeline_postprocess_test(verbose=True):
+    """tests/cpp/test_pipeline_postprocess.cpp: GetPath(ticket) of HybridAStarPipeline against HybridAStar::SearchPath + GetPath (run on the GPU box)."""
+    build()
+    out = os.path.join(LIB_DIR, "test_pipeline_postprocess")
+    src = os.path.join(HERE, "..", "tests", "cpp", "test_pipeline_postprocess.cpp")
+    cmd = ["g++", "-O2", "-std=c++17", src, "-o", out, "-L" + LIB_DIR, "-lpphip", "-Wl,-rpath,$ORIGIN"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return out
+
+
 def build_row_test(verbose=True):
     """tests/cpp/test_row_primitives.hip: GPU self-test of the DPP row primitives (run on the GPU box)."""
     out = os.path.join(LIB_DIR, "test_row_primitives")
@@ -102,4 +114,5 @@ if __name__ == "__main__":
     print(build_pyplanning())
     print(build_plugin_test())
     print(build_pipeline_footprint_test())
+    print(build_pipeline_postprocess_test())
     print(build_row_test())

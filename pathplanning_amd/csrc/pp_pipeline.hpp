@@ -207,6 +207,19 @@ struct pp_pipeline {
 	unsigned long long idleTicks = 250000ull; // idle loop passes of ~4 us: about 1 s.  (50 ms until round 4: shorter than the ~100 ms the first fields of a run take, so the
 	                                         // grid's waves left before their first work arrived and came back by the luck of the top-up launches.)  Idle waves leave at once when
 	                                         // the host has polled every result (PipeCtl::quiesce), so the time-out only matters when a producer really cannot run.
+	// pp_pipeline_postprocess (k_postprocess_tickets): outputs at the compact index of a ticket in the last call's list.  The sample buffers hold
+	// postSamples = the largest n x max_points asked so far (58 bytes per sample), never capacity x max_points.
+	pph::Dev<double> postRatios, postResampled, postSmoothed, postEdgeEnd;
+	pph::Dev<uint8_t> postCusp, postOptimise;
+	pph::Dev<pp_post_result> postOut;
+	pph::Dev<int32_t> postSlots;
+	size_t postSamples = 0; // samples the five sample buffers hold; 0 until every one of them exists
+	int postRows = 0;       // plans postEdgeEnd / postOut / postSlots hold
+	std::vector<pph::DeviceMem> postParked; // buffers outgrown while queries were in flight: hipFree waits for the whole device (the persistent grid
+	                                        // included), so they are kept until a call finds nothing in flight (or the pipeline goes)
+	int postPoints = 0;     // the last call's max_points: its sample limit and the buffers' per-plan stride
+	std::vector<pp_post_result> postHost;                  // the last call's results, by compact index
+	std::unordered_map<uint64_t, int32_t> postIndexOfTicket; // tickets of the last call that are still held -> compact index
 	int nWf = 2;      // wavefront streams in use: consecutive submissions' launches overlap (the tail of one under the head of the next)
 	int wfBlocks = 0; // workgroups per wavefront launch (<= the resident number): the wavefront kernel's share of the chip
 };
@@ -540,6 +553,19 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 				"time-out.  Give the runtime a hardware queue per stream (GPU_MAX_HW_QUEUES in the environment before the process's first HIP call), or set "
 				"PP_PIPE_ALLOW_SHARED_QUEUES=1 to run anyway (bench.py and the tests do)");
 			return PP_ERR_INVALID;
+		}
+	}
+	{
+		// an empty dispatch of k_postprocess_tickets on the stream pp_pipeline_postprocess uses: the queue allocates its scratch here, where a
+		// failure is an error code (see warm_up_kernels)
+		hipLaunchKernelGGL(k_postprocess_tickets, dim3(1), dim3(kPostThreads), 64, P->ctlStream, pl->args, PostParams {}, Footprint {}, 0, (const int32_t*)nullptr, (const PathRec*)nullptr,
+			(const RsLogEntry*)nullptr, (const DevResult*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, PostBuffers {});
+		e = hipGetLastError();
+		if (e == hipSuccess)
+			e = hipStreamSynchronize(P->ctlStream);
+		if (e != hipSuccess) {
+			free_pipeline(P);
+			return pph::hip_fail(e, "pipeline post-processing kernel warm-up (scratch allocation)");
 		}
 	}
 	std::memset(P->done, 0, ring * sizeof(PipeDone));
@@ -918,6 +944,7 @@ int pp_pipeline_poll(pp_pipeline* P, int32_t max_results, uint64_t* tickets_out,
 		results_out[n] = rec->r.r;
 		if (release) {
 			P->slotOfTicket.erase(P->ticketOfSlot[(size_t)slot]);
+			P->postIndexOfTicket.erase(P->ticketOfSlot[(size_t)slot]); // (a ticket in flight has no entry: every route that frees a slot says so all the same)
 			P->slotState[(size_t)slot] = 0;
 			P->freeSlots.push_back(slot);
 		} else {
@@ -973,6 +1000,7 @@ int pp_pipeline_release(pp_pipeline* P, int32_t n, const uint64_t* tickets)
 		}
 		P->slotState[(size_t)it->second] = 0;
 		P->freeSlots.push_back(it->second);
+		P->postIndexOfTicket.erase(it->first);
 		P->slotOfTicket.erase(it);
 	}
 	return PP_OK;
@@ -1033,6 +1061,198 @@ int pp_pipeline_get_paths(pp_pipeline* P, int32_t n, const uint64_t* tickets, in
 			}
 		}
 	}
+	if (release)
+		return pp_pipeline_release(P, n, tickets);
+	return PP_OK;
+}
+
+/// HybridAStar::SearchPath's post-processing of n completed, held queries, in the order of `tickets` (include/pp_hip.h).  Legal with queries in
+/// flight: a held slot's path records, Reeds-Shepp log and result record were written by the row that finished it BEFORE its completion record
+/// (finish() in pp_planner_rows.hpp: the stores, a system-scope release fence, s_waitcnt vmcnt(0), then the record and its stamp), the host saw
+/// that record with an acquire load in pp_pipeline_poll, and nothing writes the slot again until it is released and refilled.  The launch goes
+/// on the control stream with a COPY of the search arguments and the map view of the last submission: the buffer set's `args`, which the
+/// grid's top-up launches read, is not written, and only the control stream is synchronised: a buffer that has to grow while queries are in
+/// flight is parked, not freed (pp_pipeline::postParked).
+int pp_pipeline_postprocess(pp_pipeline* P, int32_t n, const uint64_t* tickets, float path_interpolation, const pp_smoother_params* smoother, int32_t max_points,
+	pp_post_result* results_host)
+{
+	if (!P) {
+		set_error("null pipeline");
+		return PP_ERR_INVALID;
+	}
+	if (P->dead) {
+		set_error("the pipeline failed earlier and must be destroyed");
+		return PP_ERR_HIP;
+	}
+	if (n < 0 || n > P->capacity || (n > 0 && !tickets)) {
+		set_error("invalid arguments (0 <= n <= capacity = " + std::to_string(P->capacity) + ", got n = " + std::to_string(n) + ")");
+		return PP_ERR_INVALID;
+	}
+	if (max_points < 8 || max_points > 8 * kPostThreads) {
+		set_error("invalid arguments (8 <= max_points <= 2048, got " + std::to_string(max_points) + ")");
+		return PP_ERR_INVALID;
+	}
+	if (!(path_interpolation > 0.0f)) {
+		set_error("invalid arguments (path_interpolation > 0)");
+		return PP_ERR_INVALID;
+	}
+	pp_planner* pl = P->pl;
+	pp_map* map = pl->map;
+	if (!map->obstLabel[map->obstResult] || !map->voroLabel[map->voroResult]) {
+		set_error("nearest-obstacle / nearest-edge cell grids missing: pp_map_update_gvd or pp_map_upload_nearest_cells first");
+		return PP_ERR_INVALID;
+	}
+	std::vector<int32_t> slots((size_t)n);
+	{
+		std::unordered_map<uint64_t, int32_t> seen;
+		for (int i = 0; i < n; i++) {
+			auto it = P->slotOfTicket.find(tickets[i]);
+			if (it == P->slotOfTicket.end()) {
+				set_error("ticket " + std::to_string(tickets[i]) + " is unknown or already released");
+				return PP_ERR_INVALID;
+			}
+			if (P->slotState[(size_t)it->second] != 2) {
+				set_error("ticket " + std::to_string(tickets[i]) + " is still in flight (or was not polled with release = 0): only completed, held queries are post-processed");
+				return PP_ERR_INVALID;
+			}
+			if (!seen.emplace(tickets[i], i).second) {
+				set_error("ticket " + std::to_string(tickets[i]) + " is given twice");
+				return PP_ERR_INVALID;
+			}
+			slots[(size_t)i] = it->second;
+		}
+	}
+	// the last call's results end here (also for n == 0), whatever happens below
+	P->postIndexOfTicket.clear();
+	P->postHost.clear();
+	if (n == 0)
+		return PP_OK;
+	PP_HIP_TRY(hipSetDevice(map->ctx->device));
+	const size_t samples = (size_t)n * (size_t)max_points;
+	// Nothing is freed while queries are in flight: hipFree waits for every stream of the device, i.e. for the searches in flight and the grid's
+	// idle waves.  A buffer that has to grow is parked instead, and the parked ones go when a call finds the pipeline idle.
+	const bool idle = P->nSubmitted == P->doneHead;
+	if (idle)
+		P->postParked.clear();
+	auto park = [&](pph::DeviceMem& b) {
+		if (!idle && b.get())
+			P->postParked.emplace_back(std::move(b));
+	};
+	if (P->postSamples < samples) {
+		P->postSamples = 0; // until every buffer below exists again: a failed allocation must not leave a stale capacity behind
+		park(P->postRatios), park(P->postResampled), park(P->postSmoothed), park(P->postCusp), park(P->postOptimise);
+		PP_HIP_TRY(P->postRatios.alloc(samples * 8));
+		PP_HIP_TRY(P->postResampled.alloc(samples * 24));
+		PP_HIP_TRY(P->postSmoothed.alloc(samples * 24));
+		PP_HIP_TRY(P->postCusp.alloc(samples));
+		PP_HIP_TRY(P->postOptimise.alloc(samples));
+		P->postSamples = samples;
+	}
+	if (P->postRows < n) {
+		P->postRows = 0;
+		park(P->postEdgeEnd), park(P->postOut), park(P->postSlots);
+		PP_HIP_TRY(P->postEdgeEnd.alloc((size_t)n * (size_t)(pl->maxPath + 1) * 8));
+		PP_HIP_TRY(P->postOut.alloc((size_t)n * sizeof(pp_post_result)));
+		PP_HIP_TRY(P->postSlots.alloc((size_t)n * 4));
+		P->postRows = n;
+	}
+	const PostBuffers post { P->postRatios, P->postResampled, P->postSmoothed, P->postCusp, P->postOptimise, P->postEdgeEnd, P->postOut };
+	PostParams pp {};
+	pp.pathInterpolation = path_interpolation;
+	pp_smoother_params sp { 1e-3f, 2000, 0.01f, 0.0f, 0.4f, 0.02f, 0.2f, 0.4f, 0.2f, (float)(1.0 / pl->params.min_turning_radius) }; // as pp_planner_postprocess
+	if (smoother)
+		sp = *smoother;
+	pp.stepTolerance = sp.step_tolerance;
+	pp.maxIterations = sp.max_iterations;
+	pp.learningRate = sp.learning_rate;
+	pp.pathWeight = sp.path_weight;
+	pp.smoothWeight = sp.smooth_weight;
+	pp.voronoiWeight = sp.voronoi_weight;
+	pp.collisionWeight = sp.collision_weight;
+	pp.curvatureWeight = sp.curvature_weight;
+	pp.collisionRatio = sp.collision_ratio;
+	pp.maxCurvature = sp.max_curvature;
+	pp.alpha = 20.0f; // GVD::alpha / dMax, gvd.h:181
+	pp.dMax = 30.0f;
+	pp.maxPoints = max_points;
+	SearchArgs args = pl->args;                          // a copy: the top-up launches of the search grid read pl->args
+	args.m = P->viewValid ? P->lastView : map->view(); // (held slots exist only after a submission, which cached the view)
+	Footprint foot {};                                   // n = 0: no footprint check
+	if (P->footprint)
+		foot = P->footprint->fp;
+	hipStream_t s = P->ctlStream;
+	PP_HIP_TRY(hipMemcpyAsync(P->postSlots, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, s)); // (pageable source: staged before the call returns)
+	hipLaunchKernelGGL(k_postprocess_tickets, dim3(n), dim3(kPostThreads), (size_t)max_points * 16, s, args, pp, foot, n, P->postSlots.get(), pl->paths.get(), pl->rsLogs.get(),
+		pl->results.get(), map->obstLabel[map->obstResult].get(), map->voroLabel[map->voroResult].get(), post);
+	PP_HIP_TRY(hipGetLastError());
+	std::vector<pp_post_result> host((size_t)n);
+	PP_HIP_TRY(hipMemcpyAsync(host.data(), P->postOut, (size_t)n * sizeof(pp_post_result), hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipStreamSynchronize(s));
+	P->postHost.swap(host);
+	P->postPoints = max_points;
+	for (int i = 0; i < n; i++)
+		P->postIndexOfTicket[tickets[i]] = i;
+	if (results_host)
+		for (int i = 0; i < n; i++)
+			results_host[i] = P->postHost[(size_t)i];
+	return PP_OK;
+}
+
+/// sampled path, cusp flags and smoothed path of tickets of the LAST pp_pipeline_postprocess call that are still held (include/pp_hip.h)
+int pp_pipeline_get_processed_paths(pp_pipeline* P, int32_t n, const uint64_t* tickets, int32_t max_points, double* sampled_host, uint8_t* cusp_host, double* smoothed_host,
+	int32_t* n_points_host, int32_t release)
+{
+	if (!P || n < 0 || max_points < 1 || (n > 0 && (!tickets || !n_points_host))) {
+		set_error("invalid arguments");
+		return PP_ERR_INVALID;
+	}
+	if (P->dead) {
+		set_error("the pipeline failed earlier and must be destroyed");
+		return PP_ERR_HIP;
+	}
+	std::vector<int32_t> index((size_t)n);
+	for (int i = 0; i < n; i++) {
+		auto it = P->postIndexOfTicket.find(tickets[i]);
+		auto st = P->slotOfTicket.find(tickets[i]);
+		if (it == P->postIndexOfTicket.end() || st == P->slotOfTicket.end() || P->slotState[(size_t)st->second] != 2) {
+			set_error("ticket " + std::to_string(tickets[i]) + " has no post-processed path: not in the last pp_pipeline_postprocess call, or released since");
+			return PP_ERR_INVALID;
+		}
+		index[(size_t)i] = it->second;
+	}
+	if (n == 0)
+		return PP_OK;
+	PP_HIP_TRY(hipSetDevice(P->pl->map->ctx->device));
+	hipStream_t s = P->ctlStream;
+	const size_t cap = (size_t)P->postPoints, stride = (size_t)max_points;
+	bool consecutive = stride == cap;
+	for (int i = 1; i < n && consecutive; i++)
+		consecutive = index[(size_t)i] == index[0] + i;
+	for (int i = 0; i < n; i++)
+		n_points_host[i] = P->postHost[(size_t)index[(size_t)i]].n_points;
+	if (consecutive) { // the caller's layout is the buffers': one copy per array (rows beyond n_points are unspecified either way)
+		const size_t first = (size_t)index[0] * cap, count = (size_t)n * cap;
+		if (sampled_host)
+			PP_HIP_TRY(hipMemcpyAsync(sampled_host, P->postResampled + first * 3, count * 24, hipMemcpyDeviceToHost, s));
+		if (cusp_host)
+			PP_HIP_TRY(hipMemcpyAsync(cusp_host, P->postCusp + first, count, hipMemcpyDeviceToHost, s));
+		if (smoothed_host)
+			PP_HIP_TRY(hipMemcpyAsync(smoothed_host, P->postSmoothed + first * 3, count * 24, hipMemcpyDeviceToHost, s));
+	} else {
+		for (int i = 0; i < n; i++) {
+			const size_t from = (size_t)index[(size_t)i] * cap, to = (size_t)i * stride;
+			const size_t np = (size_t)n_points_host[i] < stride ? (size_t)n_points_host[i] : stride;
+			if (np == 0)
+				continue;
+			if (sampled_host)
+				PP_HIP_TRY(hipMemcpyAsync(sampled_host + to * 3, P->postResampled + from * 3, np * 24, hipMemcpyDeviceToHost, s));
+			if (cusp_host)
+				PP_HIP_TRY(hipMemcpyAsync(cusp_host + to, P->postCusp + from, np, hipMemcpyDeviceToHost, s));
+			if (smoothed_host)
+				PP_HIP_TRY(hipMemcpyAsync(smoothed_host + to * 3, P->postSmoothed + from * 3, np * 24, hipMemcpyDeviceToHost, s));
+		}
+	}
+	PP_HIP_TRY(hipStreamSynchronize(s));
 	if (release)
 		return pp_pipeline_release(P, n, tickets);
 	return PP_OK;

@@ -289,7 +289,13 @@ struct PipeView {
 #define PP_ROWS_FOOTPRINT 1
 #include "pp_planner_rows.hpp"
 #undef PP_ROWS_FOOTPRINT
+// ... and so is the post-processing kernel's (see the head of pp_postprocess.hpp): k_postprocess, then k_postprocess_tickets
+#define PP_POST_TICKETS 0
 #include "pp_postprocess.hpp"
+#undef PP_POST_TICKETS
+#define PP_POST_TICKETS 1
+#include "pp_postprocess.hpp"
+#undef PP_POST_TICKETS
 
 } // namespace
 

@@ -11,7 +11,19 @@
 // by one lane; sampling and every smoother iteration are parallel over the points.  A point's gradient receives its
 // contributions in the reference's order: the curvature term of point i-1, the five terms of point i, the curvature term of
 // point i+1 (the reference walks the optimised indices in ascending order and `+=`s into gradients[i-1], [i], [i+1]).
-#pragma once
+//
+// The kernel's text is compiled twice (pp_planner.hip includes this file with PP_POST_TICKETS 0, then 1), as the rows kernel's is:
+//   k_postprocess          workgroup q works on query q of a batch and writes its outputs at q;
+//   k_postprocess_tickets  workgroup i works on field slot slots[i] of a pipeline's buffer set and writes its outputs at the compact
+//                          index i (pp_pipeline_postprocess: buffers sized by the call, not by the capacity); with a footprint
+//                          (Footprint::n > 0) a path whose point checks passed is checked once more, sample by sample, against the
+//                          footprint (fp_state_valid): smoothing_status -2 when one fails.  The descent itself is the same text.
+// Two kernels from one text rather than a shared __device__ template: the first form's registers and spills stay what they were.
+#ifndef PP_POST_TICKETS
+#error "define PP_POST_TICKETS (0: k_postprocess, 1: k_postprocess_tickets) before including pp_postprocess.hpp"
+#endif
+#ifndef PP_POSTPROCESS_SHARED
+#define PP_POSTPROCESS_SHARED
 
 constexpr int kPostThreads = 256;
 
@@ -122,13 +134,27 @@ __device__ inline PostEdge load_edge(const SearchArgs& A, const PathRec* recs, i
 	return E;
 }
 
+#endif // PP_POSTPROCESS_SHARED
+
+#if PP_POST_TICKETS
+__global__ void __launch_bounds__(kPostThreads) k_postprocess_tickets(SearchArgs A, PostParams P, Footprint F, int nQueries, const int32_t* __restrict__ slots,
+	const PathRec* __restrict__ pathBase, const RsLogEntry* __restrict__ rsLogBase, const DevResult* __restrict__ results, const uint32_t* __restrict__ obstLabel,
+	const uint32_t* __restrict__ voroLabel, PostBuffers B)
+{
+	const int q = blockIdx.x, tid = threadIdx.x; // the compact index: where every output goes
+	if (q >= nQueries)
+		return;
+	const int slot = slots[q]; // the field slot whose plan is read
+#else
 __global__ void __launch_bounds__(kPostThreads) k_postprocess(SearchArgs A, PostParams P, int nQueries, const PathRec* __restrict__ pathBase, const RsLogEntry* __restrict__ rsLogBase,
 	const DevResult* __restrict__ results, const uint32_t* __restrict__ obstLabel, const uint32_t* __restrict__ voroLabel, PostBuffers B)
 {
 	const int q = blockIdx.x, tid = threadIdx.x;
 	if (q >= nQueries)
 		return;
-	const DevResult res = results[q];
+	const int slot = q;
+#endif
+	const DevResult res = results[slot];
 	const int cap = P.maxPoints;
 	double* const ratios = B.ratios + (size_t)q * cap;
 	double* const resampled = B.resampled + (size_t)q * cap * 3;
@@ -136,14 +162,17 @@ __global__ void __launch_bounds__(kPostThreads) k_postprocess(SearchArgs A, Post
 	uint8_t* const cusp = B.cusp + (size_t)q * cap;
 	uint8_t* const optimise = B.optimise + (size_t)q * cap;
 	double* const edgeEnd = B.edgeEnd + (size_t)q * (A.maxPath + 1);
-	const PathRec* const recs = pathBase + (size_t)q * A.maxPath;
-	const RsLogEntry* const rslog = rsLogBase + (size_t)q * kRsLogCap;
+	const PathRec* const recs = pathBase + (size_t)slot * A.maxPath;
+	const RsLogEntry* const rslog = rsLogBase + (size_t)slot * kRsLogCap;
 	const MapView& m = A.m;
 	__shared__ int s_n, s_status, s_iter, s_go;
 	__shared__ double s_length;
 	__shared__ float s_stepW[kPostThreads / 64];
 	__shared__ float s_step;
 	__shared__ int s_unsafe;
+#if PP_POST_TICKETS
+	__shared__ int s_offFootprint;
+#endif
 	extern __shared__ double s_pos[]; // [2 * cap] current positions (x, y interleaved)
 
 	const int nPath = res.r.n_path;
@@ -269,14 +298,34 @@ __global__ void __launch_bounds__(kPostThreads) k_postprocess(SearchArgs A, Post
 			if (!is_state_valid(m, resampled[3 * i], resampled[3 * i + 1], resampled[3 * i + 2], d))
 				bad = 1;
 		}
-		if (tid == 0)
+		if (tid == 0) {
 			s_unsafe = 0;
+#if PP_POST_TICKETS
+			s_offFootprint = 0;
+#endif
+		}
 		__syncthreads();
 		if (bad)
 			atomicOr(&s_unsafe, 1);
 		__syncthreads();
+#if PP_POST_TICKETS
+		if (F.n > 0 && !s_unsafe) { // (workgroup-uniform: s_unsafe is not written any more)
+			int off = 0;
+			for (int i = tid; i < n; i += kPostThreads) {
+				float clearance, border;
+				if (!fp_state_valid(m, F, smoothed[3 * i], smoothed[3 * i + 1], smoothed[3 * i + 2], clearance, border))
+					off = 1;
+			}
+			if (off)
+				atomicOr(&s_offFootprint, 1);
+			__syncthreads();
+		}
+		if (tid == 0)
+			B.out[q] = pp_post_result { n, s_unsafe ? -1 : (s_offFootprint ? -2 : 2), 0, 0, s_length };
+#else
 		if (tid == 0)
 			B.out[q] = pp_post_result { n, s_unsafe ? -1 : 2, 0, 0, s_length };
+#endif
 		return;
 	}
 	if (tid == 0) { // the indices to optimise, smoother.cpp:54-76
@@ -409,8 +458,12 @@ __global__ void __launch_bounds__(kPostThreads) k_postprocess(SearchArgs A, Post
 		__syncthreads();
 	}
 	// ---------------- IsPathSafe + results
-	if (tid == 0)
+	if (tid == 0) {
 		s_unsafe = 0;
+#if PP_POST_TICKETS
+		s_offFootprint = 0;
+#endif
+	}
 	__syncthreads();
 	int bad = 0;
 	for (int i = tid; i < n; i += kPostThreads) {
@@ -423,6 +476,24 @@ __global__ void __launch_bounds__(kPostThreads) k_postprocess(SearchArgs A, Post
 	if (bad)
 		atomicOr(&s_unsafe, 1);
 	__syncthreads();
+#if PP_POST_TICKETS
+	// what HybridAStar::SearchPath of the C++ mirror does on the host: a path the smoother returned (status >= 0) is checked sample by sample
+	// against the footprint, each sample at its own heading; one that fails makes the sampled path the result (-2)
+	if (F.n > 0 && !s_unsafe && status >= 0) { // (workgroup-uniform: s_unsafe is not written any more)
+		int off = 0;
+		for (int i = tid; i < n; i += kPostThreads) {
+			float clearance, border;
+			if (!fp_state_valid(m, F, s_pos[2 * i], s_pos[2 * i + 1], smoothed[3 * i + 2], clearance, border))
+				off = 1;
+		}
+		if (off)
+			atomicOr(&s_offFootprint, 1);
+		__syncthreads();
+	}
+	if (tid == 0)
+		B.out[q] = pp_post_result { n, s_unsafe ? -1 : (s_offFootprint ? -2 : status), count, 0, s_length };
+#else
 	if (tid == 0)
 		B.out[q] = pp_post_result { n, s_unsafe ? -1 : status, count, 0, s_length };
+#endif
 }

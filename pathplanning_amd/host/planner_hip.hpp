@@ -18,6 +18,7 @@
 #include <cmath>
 #include <algorithm>
 #include <tuple>
+#include <unordered_map>
 
 #include "types.hpp"
 #include "paths.hpp"
@@ -1002,9 +1003,12 @@ struct RRTStarParameters {
 	double radiusGamma = 0.0;
 };
 
-/// HybridAStar::SearchPath's search stage for a STREAM of queries (include/pp_hip.h: pp_pipeline_*): queries are submitted as they
+/// HybridAStar::SearchPath for a STREAM of queries (include/pp_hip.h: pp_pipeline_*): queries are submitted as they
 /// come -- up to `capacity` in flight -- and results polled in completion order; per query they are what HybridAStar::SearchPath
 /// finds (same device code).  The scheduling that keeps the GPU full lives in the library, not in the caller.
+/// Poll(out, max, hold = true) keeps the completed queries' slots: GetGraphSearchPath(ticket) is their graph-search nodes, PostProcess(tickets)
+/// samples and smooths them on the device (pp_pipeline_postprocess, legal while others are in flight), GetPath(ticket) is then what
+/// HybridAStar::GetPath() returns for that query, GetSmoothingStatus(ticket) its Stats::smoothingStatus; Release(tickets) frees the slots.
 class HybridAStarPipeline {
 public:
 	struct Result {
@@ -1014,7 +1018,7 @@ public:
 		int numExpanded = 0, numPathNodes = 0, latticeBoundaryHits = 0;
 	};
 	explicit HybridAStarPipeline(const HybridAStar::SearchParameters& p, int capacity = 24576, int maxNodes = 81920, int searchRows = 0) :
-		m_param(p), m_capacity(capacity), m_maxNodes(maxNodes), m_searchRows(searchRows) { }
+		m_smootherParam((float)(1.0 / p.minTurningRadius)), m_param(p), m_capacity(capacity), m_maxNodes(maxNodes), m_searchRows(searchRows) { } // hybrid_a_star.cpp:214
 	HybridAStarPipeline(const HybridAStarPipeline&) = delete;
 	HybridAStarPipeline& operator=(const HybridAStarPipeline&) = delete;
 	~HybridAStarPipeline()
@@ -1035,6 +1039,7 @@ public:
 			pp_pipeline_destroy(m_pipe);
 			m_pipe = nullptr;
 		}
+		m_held.clear();
 		if (pp_pipeline_create(validator->Device(), &hp, m_capacity, m_maxNodes, m_searchRows, 0, &m_pipe))
 			return false;
 		m_pipeFootprint = nullptr;
@@ -1066,8 +1071,8 @@ public:
 			tickets->assign(t.begin(), t.begin() + taken);
 		return taken;
 	}
-	/// completed queries so far (never blocks); their slots are free again
-	int Poll(std::vector<Result>& out, int maxResults = 4096)
+	/// completed queries so far (never blocks); their slots are free again, or with `hold` kept until Release
+	int Poll(std::vector<Result>& out, int maxResults = 4096, bool hold = false)
 	{
 		out.clear();
 		if (!m_pipe)
@@ -1075,8 +1080,10 @@ public:
 		std::vector<uint64_t> t((size_t)maxResults);
 		std::vector<pp_query_result> r((size_t)maxResults);
 		int32_t n = 0;
-		ppCheck(pp_pipeline_poll(m_pipe, maxResults, t.data(), r.data(), 1, &n));
+		ppCheck(pp_pipeline_poll(m_pipe, maxResults, t.data(), r.data(), hold ? 0 : 1, &n));
 		for (int i = 0; i < n; i++) {
+			if (hold)
+				m_held[t[(size_t)i]] = Held { r[(size_t)i].status == 0 ? r[(size_t)i].n_path : 0 };
 			Result x;
 			x.ticket = t[(size_t)i];
 			x.status = r[(size_t)i].status == 0 ? Status::Success : Status::Failure;
@@ -1099,8 +1106,94 @@ public:
 	float GetHeuristicClearance() const { return m_heuristicClearance; }
 	int InFlight() const { return m_pipe ? pp_pipeline_in_flight(m_pipe) : 0; }
 	int FreeSlots() const { return m_pipe ? pp_pipeline_free_slots(m_pipe) : 0; }
+	/// nodes of a held query's graph-search solution, root .. goal (HybridAStar::GetGraphSearchNodes); empty when the search failed
+	std::vector<Pose2d> GetGraphSearchPath(uint64_t ticket) const
+	{
+		const Held& h = HeldOf(ticket);
+		std::vector<Pose2d> out((size_t)h.nPath);
+		if (h.nPath > 0) {
+			int32_t n = 0;
+			ppCheck(pp_pipeline_get_paths(m_pipe, 1, &ticket, h.nPath, &out[0].position.v[0], &n, 0));
+		}
+		return out;
+	}
+	/// HybridAStar::SearchPath's post-processing (hybrid_a_star.cpp:260-303) of held queries, sampled every `pathInterpolation` metres, with
+	/// Get/SetSmootherParameters: afterwards GetPath(ticket) is the smoothed path when smoothing worked, else the sampled one, and
+	/// GetSmoothingStatus(ticket) says which.  With a footprint on the validator a smoothed path with a sample off the footprint gives the
+	/// sampled path and Smoother::Status::Collision (checked on the device).  A query whose search failed, a one-node path, a path of more
+	/// than 2048 samples and a map without nearest-cell grids keep the graph-search nodes and Smoother::Status::Failure, as HybridAStar does.
+	void PostProcess(const std::vector<uint64_t>& tickets, float pathInterpolation = 0.1f)
+	{
+		for (uint64_t t : tickets) {
+			HeldOf(t); // (throws for a ticket that is not held)
+			Held& h = m_held[t];
+			h.path = GetGraphSearchPath(t);
+			h.smoothingStatus = Smoother::Status::Failure;
+			h.processed = true;
+		}
+		if (tickets.empty() || !m_validator->GetOccupancyMap()->HasNearestCells())
+			return;
+		if (InFlight() == 0)
+			SyncFootprint(); // (a footprint set, changed or cleared while the queries were held; with queries in flight the pipeline's stays)
+		const pp_smoother_params sp { m_smootherParam.stepTolerance, m_smootherParam.maxIterations, m_smootherParam.learningRate, m_smootherParam.pathWeight,
+			m_smootherParam.smoothWeight, m_smootherParam.voronoiWeight, m_smootherParam.collisionWeight, m_smootherParam.curvatureWeight, m_smootherParam.collisionRatio,
+			m_smootherParam.maxCurvature };
+		const int n = (int)tickets.size();
+		std::vector<pp_post_result> post((size_t)n);
+		ppCheck(pp_pipeline_postprocess(m_pipe, n, tickets.data(), pathInterpolation, &sp, 2048, post.data()));
+		int cap = 1;
+		for (const pp_post_result& r : post)
+			cap = std::max(cap, (int)r.n_points);
+		std::vector<Pose2d> sampled((size_t)n * (size_t)cap), smoothed((size_t)n * (size_t)cap);
+		std::vector<int32_t> nPoints((size_t)n);
+		ppCheck(pp_pipeline_get_processed_paths(m_pipe, n, tickets.data(), cap, &sampled[0].position.v[0], nullptr, &smoothed[0].position.v[0], nPoints.data(), 0));
+		for (int i = 0; i < n; i++) {
+			const pp_post_result& r = post[(size_t)i];
+			if (r.n_points <= 0)
+				continue;
+			Held& h = m_held[tickets[(size_t)i]];
+			h.smoothingStatus = (Smoother::Status)r.smoothing_status; // (-2 is Smoother::Status::Collision)
+			const std::vector<Pose2d>& from = r.smoothing_status >= 0 ? smoothed : sampled;
+			h.path.assign(from.begin() + (size_t)i * (size_t)cap, from.begin() + (size_t)i * (size_t)cap + (size_t)r.n_points);
+		}
+	}
+	/// HybridAStar::GetPath() of a held query: after PostProcess the sampled and, when the smoother succeeded, smoothed path; before it the
+	/// graph-search nodes
+	std::vector<Pose2d> GetPath(uint64_t ticket) const
+	{
+		const Held& h = HeldOf(ticket);
+		return h.processed ? h.path : GetGraphSearchPath(ticket);
+	}
+	/// HybridAStar::Stats::smoothingStatus of a held query (Failure before PostProcess)
+	Smoother::Status GetSmoothingStatus(uint64_t ticket) const { return HeldOf(ticket).smoothingStatus; }
+	/// returns held queries' slots to the pipeline; their paths are gone
+	void Release(const std::vector<uint64_t>& tickets)
+	{
+		if (!m_pipe || tickets.empty())
+			return;
+		ppCheck(pp_pipeline_release(m_pipe, (int32_t)tickets.size(), tickets.data()));
+		for (uint64_t t : tickets)
+			m_held.erase(t);
+	}
+	const Smoother::Parameters& GetSmootherParameters() const { return m_smootherParam; }
+	void SetSmootherParameters(const Smoother::Parameters& p) { m_smootherParam = p; }
 
 private:
+	struct Held {
+		int nPath = 0; // nodes of the graph-search solution (0: the search failed)
+		Smoother::Status smoothingStatus = Smoother::Status::Failure;
+		std::vector<Pose2d> path; // GetPath() once PostProcess has run
+		bool processed = false; // PostProcess has run on it
+	};
+	const Held& HeldOf(uint64_t ticket) const
+	{
+		auto it = m_held.find(ticket);
+		if (it == m_held.end())
+			throw std::invalid_argument("HybridAStarPipeline: ticket is not a completed, held query (Poll with hold = true)");
+		return it->second;
+	}
+	std::unordered_map<uint64_t, Held> m_held;
+	Smoother::Parameters m_smootherParam;
 	/// hands the validator's footprint as it is now to the pipeline (HybridAStar::SyncFootprint); the grid's waves keep the footprint they were
 	/// launched with, so a change with queries in flight throws with the library's message: poll everything first
 	void SyncFootprint()

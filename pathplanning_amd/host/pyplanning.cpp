@@ -380,6 +380,39 @@ PYBIND11_MODULE(pyplanning, m)
 				return out;
 			});
 
+	// ---- the streaming pipeline (beyond the reference's surface): HybridAStar::SearchPath for a stream of queries, paths by ticket ----
+	py::class_<HybridAStarPipeline>(m, "HybridAStarPipeline")
+		.def(py::init<const HybridAStar::SearchParameters&, int, int, int>(), py::arg("parameters"), py::arg("capacity") = 24576, py::arg("max_nodes") = 81920,
+			py::arg("search_rows") = 0)
+		.def("initialize", &HybridAStarPipeline::Initialize)
+		.def("submit",
+			[](HybridAStarPipeline& h, const std::vector<Pose2d>& starts, const std::vector<Pose2d>& goals, const std::vector<uint64_t>& seeds) {
+				std::vector<uint64_t> tickets;
+				h.Submit(starts, goals, seeds, &tickets);
+				return tickets; // of the prefix taken
+			})
+		// completed queries as (ticket, status, cost, n_expanded, n_path); hold=True keeps their slots for get_path / post_process until release
+		.def("poll",
+			[](HybridAStarPipeline& h, int maxResults, bool hold) {
+				std::vector<HybridAStarPipeline::Result> res;
+				h.Poll(res, maxResults, hold);
+				py::list out;
+				for (const auto& r : res)
+					out.append(py::make_tuple(r.ticket, r.status, r.cost, r.numExpanded, r.numPathNodes));
+				return out;
+			},
+			py::arg("max_results") = 4096, py::arg("hold") = false)
+		.def("post_process", &HybridAStarPipeline::PostProcess, py::arg("tickets"), py::arg("path_interpolation") = 0.1f)
+		.def("get_path", &HybridAStarPipeline::GetPath, py::arg("ticket"))
+		.def("get_graph_search_path", &HybridAStarPipeline::GetGraphSearchPath, py::arg("ticket"))
+		.def("get_smoothing_status", &HybridAStarPipeline::GetSmoothingStatus, py::arg("ticket"))
+		.def("release", &HybridAStarPipeline::Release, py::arg("tickets"))
+		.def("in_flight", &HybridAStarPipeline::InFlight)
+		.def("free_slots", &HybridAStarPipeline::FreeSlots)
+		.def_property("smoother_parameters", &HybridAStarPipeline::GetSmootherParameters, &HybridAStarPipeline::SetSmootherParameters)
+		.def("set_heuristic_clearance", &HybridAStarPipeline::SetHeuristicClearance, py::arg("radius"))
+		.def_property_readonly("heuristic_clearance", &HybridAStarPipeline::GetHeuristicClearance);
+
 	// ---- grid A* (pyplanning.cpp:124-197): cost / heuristic are Python callables per edge, as in the reference ----
 	py::class_<NullAction>(m, "NullAction").def(py::init<>());
 	using AStarHeuristicN2 = AStarHeuristic<GridCellPosition>;

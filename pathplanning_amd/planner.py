@@ -860,6 +860,7 @@ class HybridAStarPipeline:
         if release:
             for x in t:
                 self._held.pop(int(x), None)
+                getattr(self, "_post_by_ticket", {}).pop(int(x), None)
         return poses[:k], n_poses[:k]
 
     def backlog(self):
@@ -890,6 +891,7 @@ class HybridAStarPipeline:
         check(self.lib.pp_pipeline_release(self.h, len(t), ptr(t)))
         for x in t:
             self._held.pop(int(x), None)
+            getattr(self, "_post_by_ticket", {}).pop(int(x), None)
 
     def get_path_of(self, ticket):
         """solution path of a completed query polled with release=False"""
@@ -906,7 +908,9 @@ class HybridAStarPipeline:
         """HybridAStar::SearchPath's post-processing (hybrid_a_star.cpp:260-304) over the field slots 0 .. n_slots-1 of the pipeline's buffer
         set (pp_planner_postprocess on pp_pipeline_planner()): meaningful for slots whose queries are completed and HELD (polled with
         release=False); read a query's processed path with get_processed_path_of(ticket).  The smoother knows the point validator only:
-        with a footprint set (set_footprint) the search's plans respect it, the smoothed paths are checked against the reference point alone."""
+        with a footprint set (set_footprint) the search's plans respect it, the smoothed paths are checked against the reference point alone.
+        postprocess(tickets) is the form by ticket: it works on the held queries named, with buffers sized by the call, may run with
+        queries in flight, and checks the smoothed samples against the footprint."""
         n = self.capacity if n_slots is None else int(n_slots)
         sp = None
         if smoother is not None:
@@ -931,6 +935,49 @@ class HybridAStarPipeline:
             check(self.lib.pp_planner_get_processed_path(self.planner_h, slot, ptr(sampled), ptr(cusp), ptr(smoothed)))
         return dict(sampled=sampled, cusp=cusp.astype(bool), smoothed=smoothed, status=r.smoothing_status, iterations=r.iterations, length=r.length,
                     path=smoothed if r.smoothing_status >= 0 else sampled)
+
+    def postprocess(self, tickets, path_interpolation=0.1, smoother=None, max_points=2048):
+        """HybridAStar::SearchPath's post-processing (hybrid_a_star.cpp:260-304) of the completed, HELD queries `tickets`
+        (pp_pipeline_postprocess), in that order; legal while other queries are in flight.  `smoother` as HybridAStarBatch.postprocess.
+        Returns one PostResult per ticket.  With a footprint set (set_footprint) a path the smoother kept is checked sample by sample
+        against it: smoothing_status -2 when one fails, and the sampled path is then the result.  Raises PPError, with nothing launched,
+        for a ticket that is unknown, released, in flight or given twice."""
+        t = np.ascontiguousarray(tickets, dtype=np.uint64).reshape(-1)
+        sp = None
+        if smoother is not None:
+            d = dict(step_tolerance=1e-3, max_iterations=2000, learning_rate=0.01, path_weight=0.0, smooth_weight=0.4, voronoi_weight=0.02, collision_weight=0.2,
+                     curvature_weight=0.4, collision_ratio=0.2, max_curvature=1.0 / self.params.min_turning_radius)
+            d.update(smoother)
+            sp = SmootherParams(**d)
+        out = (PostResult * max(len(t), 1))()
+        check(self.lib.pp_pipeline_postprocess(self.h, len(t), ptr(t), C.c_float(path_interpolation), C.byref(sp) if sp is not None else None, int(max_points), out))
+        self._post_by_ticket = {int(x): out[i] for i, x in enumerate(t)}
+        self._post_points = int(max_points)
+        return list(out)[:len(t)]
+
+    def get_processed_paths(self, tickets, release=False):
+        """Sampled path, cusp flags and smoothed path of tickets of the LAST postprocess() call that are still held
+        (pp_pipeline_get_processed_paths): a list of dicts shaped like get_processed_path_of's; `path` = what HybridAStar::GetPath()
+        returns (the smoothed path when status >= 0, else the sampled one).  Any other ticket raises PPError."""
+        t = np.ascontiguousarray(tickets, dtype=np.uint64).reshape(-1)
+        k = len(t)
+        post = getattr(self, "_post_by_ticket", {})
+        cap = max([post[int(x)].n_points for x in t if int(x) in post] + [1])
+        sampled, smoothed = np.empty((max(k, 1), cap, 3)), np.empty((max(k, 1), cap, 3))
+        cusp = np.empty((max(k, 1), cap), dtype=np.uint8)
+        n_points = np.zeros(max(k, 1), dtype=np.int32)
+        check(self.lib.pp_pipeline_get_processed_paths(self.h, k, ptr(t), cap, ptr(sampled), ptr(cusp), ptr(smoothed), ptr(n_points), int(bool(release))))
+        out = []
+        for i, x in enumerate(t):
+            r, n = post[int(x)], int(n_points[i])
+            a, b = sampled[i, :n].copy(), smoothed[i, :n].copy()
+            out.append(dict(sampled=a, cusp=cusp[i, :n].astype(bool), smoothed=b, status=r.smoothing_status, iterations=r.iterations, length=r.length,
+                            path=b if r.smoothing_status >= 0 else a))
+        if release:
+            for x in t:
+                self._held.pop(int(x), None)
+                post.pop(int(x), None)
+        return out
 
     def get_expanded_of(self, ticket):
         """expansion sequence (log_expansions=True) of a completed query polled with release=False"""
