@@ -505,6 +505,47 @@ int pp_pipeline_postprocess(pp_pipeline* pipeline, int32_t n, const uint64_t* ti
  * smoothing_status >= 0, else the sampled one.  release != 0: as pp_pipeline_release. */
 int pp_pipeline_get_processed_paths(pp_pipeline* pipeline, int32_t n, const uint64_t* tickets, int32_t max_points, double* sampled_host, uint8_t* cusp_host,
 	double* smoothed_host, int32_t* n_points_host, int32_t release);
+/* ---- re-validation of held plans against a changed map, by ticket ------------------------------------------------------------------
+ * Is the plan of a completed, HELD query still collision-free on `target` as that map is NOW?  One wave per ticket (k_revalidate_tickets)
+ * reads the plan where the search left it -- the path records and the Reeds-Shepp log of the ticket's field slot -- and marches every
+ * edge (a constant-steer arc per node, the Reeds-Shepp path of the analytic expansion at the end) with the predicate the search used
+ * on it, against the target map's view at the time of the call; then the plan's last pose gets the state check, because IsPathValid
+ * (state_validator_occupancy_map.cpp:28-71) never samples ratio 1 of a path.  results_host[i] (may be NULL) belongs to tickets[i].
+ *  - target == NULL: the pipeline's own map as it is now (not the view of the last submission, which pp_pipeline_postprocess uses).
+ *    Otherwise any pp_map of the same context with a distance grid, of any geometry: bounds, resolution, origins, the distance grid and
+ *    pp_map_set_validator's tunables (min_safe_radius, min_path_interpolation_distance) are all the target's.  So a caller may edit map B
+ *    while the grid searches map A.  With the pipeline's own map as the target the rule of pp_pipeline_submit_dev holds: changing the
+ *    CONTENTS of a map's grids while queries that read them are in flight is the caller's to avoid.
+ *  - Without a footprint (pp_pipeline_set_footprint) an edge is checked as pp_check_arcs / pp_check_rs_paths check it and the last pose
+ *    as pp_check_states does.  With the pipeline's current footprint: as pp_check_arcs_footprint (gain (float)(1 + |kappa| * rho)),
+ *    pp_check_rs_paths_footprint (gain (float)(1 + rho / min_turning_radius)) and pp_check_states_footprint.  Only the footprint's discs
+ *    are used; every distance is read from the target's grid, so the footprint need not belong to the target.
+ *  - Legal with queries in flight: a held slot is not written until it is released.  The launch runs on the pipeline's control stream
+ *    with a copy of the search arguments; only that stream is synchronised, and nothing the search grid reads is written.
+ *  - PP_ERR_INVALID, nothing launched, the pipeline usable as before, the message naming the first offending ticket: n < 0 or
+ *    n > capacity; a ticket that is unknown, released or still in flight; a ticket given twice; a target of another context; a target
+ *    without a distance grid.  n == 0 is PP_OK.
+ *  - The pipeline owns the slot list and the result buffer (4 + 32 bytes per ticket of the largest call so far).  One that has to grow while
+ *    queries are in flight is kept aside like the post-processing buffers.  The results of the last pp_pipeline_postprocess call are
+ *    not touched: pp_pipeline_get_processed_paths works as before.
+ * Lengths: `length` is the sequential root-first sum of the edges' lengths, pp_post_result::length bit for bit. */
+typedef struct pp_revalidate_result {
+	int32_t status;        /* 0 still valid; 1 an edge is blocked; 2 every edge passes, the goal pose fails the state check;
+	                          -1 no plan (the search did not succeed); -4 path longer than the planner's path capacity */
+	int32_t n_edges;       /* n_path - 1 */
+	int32_t blocked_edge;  /* status 1: first blocked edge, root first, 1..n_edges (edge e joins path poses e-1 and e); else 0 */
+	float   blocked_ratio; /* status 1: IsPathValid's `last` of that edge; else 1 */
+	double  valid_length;  /* metres drivable from the start: lengths of the edges before blocked_edge
+	                          + (double)blocked_ratio * that edge's length; == length for status 0 and 2; 0 for status < 0 */
+	double  length;        /* composite length, sequential root-first sum */
+} pp_revalidate_result;
+int pp_pipeline_revalidate(pp_pipeline* pipeline, pp_map* target /* NULL: the pipeline's map as it is now */, int32_t n, const uint64_t* tickets,
+	pp_revalidate_result* results_host);
+/* The same kernel over the first n_queries queries of the planner's last batch (identity slots), on the planner's stream, with the planner's
+ * footprint if it has one (pp_planner_set_footprint).  target == NULL: the planner's own map.  PP_ERR_INVALID: n_queries < 0 or beyond the
+ * last batch; a target of another context or without a distance grid; a planner that is a pipeline's buffer set (pp_pipeline_revalidate
+ * knows which of its slots are held). */
+int pp_planner_revalidate(pp_planner* planner, pp_map* target /* NULL: own map */, int32_t n_queries, pp_revalidate_result* results_host);
 /* Diagnostics: waves of the search grid that are alive right now (a blocking device-to-host copy; -1 on error). */
 int pp_pipeline_alive_waves(pp_pipeline* pipeline);
 pp_planner* pp_pipeline_planner(pp_pipeline* pipeline);           /* the buffer set: set_nonholo_table, set_primitives, get_path(slot), ... */

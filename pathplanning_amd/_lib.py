@@ -81,6 +81,12 @@ class PostResult(C.Structure):
     _fields_ = [("n_points", C.c_int32), ("smoothing_status", C.c_int32), ("iterations", C.c_int32), ("reserved", C.c_int32), ("length", C.c_double)]
 
 
+class RevalidateResult(C.Structure):
+    """pp_revalidate_result: status 0 still valid, 1 an edge is blocked, 2 only the goal pose fails, -1 no plan, -4 path beyond the path capacity"""
+    _fields_ = [("status", C.c_int32), ("n_edges", C.c_int32), ("blocked_edge", C.c_int32), ("blocked_ratio", C.c_float), ("valid_length", C.c_double),
+                ("length", C.c_double)]
+
+
 class GridResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("n_path", C.c_int32), ("n_expanded", C.c_int32), ("n_expanded_reverse", C.c_int32), ("cost", C.c_double)]
 
@@ -203,6 +209,8 @@ def load():
     L.pp_pipeline_slot_of.argtypes = [vp, C.c_uint64]
     L.pp_pipeline_postprocess.argtypes = [vp, C.c_int32, vp, C.c_float, vp, C.c_int32, vp]
     L.pp_pipeline_get_processed_paths.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, C.c_int32]
+    L.pp_pipeline_revalidate.argtypes = [vp, vp, C.c_int32, vp, vp]
+    L.pp_planner_revalidate.argtypes = [vp, vp, C.c_int32, vp]
     L.pp_pipeline_timings.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.pp_pipeline_backlog.argtypes = [vp, vp, vp]
     L.pp_pipeline_planner.argtypes = [vp]

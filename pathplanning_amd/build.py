@@ -95,6 +95,18 @@ def build_pipeline_postprocess_test(verbose=True):
     return out
 
 
+def build_pipeline_revalidate_test(verbose=True):
+    """tests/cpp/test_pipeline_revalidate.cpp: Revalidate(tickets) of HybridAStarPipeline against the plan's path objects marched one by one (run on the GPU box)."""
+    build()
+    out = os.path.join(LIB_DIR, "test_pipeline_revalidate")
+    src = os.path.join(HERE, "..", "tests", "cpp", "test_pipeline_revalidate.cpp")
+    cmd = ["g++", "-O2", "-std=c++17", src, "-o", out, "-L" + LIB_DIR, "-lpphip", "-Wl,-rpath,$ORIGIN"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return out
+
+
 def build_row_test(verbose=True):
     """tests/cpp/test_row_primitives.hip: GPU self-test of the DPP row primitives (run on the GPU box)."""
     out = os.path.join(LIB_DIR, "test_row_primitives")
@@ -115,4 +127,5 @@ if __name__ == "__main__":
     print(build_plugin_test())
     print(build_pipeline_footprint_test())
     print(build_pipeline_postprocess_test())
+    print(build_pipeline_revalidate_test())
     print(build_row_test())

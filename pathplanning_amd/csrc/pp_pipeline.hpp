@@ -220,6 +220,10 @@ struct pp_pipeline {
 	int postPoints = 0;     // the last call's max_points: its sample limit and the buffers' per-plan stride
 	std::vector<pp_post_result> postHost;                  // the last call's results, by compact index
 	std::unordered_map<uint64_t, int32_t> postIndexOfTicket; // tickets of the last call that are still held -> compact index
+	// pp_pipeline_revalidate (k_revalidate_tickets): the slot list and the results of a call, by compact index; revRows = tickets they hold
+	pph::Dev<int32_t> revSlots;
+	pph::Dev<pp_revalidate_result> revOut;
+	int revRows = 0;
 	int nWf = 2;      // wavefront streams in use: consecutive submissions' launches overlap (the tail of one under the head of the next)
 	int wfBlocks = 0; // workgroups per wavefront launch (<= the resident number): the wavefront kernel's share of the chip
 };
@@ -566,6 +570,16 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 		if (e != hipSuccess) {
 			free_pipeline(P);
 			return pph::hip_fail(e, "pipeline post-processing kernel warm-up (scratch allocation)");
+		}
+		// ... and of k_revalidate_tickets, which pp_pipeline_revalidate launches on the same stream
+		hipLaunchKernelGGL(k_revalidate_tickets, dim3(1), dim3(64), 0, P->ctlStream, pl->args, Footprint {}, 0, (const int32_t*)nullptr, (const PathRec*)nullptr,
+			(const RsLogEntry*)nullptr, (const DevResult*)nullptr, (pp_revalidate_result*)nullptr);
+		e = hipGetLastError();
+		if (e == hipSuccess)
+			e = hipStreamSynchronize(P->ctlStream);
+		if (e != hipSuccess) {
+			free_pipeline(P);
+			return pph::hip_fail(e, "pipeline re-validation kernel warm-up (scratch allocation)");
 		}
 	}
 	std::memset(P->done, 0, ring * sizeof(PipeDone));
@@ -1255,6 +1269,84 @@ int pp_pipeline_get_processed_paths(pp_pipeline* P, int32_t n, const uint64_t* t
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	if (release)
 		return pp_pipeline_release(P, n, tickets);
+	return PP_OK;
+}
+
+/// Are the plans of n completed, held queries still collision-free on `target` as it is now (include/pp_hip.h)?  Legal with queries in flight for the
+/// reasons given at pp_pipeline_postprocess: a held slot's records were published before its completion record and nothing writes them until the
+/// slot is released.  The launch goes on the control stream with a COPY of the search arguments whose map view is the target's view of this moment
+/// (every writer of a map's grids has drained the map's stream before it returned, so the view is current); the buffer set's `args` is not written
+/// and only the control stream is synchronised.  Nothing of the last post-processing call is touched.
+int pp_pipeline_revalidate(pp_pipeline* P, pp_map* target, int32_t n, const uint64_t* tickets, pp_revalidate_result* results_host)
+{
+	if (!P) {
+		set_error("null pipeline");
+		return PP_ERR_INVALID;
+	}
+	if (P->dead) {
+		set_error("the pipeline failed earlier and must be destroyed");
+		return PP_ERR_HIP;
+	}
+	if (n < 0 || n > P->capacity || (n > 0 && !tickets)) {
+		set_error("invalid arguments (0 <= n <= capacity = " + std::to_string(P->capacity) + ", got n = " + std::to_string(n) + ")");
+		return PP_ERR_INVALID;
+	}
+	pp_planner* pl = P->pl;
+	pp_map* const map = target ? target : pl->map;
+	if (int rc = revalidate_check_target(pl->map, map))
+		return rc;
+	std::vector<int32_t> slots((size_t)n);
+	{
+		std::unordered_map<uint64_t, int32_t> seen;
+		for (int i = 0; i < n; i++) {
+			auto it = P->slotOfTicket.find(tickets[i]);
+			if (it == P->slotOfTicket.end()) {
+				set_error("ticket " + std::to_string(tickets[i]) + " is unknown or already released");
+				return PP_ERR_INVALID;
+			}
+			if (P->slotState[(size_t)it->second] != 2) {
+				set_error("ticket " + std::to_string(tickets[i]) + " is still in flight (or was not polled with release = 0): only completed, held queries are re-validated");
+				return PP_ERR_INVALID;
+			}
+			if (!seen.emplace(tickets[i], i).second) {
+				set_error("ticket " + std::to_string(tickets[i]) + " is given twice");
+				return PP_ERR_INVALID;
+			}
+			slots[(size_t)i] = it->second;
+		}
+	}
+	if (n == 0)
+		return PP_OK;
+	PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
+	const bool idle = P->nSubmitted == P->doneHead; // (see pp_pipeline_postprocess: nothing is freed beside queries in flight)
+	if (idle)
+		P->postParked.clear();
+	if (P->revRows < n) {
+		P->revRows = 0;
+		auto park = [&](pph::DeviceMem& b) {
+			if (!idle && b.get())
+				P->postParked.emplace_back(std::move(b));
+		};
+		park(P->revSlots), park(P->revOut);
+		PP_HIP_TRY(P->revSlots.alloc((size_t)n * 4));
+		PP_HIP_TRY(P->revOut.alloc((size_t)n * sizeof(pp_revalidate_result)));
+		P->revRows = n;
+	}
+	SearchArgs args = pl->args; // a copy: the top-up launches of the search grid read pl->args
+	args.m = map->view();       // the target as it is NOW
+	Footprint foot {};          // n = 0: the point validator
+	if (P->footprint)
+		foot = P->footprint->fp;
+	hipStream_t s = P->ctlStream;
+	PP_HIP_TRY(hipMemcpyAsync(P->revSlots, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, s)); // (pageable source: staged before the call returns)
+	hipLaunchKernelGGL(k_revalidate_tickets, dim3(n), dim3(64), 0, s, args, foot, n, P->revSlots.get(), pl->paths.get(), pl->rsLogs.get(), pl->results.get(), P->revOut.get());
+	PP_HIP_TRY(hipGetLastError());
+	std::vector<pp_revalidate_result> host((size_t)n);
+	PP_HIP_TRY(hipMemcpyAsync(host.data(), P->revOut, (size_t)n * sizeof(pp_revalidate_result), hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipStreamSynchronize(s));
+	if (results_host)
+		for (int i = 0; i < n; i++)
+			results_host[i] = host[(size_t)i];
 	return PP_OK;
 }
 

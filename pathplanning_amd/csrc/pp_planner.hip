@@ -296,6 +296,8 @@ struct PipeView {
 #define PP_POST_TICKETS 1
 #include "pp_postprocess.hpp"
 #undef PP_POST_TICKETS
+// re-validation of plans against a changed map (one wave per plan; PostEdge / load_edge of the file above)
+#include "pp_revalidate.hpp"
 
 } // namespace
 
@@ -359,6 +361,7 @@ struct pp_planner {
 	int postMaxPoints = 0, postDone = 0; // capacity of the buffers per query; queries of the last call
 	int postPoints = 0; // the last call's max_points: its sample limit and the buffers' per-query stride
 	std::vector<pp_post_result> hostPost;
+	pph::Dev<pp_revalidate_result> revOut; // [maxBatch], allocated at the first pp_planner_revalidate
 };
 
 namespace {
@@ -449,6 +452,11 @@ int warm_up_kernels(pp_planner* p, pp_map* map)
 			(const uint32_t*)nullptr, (const uint32_t*)nullptr, PostBuffers {});
 		e = hipGetLastError();
 	}
+	if (e == hipSuccess) {
+		hipLaunchKernelGGL(k_revalidate_tickets, dim3(1), dim3(64), 0, s, p->args, Footprint {}, 0, (const int32_t*)nullptr, (const PathRec*)nullptr, (const RsLogEntry*)nullptr,
+			(const DevResult*)nullptr, (pp_revalidate_result*)nullptr);
+		e = hipGetLastError();
+	}
 	if (e == hipSuccess)
 		e = hipStreamSynchronize(s);
 	if (e != hipSuccess)
@@ -479,6 +487,20 @@ int primitives_from_deltas(pp_planner* p)
 		T.backward[2 * d] = 0;
 		T.kappa[2 * d + 1] = DthetaDdist;
 		T.backward[2 * d + 1] = 1;
+	}
+	return PP_OK;
+}
+
+/// the map a plan is re-validated against (pp_planner_revalidate, pp_pipeline_revalidate): of the owner's context, with a distance grid
+int revalidate_check_target(const pp_map* own, const pp_map* target)
+{
+	if (target->ctx != own->ctx) {
+		set_error("the target map belongs to another context than the planner's map");
+		return PP_ERR_INVALID;
+	}
+	if (!target->dist) {
+		set_error("the target map has no distance grid: pp_map_upload_dist2, pp_map_upload_distance or pp_map_update_gvd first");
+		return PP_ERR_INVALID;
 	}
 	return PP_OK;
 }
@@ -1330,6 +1352,41 @@ int pp_planner_get_processed_path(pp_planner* planner, int32_t q, double* sample
 		PP_HIP_TRY(hipMemcpy(cusp_host, planner->postCusp + (size_t)q * cap, n, hipMemcpyDeviceToHost));
 	if (smoothed_host)
 		PP_HIP_TRY(hipMemcpy(smoothed_host, planner->postSmoothed + (size_t)q * cap * 3, n * 24, hipMemcpyDeviceToHost));
+	return PP_OK;
+}
+
+int pp_planner_revalidate(pp_planner* planner, pp_map* target, int32_t n_queries, pp_revalidate_result* results_host)
+{
+	if (!planner || n_queries < 0 || n_queries > planner->lastBatch) {
+		set_error("invalid arguments (0 <= n_queries <= last batch)");
+		return PP_ERR_INVALID;
+	}
+	if (planner->pipelineOwned) {
+		set_error("this planner is a pipeline's buffer set: pp_pipeline_revalidate re-validates its held tickets");
+		return PP_ERR_INVALID;
+	}
+	pp_map* const map = target ? target : planner->map;
+	if (int rc = revalidate_check_target(planner->map, map))
+		return rc;
+	if (n_queries == 0)
+		return PP_OK;
+	PP_HIP_TRY(hipSetDevice(planner->map->ctx->device));
+	hipStream_t s = planner->map->ctx->stream;
+	PP_HIP_TRY(planner->revOut.ensure((size_t)planner->maxBatch * sizeof(pp_revalidate_result)));
+	SearchArgs args = planner->args; // a copy: the planner's own arguments keep its own map's view
+	args.m = map->view();
+	Footprint foot {}; // n = 0: the point validator
+	if (planner->footprint)
+		foot = planner->footprint->fp;
+	hipLaunchKernelGGL(k_revalidate_tickets, dim3(n_queries), dim3(64), 0, s, args, foot, n_queries, (const int32_t*)nullptr, planner->paths.get(), planner->rsLogs.get(),
+		planner->results.get(), planner->revOut.get());
+	PP_HIP_TRY(hipGetLastError());
+	std::vector<pp_revalidate_result> host((size_t)n_queries);
+	PP_HIP_TRY(hipMemcpyAsync(host.data(), planner->revOut, (size_t)n_queries * sizeof(pp_revalidate_result), hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipStreamSynchronize(s));
+	if (results_host)
+		for (int i = 0; i < n_queries; i++)
+			results_host[i] = host[(size_t)i];
 	return PP_OK;
 }
 

@@ -1009,6 +1009,7 @@ struct RRTStarParameters {
 /// Poll(out, max, hold = true) keeps the completed queries' slots: GetGraphSearchPath(ticket) is their graph-search nodes, PostProcess(tickets)
 /// samples and smooths them on the device (pp_pipeline_postprocess, legal while others are in flight), GetPath(ticket) is then what
 /// HybridAStar::GetPath() returns for that query, GetSmoothingStatus(ticket) its Stats::smoothingStatus; Release(tickets) frees the slots.
+/// Revalidate(tickets) asks whether held plans are still collision-free after the map changed (pp_pipeline_revalidate).
 class HybridAStarPipeline {
 public:
 	struct Result {
@@ -1156,6 +1157,47 @@ public:
 			const std::vector<Pose2d>& from = r.smoothing_status >= 0 ? smoothed : sampled;
 			h.path.assign(from.begin() + (size_t)i * (size_t)cap, from.begin() + (size_t)i * (size_t)cap + (size_t)r.n_points);
 		}
+	}
+	/// What Revalidate says about one held plan (pp_revalidate_result)
+	struct Revalidation {
+		enum class Verdict { Valid = 0, EdgeBlocked = 1, GoalBlocked = 2, NoPlan = -1, PathTooLong = -4 };
+		Verdict verdict = Verdict::NoPlan;
+		int numEdges = 0;          // nodes of the graph-search solution - 1
+		int blockedEdge = 0;       // EdgeBlocked: the first blocked edge, root first, from 1 (edge e joins nodes e-1 and e); else 0
+		float blockedRatio = 1.0f; // EdgeBlocked: how far along that edge the march got (IsPathValid's last valid ratio); else 1
+		double validLength = 0.0;  // metres drivable from the start
+		double length = 0.0;       // length of the composite path
+		bool StillValid() const { return verdict == Verdict::Valid; }
+	};
+	/// Are the graph-search plans of held queries still collision-free on a map as it is NOW (pp_pipeline_revalidate)?  `against`: the validator
+	/// whose map and tunables the plans are marched against -- nullptr: the pipeline's own, with whatever has been written to its map since the
+	/// plans were made; another validator's map may have any geometry.  Obstacles written since the fields were last built are built in first
+	/// (GVD::Update).  Legal while other queries are in flight (then the pipeline's footprint stays what it is; with none in flight the
+	/// validator's current footprint is taken, as in PostProcess).  Post-processed paths are not touched.
+	std::vector<Revalidation> Revalidate(const std::vector<uint64_t>& tickets, const Ref<StateValidatorOccupancyMap>& against = nullptr)
+	{
+		for (uint64_t t : tickets)
+			HeldOf(t); // (throws for a ticket that is not held)
+		std::vector<Revalidation> out(tickets.size());
+		if (tickets.empty() || !m_pipe)
+			return out;
+		const Ref<StateValidatorOccupancyMap>& v = against ? against : m_validator;
+		if (v->GetOccupancyMap()->FieldsOutdated())
+			v->GetOccupancyMap()->BuildFields(20.0f, 30.0f);
+		pp_map* const target = v->Device(); // pushes host-side grids and the validator's tunables
+		if (InFlight() == 0)
+			SyncFootprint();
+		std::vector<pp_revalidate_result> r(tickets.size());
+		ppCheck(pp_pipeline_revalidate(m_pipe, target, (int32_t)tickets.size(), tickets.data(), r.data()));
+		for (size_t i = 0; i < r.size(); i++) {
+			out[i].verdict = (Revalidation::Verdict)r[i].status;
+			out[i].numEdges = r[i].n_edges;
+			out[i].blockedEdge = r[i].blocked_edge;
+			out[i].blockedRatio = r[i].blocked_ratio;
+			out[i].validLength = r[i].valid_length;
+			out[i].length = r[i].length;
+		}
+		return out;
 	}
 	/// HybridAStar::GetPath() of a held query: after PostProcess the sampled and, when the smoother succeeded, smoothed path; before it the
 	/// graph-search nodes

@@ -403,6 +403,16 @@ PYBIND11_MODULE(pyplanning, m)
 			},
 			py::arg("max_results") = 4096, py::arg("hold") = false)
 		.def("post_process", &HybridAStarPipeline::PostProcess, py::arg("tickets"), py::arg("path_interpolation") = 0.1f)
+		// held plans against a map as it is now: (status, n_edges, blocked_edge, blocked_ratio, valid_length, length) per ticket; status 0 still valid,
+		// 1 an edge is blocked, 2 only the goal pose fails, -1 no plan.  validator=None: the pipeline's own validator and map
+		.def("revalidate",
+			[](HybridAStarPipeline& h, const std::vector<uint64_t>& tickets, const Ref<StateValidatorOccupancyMap>& validator) {
+				py::list out;
+				for (const auto& r : h.Revalidate(tickets, validator))
+					out.append(py::make_tuple((int)r.verdict, r.numEdges, r.blockedEdge, r.blockedRatio, r.validLength, r.length));
+				return out;
+			},
+			py::arg("tickets"), py::arg("validator") = Ref<StateValidatorOccupancyMap>())
 		.def("get_path", &HybridAStarPipeline::GetPath, py::arg("ticket"))
 		.def("get_graph_search_path", &HybridAStarPipeline::GetGraphSearchPath, py::arg("ticket"))
 		.def("get_smoothing_status", &HybridAStarPipeline::GetSmoothingStatus, py::arg("ticket"))

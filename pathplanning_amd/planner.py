@@ -12,7 +12,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import RS_PATH_DTYPE, FootprintDisc, HybridParams, MapDesc, PostResult, QueryResult, SmootherParams, check, ptr
+from ._lib import RS_PATH_DTYPE, FootprintDisc, HybridParams, MapDesc, PostResult, QueryResult, RevalidateResult, SmootherParams, check, ptr
 
 
 class Status:
@@ -680,6 +680,16 @@ class HybridAStarBatch:
         return dict(sampled=sampled, cusp=cusp.astype(bool), smoothed=smoothed, status=r.smoothing_status, iterations=r.iterations, length=r.length,
                     path=smoothed if r.smoothing_status >= 0 else sampled)
 
+    def revalidate(self, n_queries=None, map_set=None):
+        """Are the plans of the first n queries of the last batch still collision-free on `map_set` (an OccupancyMapSet of the same
+        context; None: the planner's own map) as it is now (pp_planner_revalidate)?  Every edge is marched as the search marched it, with
+        the planner's footprint if it has one, then the last pose gets the state check.  Returns one RevalidateResult per query
+        (status, n_edges, blocked_edge, blocked_ratio, valid_length, length)."""
+        n = len(self._results) if n_queries is None else int(n_queries)
+        out = (RevalidateResult * max(n, 1))()
+        check(self.lib.pp_planner_revalidate(self.h, map_set.h if map_set is not None else None, n, out))
+        return list(out)[:n]
+
     def certify_lattice(self, q):
         """SURVEY 7.3 H2 as a contract (pp_planner_certify_lattice): created nodes and logged lattice-line children of query q recomputed on
         the host with glibc; returns (checked, cell mismatches, unverified events, largest pose difference).  mismatches == unverified == 0
@@ -978,6 +988,19 @@ class HybridAStarPipeline:
                 self._held.pop(int(x), None)
                 post.pop(int(x), None)
         return out
+
+    def revalidate(self, tickets, map_set=None):
+        """Are the plans of the completed, HELD queries `tickets` still collision-free on `map_set` (an OccupancyMapSet of the same
+        context, any geometry; None: the pipeline's own map) as it is NOW (pp_pipeline_revalidate)?  Legal while other queries are in
+        flight.  Every edge is marched as the search marched it -- with the pipeline's footprint if one is set, else the point validator with
+        the target map's tunables -- then the last pose gets the state check.  Returns one RevalidateResult per ticket, in that order:
+        status 0 valid, 1 blocked at `blocked_edge` (root first, from 1) after `blocked_ratio` of it, 2 only the goal pose fails, -1 no
+        plan; valid_length = metres drivable from the start.  The results of the last postprocess() call stay readable.  Raises PPError,
+        with nothing launched, for a ticket that is unknown, released, in flight or given twice."""
+        t = np.ascontiguousarray(tickets, dtype=np.uint64).reshape(-1)
+        out = (RevalidateResult * max(len(t), 1))()
+        check(self.lib.pp_pipeline_revalidate(self.h, map_set.h if map_set is not None else None, len(t), ptr(t), out))
+        return list(out)[:len(t)]
 
     def get_expanded_of(self, ticket):
         """expansion sequence (log_expansions=True) of a completed query polled with release=False"""
