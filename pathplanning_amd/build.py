@@ -107,6 +107,21 @@ def build_pipeline_revalidate_test(verbose=True):
     return out
 
 
+def build_ticket_table_test(verbose=True):
+    """tests/cpp/test_ticket_table.cpp: the pipeline's slot and ticket bookkeeping (csrc/pp_ticket_table.hpp) alone, on the CPU, under the address and
+    undefined-behaviour sanitizers."""
+    os.makedirs(LIB_DIR, exist_ok=True)
+    out = os.path.join(LIB_DIR, "test_ticket_table")
+    src = os.path.join(HERE, "..", "tests", "cpp", "test_ticket_table.cpp")
+    if os.path.exists(out) and os.path.getmtime(out) > max(os.path.getmtime(src), os.path.getmtime(os.path.join(CSRC, "pp_ticket_table.hpp"))):
+        return out
+    cmd = ["g++", "-std=c++17", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC, src, "-o", out]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return out
+
+
 def build_row_test(verbose=True):
     """tests/cpp/test_row_primitives.hip: GPU self-test of the DPP row primitives (run on the GPU box)."""
     out = os.path.join(LIB_DIR, "test_row_primitives")
@@ -128,4 +143,5 @@ if __name__ == "__main__":
     print(build_pipeline_footprint_test())
     print(build_pipeline_postprocess_test())
     print(build_pipeline_revalidate_test())
+    print(build_ticket_table_test())
     print(build_row_test())

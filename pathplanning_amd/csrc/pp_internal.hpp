@@ -9,6 +9,7 @@
 #include "../../include/pp_hip.h"
 #include "pp_device.hpp"
 #include "pp_footprint_device.hpp"
+#include "pp_ticket_table.hpp"
 
 namespace pph {
 
@@ -136,9 +137,7 @@ int wavefront_resident_blocks();
 hipError_t warm_up_wavefront(hipStream_t s, const ppd::MapView& m, int32_t* ctlDev);
 /// Pipeline use of the wavefront kernel (pp_pipeline.hpp): entry i of a launch works on field slot slotList[i] (goal pose and output
 /// field are indexed by the slot), and every finished slot is appended to the ready ring the search grid consumes.
-constexpr int kSlotBits = 20;                 // pipeline list / ring entries: field slot in the low bits, the slot's generation above
-constexpr uint32_t kSlotMask = (1u << kSlotBits) - 1u;
-constexpr uint32_t kGenMask = (1u << (31 - kSlotBits)) - 1u; // (entries are non-negative int32)
+/// (list and ring entries are slot | generation << kSlotBits: pp_ticket_table.hpp)
 struct WavefrontPublish {
 	const int32_t* slotList = nullptr;
 	unsigned long long* readyTail = nullptr; // entries appended so far (absolute)

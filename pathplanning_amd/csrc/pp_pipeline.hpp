@@ -185,12 +185,8 @@ struct pp_pipeline {
 	pph::Event evIngest, evCtl;
 	int nextWf = 0, nextSearch = 0;
 	// host bookkeeping
-	std::vector<int32_t> freeSlots;
-	std::vector<uint64_t> ticketOfSlot;
-	std::vector<uint8_t> slotState; // 0 free, 1 in flight, 2 completed and held for the caller
-	std::vector<uint32_t> slotGen;  // times the slot has been filled (mod kGenMask + 1, never 0): tags its list / ring entries and its claim word
-	std::unordered_map<uint64_t, int32_t> slotOfTicket;
-	unsigned long long nSubmitted = 0, doneHead = 0, nTickets = 0;
+	pph::TicketTable tickets; // the slots (free, in flight, held) and the tickets that name them
+	unsigned long long nSubmitted = 0, doneHead = 0;
 	std::chrono::steady_clock::time_point lastLaunch {};
 	// launch durations (HIP events on the streams the kernels are launched on), harvested by pp_pipeline_poll
 	struct Timed {
@@ -214,16 +210,17 @@ struct pp_pipeline {
 	pph::Dev<pp_post_result> postOut;
 	pph::Dev<int32_t> postSlots;
 	size_t postSamples = 0; // samples the five sample buffers hold; 0 until every one of them exists
-	int postRows = 0;       // plans postEdgeEnd / postOut / postSlots hold
-	std::vector<pph::DeviceMem> postParked; // buffers outgrown while queries were in flight: hipFree waits for the whole device (the persistent grid
-	                                        // included), so they are kept until a call finds nothing in flight (or the pipeline goes)
+	size_t postRows = 0;    // plans postEdgeEnd / postOut / postSlots hold
+	std::vector<pph::DeviceMem> heldParked; // buffers of the held-plan services (post-processing, re-validation) outgrown while queries were in flight: hipFree
+	                                        // waits for the whole device (the persistent grid included), so they are kept until a call finds nothing in flight
+	                                        // (or the pipeline goes): pipe_grow
 	int postPoints = 0;     // the last call's max_points: its sample limit and the buffers' per-plan stride
 	std::vector<pp_post_result> postHost;                  // the last call's results, by compact index
 	std::unordered_map<uint64_t, int32_t> postIndexOfTicket; // tickets of the last call that are still held -> compact index
 	// pp_pipeline_revalidate (k_revalidate_tickets): the slot list and the results of a call, by compact index; revRows = tickets they hold
 	pph::Dev<int32_t> revSlots;
 	pph::Dev<pp_revalidate_result> revOut;
-	int revRows = 0;
+	size_t revRows = 0;
 	int nWf = 2;      // wavefront streams in use: consecutive submissions' launches overlap (the tail of one under the head of the next)
 	int wfBlocks = 0; // workgroups per wavefront launch (<= the resident number): the wavefront kernel's share of the chip
 };
@@ -329,19 +326,26 @@ hipError_t pipe_dispatch_search(pp_pipeline* P, hipStream_t s, const SearchArgs&
 	return launch_search_rows<true>(pl, s, args, slots, nullptr, pipe_view(P));
 }
 
+/// An 8-byte value on its way to a field of PipeCtl: an asynchronous copy on the control stream out of the ring of 64 pinned staging words.  The stream is
+/// drained at every 32nd copy, so an entry never comes round while its copy is in flight, however long the caller goes without synchronising (the top-up
+/// launches of a long wait between submissions).  Round 3's crash under rocprofv3 --pmc was an UNBOUNDED stream of such small asynchronous copies issued
+/// from the poll path: DESIGN.md 4.10
+hipError_t pipe_stage_ctl(pp_pipeline* P, unsigned long long* field, unsigned long long value)
+{
+	if ((P->submittedStagePos & 31) == 31)
+		if (const hipError_t e = hipStreamSynchronize(P->ctlStream))
+			return e;
+	unsigned long long* const src = P->submittedStage + (P->submittedStagePos++ & 63);
+	*src = value;
+	return hipMemcpyAsync(field, src, 8, hipMemcpyHostToDevice, P->ctlStream);
+}
+
 /// the submission count goes to the device on the control stream, then a launch of the whole grid behind it: waves whose index is
 /// free start working, the others leave at once
 int pipe_launch_search(pp_pipeline* P)
 {
 	pp_planner* pl = P->pl;
-	// (the staging ring has 64 entries and the copies are asynchronous: the control stream is drained before an entry can come round again --
-	// every submission synchronises it anyway; this bounds the top-up launches of a long wait between submissions.  Round 3's crash under
-	// rocprofv3 --pmc was an UNBOUNDED stream of such small asynchronous copies issued from the poll path: DESIGN.md 4.10)
-	if ((P->submittedStagePos & 31) == 31)
-		PP_HIP_TRY(hipStreamSynchronize(P->ctlStream));
-	unsigned long long* const src = P->submittedStage + (P->submittedStagePos++ & 63);
-	*src = P->nSubmitted;
-	PP_HIP_TRY(hipMemcpyAsync(&P->ctl->nSubmitted, src, 8, hipMemcpyHostToDevice, P->ctlStream));
+	PP_HIP_TRY(pipe_stage_ctl(P, &P->ctl->nSubmitted, P->nSubmitted));
 	PP_HIP_TRY(hipEventRecord(P->evCtl, P->ctlStream));
 	// a launch starts only when the previous launch on its stream has ended, i.e. when every wave of that launch has left: the top-up goes to
 	// a stream that is idle; if every stream still carries live waves there is nothing to top up through (the waves alive keep taking work)
@@ -364,6 +368,98 @@ int pipe_launch_search(pp_pipeline* P)
 	PP_HIP_TRY(pipe_dispatch_search(P, s, pl->args));
 	timed_done(P, s, tm);
 	P->lastLaunch = std::chrono::steady_clock::now();
+	return PP_OK;
+}
+
+/// a submission that failed half way, or a field that could not be built: the pipeline's accounting is no longer trustworthy and every later call is refused
+bool pipe_dead(const pp_pipeline* P)
+{
+	if (P->dead)
+		set_error("the pipeline failed earlier and must be destroyed");
+	return P->dead;
+}
+/// ... for the entries that name a null handle in their refusal
+int pipe_check(const pp_pipeline* P)
+{
+	if (!P) {
+		set_error("null pipeline");
+		return PP_ERR_INVALID;
+	}
+	return pipe_dead(P) ? PP_ERR_HIP : PP_OK;
+}
+
+// ---- held plans by ticket.  A service that works on held plans (post-processing, re-validation, the next one) resolves its tickets with pipe_resolve, sizes its
+// buffers with pipe_grow and launches through pipe_run_held; whatever it keeps per ticket is dropped in pipe_release, the one route by which a slot is freed.
+
+/// the slots of n held tickets (pph::TicketTable::resolve), or its refusal as the library's error
+int pipe_resolve(const pp_pipeline* P, int n, const uint64_t* tickets, const char* verb, bool distinct, std::vector<int32_t>& slots)
+{
+	pph::TicketTable::Resolved r = P->tickets.resolve(n, tickets, verb, distinct);
+	slots.swap(r.slots);
+	if (r.error.empty())
+		return PP_OK;
+	set_error(r.error);
+	return PP_ERR_INVALID;
+}
+/// ... for the entries that take their tickets one by one and have found one that is not held
+int pipe_refuse(const pp_pipeline* P, uint64_t ticket, const char* verb)
+{
+	std::vector<int32_t> none;
+	if (pipe_resolve(P, 1, &ticket, verb, false, none) == PP_OK) // (cannot be: the caller found the ticket not held)
+		set_error("ticket " + std::to_string(ticket) + " is not a completed, held query");
+	return PP_ERR_INVALID;
+}
+
+/// A held ticket's slot becomes free, and the last post-processing call's results for it go with it (a ticket polled with release != 0 has none: every route
+/// that frees a slot says so all the same).  false: the ticket is not held
+bool pipe_release(pp_pipeline* P, uint64_t ticket)
+{
+	P->postIndexOfTicket.erase(ticket);
+	return P->tickets.release(ticket);
+}
+
+/// Buffers of a held-plan service that hold `capacity` units are made to hold `wanted`.  Nothing is freed while queries are in flight: hipFree waits for every
+/// stream of the device, i.e. for the searches in flight and the grid's idle waves.  A buffer that has to grow then is parked instead, and the parked ones go
+/// when a call finds the pipeline idle.  The capacity is 0 until every buffer exists again: a failed allocation must not leave a stale capacity behind.
+hipError_t pipe_grow(pp_pipeline* P, size_t& capacity, size_t wanted, std::initializer_list<std::pair<pph::DeviceMem*, size_t>> buffers)
+{
+	const bool idle = P->nSubmitted == P->doneHead;
+	if (idle)
+		P->heldParked.clear();
+	if (capacity >= wanted)
+		return hipSuccess;
+	capacity = 0;
+	for (const auto& [buffer, bytes] : buffers) {
+		if (!idle && buffer->get())
+			P->heldParked.emplace_back(std::move(*buffer));
+		if (const hipError_t e = buffer->alloc(bytes))
+			return e;
+	}
+	capacity = wanted;
+	return hipSuccess;
+}
+
+/// One kernel over the held plans in `slots`, and its n result records back.  Legal with queries in flight: the row that finished a slot wrote its path records,
+/// Reeds-Shepp log and result record BEFORE its completion record (finish() in pp_planner_rows.hpp), the host saw that record with an acquire load in
+/// pp_pipeline_poll, and nothing writes the slot again until it is released and refilled.  The launch goes on the control stream with a COPY of the search arguments
+/// under the caller's map view -- the buffer set's `args`, which the grid's top-up launches read, is not written -- and with the pipeline's footprint (or none:
+/// Footprint::n = 0); only the control stream is synchronised.  launch(args, footprint, n, slotsDev) dispatches the kernel on P->ctlStream.
+template <typename Rec, typename Launch>
+int pipe_run_held(pp_pipeline* P, const std::vector<int32_t>& slots, const ppd::MapView& view, int32_t* slotsDev, const Rec* outDev, std::vector<Rec>& host, Launch launch)
+{
+	const int n = (int)slots.size();
+	SearchArgs args = P->pl->args;
+	args.m = view;
+	Footprint foot {};
+	if (P->footprint)
+		foot = P->footprint->fp;
+	hipStream_t s = P->ctlStream;
+	PP_HIP_TRY(hipMemcpyAsync(slotsDev, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, s)); // (pageable source: staged before the call returns)
+	launch(args, foot, n, (const int32_t*)slotsDev);
+	PP_HIP_TRY(hipGetLastError());
+	host.resize((size_t)n);
+	PP_HIP_TRY(hipMemcpyAsync(host.data(), outDev, (size_t)n * sizeof(Rec), hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipStreamSynchronize(s));
 	return PP_OK;
 }
 
@@ -393,17 +489,19 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 		ring <<= 1;
 	P->readyMask = P->doneMask = ring - 1;
 	P->slotListCap = (size_t)capacity * 4;
-	hipError_t e = P->ctl.alloc(sizeof(PipeCtl));
-	if (e == hipSuccess)
-		e = P->ready.alloc(ring * 8);
-	if (e == hipSuccess)
-		e = P->waveAlive.alloc((size_t)P->waves * 4);
-	if (e == hipSuccess)
-		e = P->slotLists.alloc(P->slotListCap * 4);
-	if (e == hipSuccess)
-		e = P->urgent.alloc(ring * 8);
-	if (e == hipSuccess)
-		e = P->claimed.alloc((size_t)capacity * 4);
+	// every allocation, memset and stream of the pipeline, in order; the first failure skips the rest and is reported once, below
+	hipError_t e = hipSuccess;
+#define PIPE_TRY(expr)         \
+	do {                       \
+		if (e == hipSuccess)   \
+			e = (expr);        \
+	} while (0)
+	PIPE_TRY(P->ctl.alloc(sizeof(PipeCtl)));
+	PIPE_TRY(P->ready.alloc(ring * 8));
+	PIPE_TRY(P->waveAlive.alloc((size_t)P->waves * 4));
+	PIPE_TRY(P->slotLists.alloc(P->slotListCap * 4));
+	PIPE_TRY(P->urgent.alloc(ring * 8));
+	PIPE_TRY(P->claimed.alloc((size_t)capacity * 4));
 	if (const char* v = getenv("PP_PIPE_URGENT_CLEARANCE")) { // [m]; 0 switches the urgent ring off
 		const double x = strtod(v, nullptr);
 		if (x >= 0.0 && x < 1.0e6)
@@ -414,34 +512,24 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 		if (x >= 1 && x <= kPipeWavefrontStreams)
 			P->nWf = (int)x;
 	}
-	for (int i = 0; i < P->nWf && e == hipSuccess; i++) {
-		e = P->wfWorkspace[i].alloc((size_t)pl->wfBytesPerSlot * pl->wfSlots);
+	for (int i = 0; i < P->nWf; i++) {
+		PIPE_TRY(P->wfWorkspace[i].alloc((size_t)pl->wfBytesPerSlot * pl->wfSlots));
 		if (const size_t qw = pph::wavefront_tiles_queue_words(pl->map->desc.rows, pl->map->desc.cols)) {
 			P->tilesQueueWaves = 2048; // (256 CUs x 8 waves of a pack)
-			if (e == hipSuccess)
-				e = P->tilesQueue[i].alloc(qw * 4 * (size_t)P->tilesQueueWaves);
+			PIPE_TRY(P->tilesQueue[i].alloc(qw * 4 * (size_t)P->tilesQueueWaves));
 		}
-		if (e == hipSuccess)
-			e = P->wfCtl[i].alloc(64);
-		if (e == hipSuccess)
-			e = hipMemset(P->wfCtl[i], 0, 64);
-
-		if (e == hipSuccess)
-			e = P->wfStream[i].create();
+		PIPE_TRY(P->wfCtl[i].alloc(64));
+		PIPE_TRY(hipMemset(P->wfCtl[i], 0, 64));
+		PIPE_TRY(P->wfStream[i].create());
 	}
-	for (int i = 0; i < pp_pipeline::kFbSets && e == hipSuccess; i++) {
-		e = P->fbCtl[i].alloc(64);
-		if (e == hipSuccess)
-			e = hipMemset(P->fbCtl[i], 0, 64);
-		if (e == hipSuccess)
-			e = P->fbList[i].alloc((size_t)capacity * 4);
-		if (e == hipSuccess)
-			e = P->fbDone[i].create(hipEventDisableTiming);
-		if (e == hipSuccess)
-			e = P->fbAfterTiles[i].create(hipEventDisableTiming);
+	for (int i = 0; i < pp_pipeline::kFbSets; i++) {
+		PIPE_TRY(P->fbCtl[i].alloc(64));
+		PIPE_TRY(hipMemset(P->fbCtl[i], 0, 64));
+		PIPE_TRY(P->fbList[i].alloc((size_t)capacity * 4));
+		PIPE_TRY(P->fbDone[i].create(hipEventDisableTiming));
+		PIPE_TRY(P->fbAfterTiles[i].create(hipEventDisableTiming));
 	}
-	if (e == hipSuccess)
-		e = P->fbStream.create();
+	PIPE_TRY(P->fbStream.create());
 	// The wavefront workgroups of a launch in flight stay until its list AND the urgent ring are empty, and launches queue: room on the chip
 	// frees rarely and in bursts.  When it does, the waves that top up the search grid and the scatter kernel of a new submission should get
 	// it before the next wavefront launch's pending workgroups refill the chip: their streams have the highest priority.  A safeguard, not a
@@ -452,22 +540,15 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 	const bool flatPriority = prioHigh == prioLow; // a device with an empty priority range: equal priorities
 	if (flatPriority)
 		prioHigh = 0;
-	for (int i = 0; i < kPipeSearchStreams && e == hipSuccess; i++)
-		e = P->searchStream[i].create(prioHigh);
-	if (e == hipSuccess)
-		e = P->ctlStream.create(prioHigh);
-	if (e == hipSuccess)
-		e = P->evIngest.create(hipEventDisableTiming);
-	if (e == hipSuccess)
-		e = P->evCtl.create(hipEventDisableTiming);
-	if (e == hipSuccess)
-		e = P->done.alloc(ring * sizeof(PipeDone));
-	if (e == hipSuccess)
-		e = P->slotStage.alloc(P->slotListCap * 4);
-	if (e == hipSuccess)
-		e = P->submittedStage.alloc(64 * 8);
-	if (e == hipSuccess)
-		e = P->errFlags.alloc(64);
+	for (int i = 0; i < kPipeSearchStreams; i++)
+		PIPE_TRY(P->searchStream[i].create(prioHigh));
+	PIPE_TRY(P->ctlStream.create(prioHigh));
+	PIPE_TRY(P->evIngest.create(hipEventDisableTiming));
+	PIPE_TRY(P->evCtl.create(hipEventDisableTiming));
+	PIPE_TRY(P->done.alloc(ring * sizeof(PipeDone)));
+	PIPE_TRY(P->slotStage.alloc(P->slotListCap * 4));
+	PIPE_TRY(P->submittedStage.alloc(64 * 8));
+	PIPE_TRY(P->errFlags.alloc(64));
 	if (const char* v = getenv("PP_PIPE_PATH_POSES")) {
 		const long x = strtol(v, nullptr, 10);
 		if (x >= 0 && x <= 2048)
@@ -475,20 +556,15 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 	}
 	if (P->pathHostCap > pl->maxPath)
 		P->pathHostCap = pl->maxPath;
-	if (e == hipSuccess && P->pathHostCap > 0)
-		e = P->pathHost.alloc((size_t)capacity * (size_t)P->pathHostCap * 24);
-	if (e == hipSuccess)
-		e = hipMemset(P->ctl, 0, sizeof(PipeCtl));
-	if (e == hipSuccess)
-		e = hipMemset(P->ready, 0, ring * 8);
-	if (e == hipSuccess)
-		e = hipMemset(P->waveAlive, 0, (size_t)P->waves * 4);
-	if (e == hipSuccess)
-		e = hipMemset(P->urgent, 0, ring * 8);
-	if (e == hipSuccess)
-		e = hipMemset(P->claimed, 0, (size_t)capacity * 4);
-	if (e == hipSuccess)
-		e = hipDeviceSynchronize();
+	if (P->pathHostCap > 0)
+		PIPE_TRY(P->pathHost.alloc((size_t)capacity * (size_t)P->pathHostCap * 24));
+	PIPE_TRY(hipMemset(P->ctl, 0, sizeof(PipeCtl)));
+	PIPE_TRY(hipMemset(P->ready, 0, ring * 8));
+	PIPE_TRY(hipMemset(P->waveAlive, 0, (size_t)P->waves * 4));
+	PIPE_TRY(hipMemset(P->urgent, 0, ring * 8));
+	PIPE_TRY(hipMemset(P->claimed, 0, (size_t)capacity * 4));
+	PIPE_TRY(hipDeviceSynchronize());
+#undef PIPE_TRY
 	if (e != hipSuccess) {
 		free_pipeline(P);
 		return pph::hip_fail(e, "pipeline allocation");
@@ -559,37 +635,31 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 			return PP_ERR_INVALID;
 		}
 	}
-	{
-		// an empty dispatch of k_postprocess_tickets on the stream pp_pipeline_postprocess uses: the queue allocates its scratch here, where a
-		// failure is an error code (see warm_up_kernels)
-		hipLaunchKernelGGL(k_postprocess_tickets, dim3(1), dim3(kPostThreads), 64, P->ctlStream, pl->args, PostParams {}, Footprint {}, 0, (const int32_t*)nullptr, (const PathRec*)nullptr,
-			(const RsLogEntry*)nullptr, (const DevResult*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, PostBuffers {});
+	// an empty dispatch of the kernels pp_pipeline_postprocess and pp_pipeline_revalidate launch, on the stream they use: the queue allocates their scratch here,
+	// where a failure is an error code (see warm_up_kernels)
+	auto warmUp = [&](const char* what, auto&& launchEmpty) -> int {
+		launchEmpty();
 		e = hipGetLastError();
 		if (e == hipSuccess)
 			e = hipStreamSynchronize(P->ctlStream);
-		if (e != hipSuccess) {
-			free_pipeline(P);
-			return pph::hip_fail(e, "pipeline post-processing kernel warm-up (scratch allocation)");
-		}
-		// ... and of k_revalidate_tickets, which pp_pipeline_revalidate launches on the same stream
-		hipLaunchKernelGGL(k_revalidate_tickets, dim3(1), dim3(64), 0, P->ctlStream, pl->args, Footprint {}, 0, (const int32_t*)nullptr, (const PathRec*)nullptr,
-			(const RsLogEntry*)nullptr, (const DevResult*)nullptr, (pp_revalidate_result*)nullptr);
-		e = hipGetLastError();
 		if (e == hipSuccess)
-			e = hipStreamSynchronize(P->ctlStream);
-		if (e != hipSuccess) {
-			free_pipeline(P);
-			return pph::hip_fail(e, "pipeline re-validation kernel warm-up (scratch allocation)");
-		}
-	}
+			return PP_OK;
+		free_pipeline(P);
+		return pph::hip_fail(e, what);
+	};
+	if (int rc = warmUp("pipeline post-processing kernel warm-up (scratch allocation)", [&] {
+			hipLaunchKernelGGL(k_postprocess_tickets, dim3(1), dim3(kPostThreads), 64, P->ctlStream, pl->args, PostParams {}, Footprint {}, 0, (const int32_t*)nullptr,
+				(const PathRec*)nullptr, (const RsLogEntry*)nullptr, (const DevResult*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, PostBuffers {});
+		}))
+		return rc;
+	if (int rc = warmUp("pipeline re-validation kernel warm-up (scratch allocation)", [&] {
+			hipLaunchKernelGGL(k_revalidate_tickets, dim3(1), dim3(64), 0, P->ctlStream, pl->args, Footprint {}, 0, (const int32_t*)nullptr, (const PathRec*)nullptr,
+				(const RsLogEntry*)nullptr, (const DevResult*)nullptr, (pp_revalidate_result*)nullptr);
+		}))
+		return rc;
 	std::memset(P->done, 0, ring * sizeof(PipeDone));
 	std::memset(P->errFlags, 0, 64);
-	P->freeSlots.resize((size_t)capacity);
-	for (int i = 0; i < capacity; i++)
-		P->freeSlots[(size_t)i] = capacity - 1 - i; // slot 0 is handed out first
-	P->ticketOfSlot.assign((size_t)capacity, 0);
-	P->slotState.assign((size_t)capacity, 0);
-	P->slotGen.assign((size_t)capacity, 0u);
+	P->tickets.reset(capacity);
 	pl->hostResults.resize((size_t)capacity);
 	pl->lastBatch = capacity;
 	pl->pipelineOwned = true;
@@ -640,19 +710,13 @@ int pp_pipeline_destroy(pp_pipeline* P)
 int pp_pipeline_capacity(pp_pipeline* P) { return P ? P->capacity : 0; }
 int pp_pipeline_search_rows(pp_pipeline* P) { return P ? P->pl->searchRows : 0; }
 int pp_pipeline_in_flight(pp_pipeline* P) { return P ? (int)(P->nSubmitted - P->doneHead) : 0; }
-int pp_pipeline_free_slots(pp_pipeline* P) { return P ? (int)P->freeSlots.size() : 0; }
+int pp_pipeline_free_slots(pp_pipeline* P) { return P ? P->tickets.free_slots() : 0; }
 pp_planner* pp_pipeline_planner(pp_pipeline* P) { return P ? P->pl : nullptr; }
 
 int pp_pipeline_set_footprint(pp_pipeline* P, pp_footprint* fp)
 {
-	if (!P) {
-		set_error("null pipeline");
-		return PP_ERR_INVALID;
-	}
-	if (P->dead) {
-		set_error("the pipeline failed in an earlier submission and must be destroyed");
-		return PP_ERR_HIP;
-	}
+	if (int rc = pipe_check(P))
+		return rc;
 	if (fp && fp->map != P->pl->map) {
 		set_error("the footprint belongs to another map than the pipeline's: create one for the pipeline's map with pp_footprint_create");
 		return PP_ERR_INVALID;
@@ -693,14 +757,8 @@ int pp_pipeline_set_footprint(pp_pipeline* P, pp_footprint* fp)
 
 int pp_pipeline_set_heuristic_clearance(pp_pipeline* P, float radius)
 {
-	if (!P) {
-		set_error("null pipeline");
-		return PP_ERR_INVALID;
-	}
-	if (P->dead) {
-		set_error("the pipeline failed in an earlier submission and must be destroyed");
-		return PP_ERR_HIP;
-	}
+	if (int rc = pipe_check(P))
+		return rc;
 	if (int rc = pph::clearance_check_radius(radius))
 		return rc;
 	if (P->nSubmitted != P->doneHead) {
@@ -730,16 +788,14 @@ int pp_pipeline_submit_dev(pp_pipeline* P, int32_t n_queries, const double* star
 		return PP_ERR_INVALID;
 	}
 	*n_accepted = 0;
-	if (P->dead) {
-		set_error("the pipeline failed in an earlier submission and must be destroyed");
+	if (pipe_dead(P))
 		return PP_ERR_HIP;
-	}
 	pp_planner* pl = P->pl;
 	PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
 	if (!pl->tableReady)
 		if (int rc = pp_planner_set_nonholo_table(pl, nullptr))
 			return rc;
-	int k = n_queries < (int)P->freeSlots.size() ? n_queries : (int)P->freeSlots.size();
+	int k = n_queries < P->tickets.free_slots() ? n_queries : P->tickets.free_slots();
 	if (k > (int)(P->slotListCap / 4))
 		k = (int)(P->slotListCap / 4);
 	if (k == 0)
@@ -821,17 +877,10 @@ int pp_pipeline_submit_dev(pp_pipeline* P, int32_t n_queries, const double* star
 	int32_t* const listDev = P->slotLists + P->slotListPos;
 	P->slotListPos += (size_t)k;
 	for (int i = 0; i < k; i++) {
-		const int32_t s = P->freeSlots.back();
-		P->freeSlots.pop_back();
-		uint32_t& gen = P->slotGen[(size_t)s];
-		gen = gen >= pph::kGenMask ? 1u : gen + 1u;
-		stage[i] = (int32_t)((uint32_t)s | (gen << pph::kSlotBits));
-		P->slotState[(size_t)s] = 1;
-		const uint64_t ticket = P->nTickets++;
-		P->ticketOfSlot[(size_t)s] = ticket;
-		P->slotOfTicket[ticket] = s;
+		const pph::TicketTable::Taken t = P->tickets.take(); // (k <= free_slots(): there is room)
+		stage[i] = t.entry;
 		if (tickets_out)
-			tickets_out[i] = ticket;
+			tickets_out[i] = t.ticket;
 	}
 	// ---- inputs into their slots: on the control stream (never busy for long), so the caller's arrays are free when this returns
 	hipStream_t const w = P->wfStream[P->nextWf];
@@ -913,7 +962,7 @@ int pp_pipeline_submit(pp_pipeline* P, int32_t n_queries, const double* starts_h
 		return PP_ERR_INVALID;
 	}
 	*n_accepted = 0;
-	int k = n_queries < (int)P->freeSlots.size() ? n_queries : (int)P->freeSlots.size();
+	int k = n_queries < P->tickets.free_slots() ? n_queries : P->tickets.free_slots();
 	if (k == 0)
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(P->pl->map->ctx->device));
@@ -935,10 +984,8 @@ int pp_pipeline_poll(pp_pipeline* P, int32_t max_results, uint64_t* tickets_out,
 		return PP_ERR_INVALID;
 	}
 	*n_out = 0;
-	if (P->dead) {
-		set_error("the pipeline failed earlier and must be destroyed");
+	if (pipe_dead(P))
 		return PP_ERR_HIP;
-	}
 	pp_planner* pl = P->pl;
 	int n = 0;
 	while (n < max_results) {
@@ -947,23 +994,17 @@ int pp_pipeline_poll(pp_pipeline* P, int32_t max_results, uint64_t* tickets_out,
 		if ((uint32_t)(stamp >> 32) != (uint32_t)(P->doneHead + 1ull))
 			break; // the next record has not been written yet
 		const int32_t slot = (int32_t)(uint32_t)stamp;
-		if (slot < 0 || slot >= P->capacity || P->slotState[(size_t)slot] != 1) {
+		if (!P->tickets.complete(slot, true)) {
 			set_error("pipeline completion ring corrupted");
 			return PP_ERR_HIP;
 		}
 		pl->hostResults[(size_t)slot] = rec->r;
 		P->lastTail = rec->readyTail;
 		P->lastHead = rec->readyHead;
-		tickets_out[n] = P->ticketOfSlot[(size_t)slot];
+		tickets_out[n] = P->tickets.ticket_of(slot);
 		results_out[n] = rec->r.r;
-		if (release) {
-			P->slotOfTicket.erase(P->ticketOfSlot[(size_t)slot]);
-			P->postIndexOfTicket.erase(P->ticketOfSlot[(size_t)slot]); // (a ticket in flight has no entry: every route that frees a slot says so all the same)
-			P->slotState[(size_t)slot] = 0;
-			P->freeSlots.push_back(slot);
-		} else {
-			P->slotState[(size_t)slot] = 2;
-		}
+		if (release)
+			(void)pipe_release(P, tickets_out[n]);
 		P->doneHead++;
 		n++;
 	}
@@ -982,11 +1023,7 @@ int pp_pipeline_poll(pp_pipeline* P, int32_t max_results, uint64_t* tickets_out,
 		// every result has been polled: the idle waves of the search grid may leave at once instead of waiting out their time-out (a device
 		// synchronisation then returns promptly).  One 8-byte copy per such transition -- not per poll.
 		PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
-		if ((P->submittedStagePos & 31) == 31)
-			PP_HIP_TRY(hipStreamSynchronize(P->ctlStream));
-		unsigned long long* const src = P->submittedStage + (P->submittedStagePos++ & 63);
-		*src = P->nSubmitted;
-		PP_HIP_TRY(hipMemcpyAsync(&P->ctl->quiesce, src, 8, hipMemcpyHostToDevice, P->ctlStream));
+		PP_HIP_TRY(pipe_stage_ctl(P, &P->ctl->quiesce, P->nSubmitted));
 		P->quiesced = P->nSubmitted;
 	}
 	if (P->nSubmitted > P->doneHead) {
@@ -1006,17 +1043,9 @@ int pp_pipeline_release(pp_pipeline* P, int32_t n, const uint64_t* tickets)
 		set_error("invalid arguments");
 		return PP_ERR_INVALID;
 	}
-	for (int i = 0; i < n; i++) {
-		auto it = P->slotOfTicket.find(tickets[i]);
-		if (it == P->slotOfTicket.end() || P->slotState[(size_t)it->second] != 2) {
-			set_error("ticket is not a completed, held query");
-			return PP_ERR_INVALID;
-		}
-		P->slotState[(size_t)it->second] = 0;
-		P->freeSlots.push_back(it->second);
-		P->postIndexOfTicket.erase(it->first);
-		P->slotOfTicket.erase(it);
-	}
+	for (int i = 0; i < n; i++) // (one by one: the tickets in front of a bad one have been released)
+		if (!pipe_release(P, tickets[i]))
+			return pipe_refuse(P, tickets[i], "released");
 	return PP_OK;
 }
 
@@ -1028,12 +1057,9 @@ int pp_pipeline_get_paths(pp_pipeline* P, int32_t n, const uint64_t* tickets, in
 	}
 	pp_planner* pl = P->pl;
 	for (int i = 0; i < n; i++) {
-		auto it = P->slotOfTicket.find(tickets[i]);
-		if (it == P->slotOfTicket.end() || P->slotState[(size_t)it->second] != 2) {
-			set_error("ticket is not a completed, held query");
-			return PP_ERR_INVALID;
-		}
-		const int32_t slot = it->second;
+		const int32_t slot = P->tickets.slot_of(tickets[i]);
+		if (slot < 0) // (one by one: the paths in front of a bad ticket have been written)
+			return pipe_refuse(P, tickets[i], "read");
 		const DevResult& r = pl->hostResults[(size_t)slot];
 		double* out = poses_host + (size_t)i * (size_t)max_poses * 3;
 		int np = r.r.status == 0 && r.solutionNode >= 0 ? r.r.n_path : 0;
@@ -1045,30 +1071,21 @@ int pp_pipeline_get_paths(pp_pipeline* P, int32_t n, const uint64_t* tickets, in
 		const int want = np < max_poses ? np : max_poses; // the first `want` poses of the path, start first = records np-1 .. np-want
 		const int inRing = np < P->pathHostCap ? np : P->pathHostCap; // records 0 .. inRing-1 (goal first) arrived with the completion record
 		const double* ring = P->pathHost + (size_t)slot * (size_t)P->pathHostCap * 3;
-		std::vector<PathRec> rest;
-		if (np > inRing || !P->pathHost) { // the ring holds the path's goal end; a longer path's start end comes from the device records (one copy)
-			const int first = P->pathHost ? inRing : 0;
-			rest.resize((size_t)(np - first));
-			if (np - first > 0) {
-				PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
-				PP_HIP_TRY(hipMemcpy(rest.data(), pl->paths + (size_t)slot * pl->maxPath + first, (size_t)(np - first) * sizeof(PathRec), hipMemcpyDeviceToHost));
-			}
-			for (int k = 0; k < want; k++) {
-				const int rec = np - 1 - k;
-				if (rec >= first) {
-					const PathRec& pr = rest[(size_t)(rec - first)];
-					out[3 * k] = pr.x;
-					out[3 * k + 1] = pr.y;
-					out[3 * k + 2] = pr.t;
-				} else {
-					out[3 * k] = ring[3 * rec];
-					out[3 * k + 1] = ring[3 * rec + 1];
-					out[3 * k + 2] = ring[3 * rec + 2];
-				}
-			}
-		} else {
-			for (int k = 0; k < want; k++) {
-				const int rec = np - 1 - k;
+		// the ring holds the path's goal end; a longer path's start end comes from the device records (one copy)
+		const int first = P->pathHost ? inRing : 0;
+		std::vector<PathRec> rest((size_t)(np - first));
+		if (np - first > 0) {
+			PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
+			PP_HIP_TRY(hipMemcpy(rest.data(), pl->paths + (size_t)slot * pl->maxPath + first, (size_t)(np - first) * sizeof(PathRec), hipMemcpyDeviceToHost));
+		}
+		for (int k = 0; k < want; k++) {
+			const int rec = np - 1 - k;
+			if (rec >= first) {
+				const PathRec& pr = rest[(size_t)(rec - first)];
+				out[3 * k] = pr.x;
+				out[3 * k + 1] = pr.y;
+				out[3 * k + 2] = pr.t;
+			} else {
 				out[3 * k] = ring[3 * rec];
 				out[3 * k + 1] = ring[3 * rec + 1];
 				out[3 * k + 2] = ring[3 * rec + 2];
@@ -1080,24 +1097,13 @@ int pp_pipeline_get_paths(pp_pipeline* P, int32_t n, const uint64_t* tickets, in
 	return PP_OK;
 }
 
-/// HybridAStar::SearchPath's post-processing of n completed, held queries, in the order of `tickets` (include/pp_hip.h).  Legal with queries in
-/// flight: a held slot's path records, Reeds-Shepp log and result record were written by the row that finished it BEFORE its completion record
-/// (finish() in pp_planner_rows.hpp: the stores, a system-scope release fence, s_waitcnt vmcnt(0), then the record and its stamp), the host saw
-/// that record with an acquire load in pp_pipeline_poll, and nothing writes the slot again until it is released and refilled.  The launch goes
-/// on the control stream with a COPY of the search arguments and the map view of the last submission: the buffer set's `args`, which the
-/// grid's top-up launches read, is not written, and only the control stream is synchronised: a buffer that has to grow while queries are in
-/// flight is parked, not freed (pp_pipeline::postParked).
+/// HybridAStar::SearchPath's post-processing of n completed, held queries, in the order of `tickets` (include/pp_hip.h), under the map view of the last
+/// submission (pipe_run_held)
 int pp_pipeline_postprocess(pp_pipeline* P, int32_t n, const uint64_t* tickets, float path_interpolation, const pp_smoother_params* smoother, int32_t max_points,
 	pp_post_result* results_host)
 {
-	if (!P) {
-		set_error("null pipeline");
-		return PP_ERR_INVALID;
-	}
-	if (P->dead) {
-		set_error("the pipeline failed earlier and must be destroyed");
-		return PP_ERR_HIP;
-	}
+	if (int rc = pipe_check(P))
+		return rc;
 	if (n < 0 || n > P->capacity || (n > 0 && !tickets)) {
 		set_error("invalid arguments (0 <= n <= capacity = " + std::to_string(P->capacity) + ", got n = " + std::to_string(n) + ")");
 		return PP_ERR_INVALID;
@@ -1112,30 +1118,11 @@ int pp_pipeline_postprocess(pp_pipeline* P, int32_t n, const uint64_t* tickets, 
 	}
 	pp_planner* pl = P->pl;
 	pp_map* map = pl->map;
-	if (!map->obstLabel[map->obstResult] || !map->voroLabel[map->voroResult]) {
-		set_error("nearest-obstacle / nearest-edge cell grids missing: pp_map_update_gvd or pp_map_upload_nearest_cells first");
-		return PP_ERR_INVALID;
-	}
-	std::vector<int32_t> slots((size_t)n);
-	{
-		std::unordered_map<uint64_t, int32_t> seen;
-		for (int i = 0; i < n; i++) {
-			auto it = P->slotOfTicket.find(tickets[i]);
-			if (it == P->slotOfTicket.end()) {
-				set_error("ticket " + std::to_string(tickets[i]) + " is unknown or already released");
-				return PP_ERR_INVALID;
-			}
-			if (P->slotState[(size_t)it->second] != 2) {
-				set_error("ticket " + std::to_string(tickets[i]) + " is still in flight (or was not polled with release = 0): only completed, held queries are post-processed");
-				return PP_ERR_INVALID;
-			}
-			if (!seen.emplace(tickets[i], i).second) {
-				set_error("ticket " + std::to_string(tickets[i]) + " is given twice");
-				return PP_ERR_INVALID;
-			}
-			slots[(size_t)i] = it->second;
-		}
-	}
+	if (int rc = post_check_grids(map))
+		return rc;
+	std::vector<int32_t> slots;
+	if (int rc = pipe_resolve(P, n, tickets, "post-processed", true, slots))
+		return rc;
 	// the last call's results end here (also for n == 0), whatever happens below
 	P->postIndexOfTicket.clear();
 	P->postHost.clear();
@@ -1143,72 +1130,25 @@ int pp_pipeline_postprocess(pp_pipeline* P, int32_t n, const uint64_t* tickets, 
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
 	const size_t samples = (size_t)n * (size_t)max_points;
-	// Nothing is freed while queries are in flight: hipFree waits for every stream of the device, i.e. for the searches in flight and the grid's
-	// idle waves.  A buffer that has to grow is parked instead, and the parked ones go when a call finds the pipeline idle.
-	const bool idle = P->nSubmitted == P->doneHead;
-	if (idle)
-		P->postParked.clear();
-	auto park = [&](pph::DeviceMem& b) {
-		if (!idle && b.get())
-			P->postParked.emplace_back(std::move(b));
-	};
-	if (P->postSamples < samples) {
-		P->postSamples = 0; // until every buffer below exists again: a failed allocation must not leave a stale capacity behind
-		park(P->postRatios), park(P->postResampled), park(P->postSmoothed), park(P->postCusp), park(P->postOptimise);
-		PP_HIP_TRY(P->postRatios.alloc(samples * 8));
-		PP_HIP_TRY(P->postResampled.alloc(samples * 24));
-		PP_HIP_TRY(P->postSmoothed.alloc(samples * 24));
-		PP_HIP_TRY(P->postCusp.alloc(samples));
-		PP_HIP_TRY(P->postOptimise.alloc(samples));
-		P->postSamples = samples;
-	}
-	if (P->postRows < n) {
-		P->postRows = 0;
-		park(P->postEdgeEnd), park(P->postOut), park(P->postSlots);
-		PP_HIP_TRY(P->postEdgeEnd.alloc((size_t)n * (size_t)(pl->maxPath + 1) * 8));
-		PP_HIP_TRY(P->postOut.alloc((size_t)n * sizeof(pp_post_result)));
-		PP_HIP_TRY(P->postSlots.alloc((size_t)n * 4));
-		P->postRows = n;
-	}
+	PP_HIP_TRY(pipe_grow(P, P->postSamples, samples,
+		{ { &P->postRatios, samples * 8 }, { &P->postResampled, samples * 24 }, { &P->postSmoothed, samples * 24 }, { &P->postCusp, samples }, { &P->postOptimise, samples } }));
+	PP_HIP_TRY(pipe_grow(P, P->postRows, (size_t)n,
+		{ { &P->postEdgeEnd, (size_t)n * (size_t)(pl->maxPath + 1) * 8 }, { &P->postOut, (size_t)n * sizeof(pp_post_result) }, { &P->postSlots, (size_t)n * 4 } }));
 	const PostBuffers post { P->postRatios, P->postResampled, P->postSmoothed, P->postCusp, P->postOptimise, P->postEdgeEnd, P->postOut };
-	PostParams pp {};
-	pp.pathInterpolation = path_interpolation;
-	pp_smoother_params sp { 1e-3f, 2000, 0.01f, 0.0f, 0.4f, 0.02f, 0.2f, 0.4f, 0.2f, (float)(1.0 / pl->params.min_turning_radius) }; // as pp_planner_postprocess
-	if (smoother)
-		sp = *smoother;
-	pp.stepTolerance = sp.step_tolerance;
-	pp.maxIterations = sp.max_iterations;
-	pp.learningRate = sp.learning_rate;
-	pp.pathWeight = sp.path_weight;
-	pp.smoothWeight = sp.smooth_weight;
-	pp.voronoiWeight = sp.voronoi_weight;
-	pp.collisionWeight = sp.collision_weight;
-	pp.curvatureWeight = sp.curvature_weight;
-	pp.collisionRatio = sp.collision_ratio;
-	pp.maxCurvature = sp.max_curvature;
-	pp.alpha = 20.0f; // GVD::alpha / dMax, gvd.h:181
-	pp.dMax = 30.0f;
-	pp.maxPoints = max_points;
-	SearchArgs args = pl->args;                          // a copy: the top-up launches of the search grid read pl->args
-	args.m = P->viewValid ? P->lastView : map->view(); // (held slots exist only after a submission, which cached the view)
-	Footprint foot {};                                   // n = 0: no footprint check
-	if (P->footprint)
-		foot = P->footprint->fp;
-	hipStream_t s = P->ctlStream;
-	PP_HIP_TRY(hipMemcpyAsync(P->postSlots, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, s)); // (pageable source: staged before the call returns)
-	hipLaunchKernelGGL(k_postprocess_tickets, dim3(n), dim3(kPostThreads), (size_t)max_points * 16, s, args, pp, foot, n, P->postSlots.get(), pl->paths.get(), pl->rsLogs.get(),
-		pl->results.get(), map->obstLabel[map->obstResult].get(), map->voroLabel[map->voroResult].get(), post);
-	PP_HIP_TRY(hipGetLastError());
-	std::vector<pp_post_result> host((size_t)n);
-	PP_HIP_TRY(hipMemcpyAsync(host.data(), P->postOut, (size_t)n * sizeof(pp_post_result), hipMemcpyDeviceToHost, s));
-	PP_HIP_TRY(hipStreamSynchronize(s));
+	const PostParams pp = post_params(path_interpolation, smoother, pl->params.min_turning_radius, max_points);
+	std::vector<pp_post_result> host;
+	// (held slots exist only after a submission, which cached the view)
+	if (int rc = pipe_run_held(P, slots, P->viewValid ? P->lastView : map->view(), P->postSlots.get(), P->postOut.get(), host,
+			[&](const SearchArgs& args, const Footprint& foot, int count, const int32_t* slotsDev) {
+				hipLaunchKernelGGL(k_postprocess_tickets, dim3(count), dim3(kPostThreads), (size_t)max_points * 16, P->ctlStream, args, pp, foot, count, slotsDev, pl->paths.get(),
+					pl->rsLogs.get(), pl->results.get(), map->obstLabel[map->obstResult].get(), map->voroLabel[map->voroResult].get(), post);
+			}))
+		return rc;
 	P->postHost.swap(host);
 	P->postPoints = max_points;
 	for (int i = 0; i < n; i++)
 		P->postIndexOfTicket[tickets[i]] = i;
-	if (results_host)
-		for (int i = 0; i < n; i++)
-			results_host[i] = P->postHost[(size_t)i];
+	records_out(P->postHost, results_host);
 	return PP_OK;
 }
 
@@ -1220,15 +1160,12 @@ int pp_pipeline_get_processed_paths(pp_pipeline* P, int32_t n, const uint64_t* t
 		set_error("invalid arguments");
 		return PP_ERR_INVALID;
 	}
-	if (P->dead) {
-		set_error("the pipeline failed earlier and must be destroyed");
+	if (pipe_dead(P))
 		return PP_ERR_HIP;
-	}
 	std::vector<int32_t> index((size_t)n);
 	for (int i = 0; i < n; i++) {
 		auto it = P->postIndexOfTicket.find(tickets[i]);
-		auto st = P->slotOfTicket.find(tickets[i]);
-		if (it == P->postIndexOfTicket.end() || st == P->slotOfTicket.end() || P->slotState[(size_t)st->second] != 2) {
+		if (it == P->postIndexOfTicket.end() || P->tickets.slot_of(tickets[i]) < 0) {
 			set_error("ticket " + std::to_string(tickets[i]) + " has no post-processed path: not in the last pp_pipeline_postprocess call, or released since");
 			return PP_ERR_INVALID;
 		}
@@ -1272,21 +1209,12 @@ int pp_pipeline_get_processed_paths(pp_pipeline* P, int32_t n, const uint64_t* t
 	return PP_OK;
 }
 
-/// Are the plans of n completed, held queries still collision-free on `target` as it is now (include/pp_hip.h)?  Legal with queries in flight for the
-/// reasons given at pp_pipeline_postprocess: a held slot's records were published before its completion record and nothing writes them until the
-/// slot is released.  The launch goes on the control stream with a COPY of the search arguments whose map view is the target's view of this moment
-/// (every writer of a map's grids has drained the map's stream before it returned, so the view is current); the buffer set's `args` is not written
-/// and only the control stream is synchronised.  Nothing of the last post-processing call is touched.
+/// Are the plans of n completed, held queries still collision-free on `target` as it is now (include/pp_hip.h)?  The map view is the target's of this moment
+/// (every writer of a map's grids has drained the map's stream before it returned, so the view is current).  Nothing of the last post-processing call is touched.
 int pp_pipeline_revalidate(pp_pipeline* P, pp_map* target, int32_t n, const uint64_t* tickets, pp_revalidate_result* results_host)
 {
-	if (!P) {
-		set_error("null pipeline");
-		return PP_ERR_INVALID;
-	}
-	if (P->dead) {
-		set_error("the pipeline failed earlier and must be destroyed");
-		return PP_ERR_HIP;
-	}
+	if (int rc = pipe_check(P))
+		return rc;
 	if (n < 0 || n > P->capacity || (n > 0 && !tickets)) {
 		set_error("invalid arguments (0 <= n <= capacity = " + std::to_string(P->capacity) + ", got n = " + std::to_string(n) + ")");
 		return PP_ERR_INVALID;
@@ -1295,58 +1223,20 @@ int pp_pipeline_revalidate(pp_pipeline* P, pp_map* target, int32_t n, const uint
 	pp_map* const map = target ? target : pl->map;
 	if (int rc = revalidate_check_target(pl->map, map))
 		return rc;
-	std::vector<int32_t> slots((size_t)n);
-	{
-		std::unordered_map<uint64_t, int32_t> seen;
-		for (int i = 0; i < n; i++) {
-			auto it = P->slotOfTicket.find(tickets[i]);
-			if (it == P->slotOfTicket.end()) {
-				set_error("ticket " + std::to_string(tickets[i]) + " is unknown or already released");
-				return PP_ERR_INVALID;
-			}
-			if (P->slotState[(size_t)it->second] != 2) {
-				set_error("ticket " + std::to_string(tickets[i]) + " is still in flight (or was not polled with release = 0): only completed, held queries are re-validated");
-				return PP_ERR_INVALID;
-			}
-			if (!seen.emplace(tickets[i], i).second) {
-				set_error("ticket " + std::to_string(tickets[i]) + " is given twice");
-				return PP_ERR_INVALID;
-			}
-			slots[(size_t)i] = it->second;
-		}
-	}
+	std::vector<int32_t> slots;
+	if (int rc = pipe_resolve(P, n, tickets, "re-validated", true, slots))
+		return rc;
 	if (n == 0)
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
-	const bool idle = P->nSubmitted == P->doneHead; // (see pp_pipeline_postprocess: nothing is freed beside queries in flight)
-	if (idle)
-		P->postParked.clear();
-	if (P->revRows < n) {
-		P->revRows = 0;
-		auto park = [&](pph::DeviceMem& b) {
-			if (!idle && b.get())
-				P->postParked.emplace_back(std::move(b));
-		};
-		park(P->revSlots), park(P->revOut);
-		PP_HIP_TRY(P->revSlots.alloc((size_t)n * 4));
-		PP_HIP_TRY(P->revOut.alloc((size_t)n * sizeof(pp_revalidate_result)));
-		P->revRows = n;
-	}
-	SearchArgs args = pl->args; // a copy: the top-up launches of the search grid read pl->args
-	args.m = map->view();       // the target as it is NOW
-	Footprint foot {};          // n = 0: the point validator
-	if (P->footprint)
-		foot = P->footprint->fp;
-	hipStream_t s = P->ctlStream;
-	PP_HIP_TRY(hipMemcpyAsync(P->revSlots, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, s)); // (pageable source: staged before the call returns)
-	hipLaunchKernelGGL(k_revalidate_tickets, dim3(n), dim3(64), 0, s, args, foot, n, P->revSlots.get(), pl->paths.get(), pl->rsLogs.get(), pl->results.get(), P->revOut.get());
-	PP_HIP_TRY(hipGetLastError());
-	std::vector<pp_revalidate_result> host((size_t)n);
-	PP_HIP_TRY(hipMemcpyAsync(host.data(), P->revOut, (size_t)n * sizeof(pp_revalidate_result), hipMemcpyDeviceToHost, s));
-	PP_HIP_TRY(hipStreamSynchronize(s));
-	if (results_host)
-		for (int i = 0; i < n; i++)
-			results_host[i] = host[(size_t)i];
+	PP_HIP_TRY(pipe_grow(P, P->revRows, (size_t)n, { { &P->revSlots, (size_t)n * 4 }, { &P->revOut, (size_t)n * sizeof(pp_revalidate_result) } }));
+	std::vector<pp_revalidate_result> host;
+	if (int rc = pipe_run_held(P, slots, map->view(), P->revSlots.get(), P->revOut.get(), host, [&](const SearchArgs& args, const Footprint& foot, int count, const int32_t* slotsDev) {
+			hipLaunchKernelGGL(k_revalidate_tickets, dim3(count), dim3(64), 0, P->ctlStream, args, foot, count, slotsDev, pl->paths.get(), pl->rsLogs.get(), pl->results.get(),
+				P->revOut.get());
+		}))
+		return rc;
+	records_out(host, results_host);
 	return PP_OK;
 }
 
@@ -1413,10 +1303,7 @@ int pp_pipeline_alive_waves(pp_pipeline* P)
 /// pp_pipeline_planner() take
 int pp_pipeline_slot_of(pp_pipeline* P, uint64_t ticket)
 {
-	if (!P)
-		return -1;
-	auto it = P->slotOfTicket.find(ticket);
-	return it == P->slotOfTicket.end() || P->slotState[(size_t)it->second] != 2 ? -1 : it->second;
+	return P ? P->tickets.slot_of(ticket) : -1;
 }
 
 } // extern "C"

@@ -505,6 +505,14 @@ int revalidate_check_target(const pp_map* own, const pp_map* target)
 	return PP_OK;
 }
 
+/// a call's result records to the caller, who may not want them (post-processing and re-validation, batch and by ticket)
+template <typename Rec>
+void records_out(const std::vector<Rec>& host, Rec* out)
+{
+	if (out)
+		std::copy(host.begin(), host.end(), out);
+}
+
 void free_planner(pp_planner* p)
 {
 	if (!p)
@@ -1281,10 +1289,8 @@ int pp_planner_postprocess(pp_planner* planner, int32_t n_queries, float path_in
 		return PP_ERR_INVALID;
 	}
 	pp_map* map = planner->map;
-	if (!map->obstLabel[map->obstResult] || !map->voroLabel[map->voroResult]) {
-		set_error("nearest-obstacle / nearest-edge cell grids missing: pp_map_update_gvd or pp_map_upload_nearest_cells first");
-		return PP_ERR_INVALID;
-	}
+	if (int rc = post_check_grids(map))
+		return rc;
 	if (n_queries == 0)
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(map->ctx->device));
@@ -1302,24 +1308,7 @@ int pp_planner_postprocess(pp_planner* planner, int32_t n_queries, float path_in
 	PP_HIP_TRY(planner->postEdgeEnd.ensure(B * (size_t)(planner->maxPath + 1) * 8));
 	PP_HIP_TRY(planner->postOut.ensure(B * sizeof(pp_post_result)));
 	const PostBuffers post { planner->postRatios, planner->postResampled, planner->postSmoothed, planner->postCusp, planner->postOptimise, planner->postEdgeEnd, planner->postOut };
-	PostParams P {};
-	P.pathInterpolation = path_interpolation;
-	pp_smoother_params sp { 1e-3f, 2000, 0.01f, 0.0f, 0.4f, 0.02f, 0.2f, 0.4f, 0.2f, (float)(1.0 / planner->params.min_turning_radius) }; // smoother.h:28-60, hybrid_a_star.cpp:214
-	if (smoother)
-		sp = *smoother;
-	P.stepTolerance = sp.step_tolerance;
-	P.maxIterations = sp.max_iterations;
-	P.learningRate = sp.learning_rate;
-	P.pathWeight = sp.path_weight;
-	P.smoothWeight = sp.smooth_weight;
-	P.voronoiWeight = sp.voronoi_weight;
-	P.collisionWeight = sp.collision_weight;
-	P.curvatureWeight = sp.curvature_weight;
-	P.collisionRatio = sp.collision_ratio;
-	P.maxCurvature = sp.max_curvature;
-	P.alpha = 20.0f; // GVD::alpha / dMax, gvd.h:181
-	P.dMax = 30.0f;
-	P.maxPoints = max_points; // the caller's limit, even below a capacity an earlier call allocated (status -4 beyond it)
+	const PostParams P = post_params(path_interpolation, smoother, planner->params.min_turning_radius, max_points);
 	planner->args.m = map->view();
 	const size_t lds = (size_t)max_points * 16;
 	hipLaunchKernelGGL(k_postprocess, dim3(n_queries), dim3(kPostThreads), lds, s, planner->args, P, n_queries, planner->paths, planner->rsLogs, planner->results,
@@ -1330,9 +1319,7 @@ int pp_planner_postprocess(pp_planner* planner, int32_t n_queries, float path_in
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	planner->postDone = n_queries;
 	planner->postPoints = max_points;
-	if (results_host)
-		for (int i = 0; i < n_queries; i++)
-			results_host[i] = planner->hostPost[i];
+	records_out(planner->hostPost, results_host);
 	return PP_OK;
 }
 
@@ -1384,9 +1371,7 @@ int pp_planner_revalidate(pp_planner* planner, pp_map* target, int32_t n_queries
 	std::vector<pp_revalidate_result> host((size_t)n_queries);
 	PP_HIP_TRY(hipMemcpyAsync(host.data(), planner->revOut, (size_t)n_queries * sizeof(pp_revalidate_result), hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
-	if (results_host)
-		for (int i = 0; i < n_queries; i++)
-			results_host[i] = host[(size_t)i];
+	records_out(host, results_host);
 	return PP_OK;
 }
 

@@ -46,6 +46,39 @@ struct PostBuffers {
 	pp_post_result* out; // [B]
 };
 
+/// the kernel's parameters from the caller's: Smoother::Params (smoother.h:28-60, max_curvature = 1 / min_turning_radius as hybrid_a_star.cpp:214 sets it)
+/// unless the caller gives its own; maxPoints is the caller's limit, even below a capacity an earlier call allocated (status -4 beyond it)
+inline PostParams post_params(float pathInterpolation, const pp_smoother_params* smoother, double minTurningRadius, int maxPoints)
+{
+	const pp_smoother_params defaults { 1e-3f, 2000, 0.01f, 0.0f, 0.4f, 0.02f, 0.2f, 0.4f, 0.2f, (float)(1.0 / minTurningRadius) };
+	const pp_smoother_params& sp = smoother ? *smoother : defaults;
+	PostParams p {};
+	p.pathInterpolation = pathInterpolation;
+	p.stepTolerance = sp.step_tolerance;
+	p.maxIterations = sp.max_iterations;
+	p.learningRate = sp.learning_rate;
+	p.pathWeight = sp.path_weight;
+	p.smoothWeight = sp.smooth_weight;
+	p.voronoiWeight = sp.voronoi_weight;
+	p.collisionWeight = sp.collision_weight;
+	p.curvatureWeight = sp.curvature_weight;
+	p.collisionRatio = sp.collision_ratio;
+	p.maxCurvature = sp.max_curvature;
+	p.alpha = 20.0f; // GVD::alpha / dMax, gvd.h:181
+	p.dMax = 30.0f;
+	p.maxPoints = maxPoints;
+	return p;
+}
+
+/// the grids the smoother's collision and Voronoi terms read
+inline int post_check_grids(const pp_map* map)
+{
+	if (map->obstLabel[map->obstResult] && map->voroLabel[map->voroResult])
+		return PP_OK;
+	pph::set_error("nearest-obstacle / nearest-edge cell grids missing: pp_map_update_gvd or pp_map_upload_nearest_cells first");
+	return PP_ERR_INVALID;
+}
+
 struct V2d {
 	double x, y;
 };
