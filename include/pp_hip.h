@@ -546,6 +546,67 @@ int pp_pipeline_revalidate(pp_pipeline* pipeline, pp_map* target /* NULL: the pi
  * last batch; a target of another context or without a distance grid; a planner that is a pipeline's buffer set (pp_pipeline_revalidate
  * knows which of its slots are held). */
 int pp_planner_revalidate(pp_planner* planner, pp_map* target /* NULL: own map */, int32_t n_queries, pp_revalidate_result* results_host);
+/* ---- stamping held plans into a map, by ticket ------------------------------------------------------------------------------------------
+ * A STAMP of a plan is the set of cells of a TARGET map covered by the vehicle's discs at sample poses along the plan.  One wave per plan
+ * (k_stamp_tickets) reads the plan where the search left it and writes the target's int32 occupancy grid, so a plan becomes part of a map
+ * -- a reservation map for the next vehicle of a prioritised planner -- without leaving the device.
+ *  Discs.   With a footprint set (pp_pipeline_set_footprint; pp_planner_set_footprint for the batch form) its discs (ox_i, oy_i, r_i); without one
+ *           the single disc (0, 0, min_safe_radius) of the pipeline's (planner's) OWN map: the point validator seen as a footprint.  Only the
+ *           discs travel, as in re-validation.  Effective radius R_i = (double)r_i + (double)margin.
+ *  Edges.   The plan's own path objects: a constant-steer arc per node, then the Reeds-Shepp path of the analytic expansion, numbered root first
+ *           1 .. n_path - 1.  S_e = the sequential root-first sum of the lengths of the edges before e (the sum of pp_revalidate_result::length: the
+ *           order is part of the result).
+ *  Samples. Edge e of length L has n = L > 0 ? (int)ceil(L / spacing) : 0 steps, in double (n is capped at 2^19).  n == 0: one sample at ratio 0;
+ *           otherwise the ratios (double)k / (double)n for k = 0 .. n -- both ends, so a junction pose is sampled twice, which is harmless.  The pose
+ *           is the path object's interpolation at that ratio (the function post-processing samples with); the sample's arc length is
+ *           s = S_e + ratio * L.  A one-pose plan has one sample: its pose, at s = 0.
+ *  Window.  Plan i takes part with the samples from_length[i] <= s <= to_length[i], compared in double (NULL array: -inf / +inf): a vehicle that has
+ *           driven 12 m reserves [12, 12 + horizon].  An empty window is legal: status 0, n_samples 0.
+ *  Centres. Disc i at a sample pose (x, y, theta): the expression of the footprint state check's step 2 -- cx = (x + ox*c) - oy*s,
+ *           cy = (y + ox*s) + oy*c with (s, c) = sincos of the unwrapped theta in double; a disc with ox == 0 && oy == 0 uses (x, y) and no trigonometry.
+ *  Cells.   Cell (row, col) of the target spans [gx + row res, gx + (row + 1) res) in x and [gy + col res, gy + (col + 1) res) in y, res = (double) of the
+ *           target's float resolution, (gx, gy) its grid origin.  It is covered iff its centre (gx + (row + 0.5) res, gy + (col + 0.5) res) satisfies
+ *           dx^2 + dy^2 <= R_i^2 in double for some sample in the window and some disc.  Whatever lies outside the target's grid is clipped silently.
+ *           No bounds test and no validity test is applied to the poses: a plan is stamped where it lies.
+ *  Write.   occupancy[cell] = max(occupancy[cell], values[i]) for every covered cell, values[i] >= 0 (NULL: 0 for every plan; free cells hold -1), by a
+ *           vector atomic max: the grid after the call does not depend on the order of plans, samples or lanes.  A target that has no int32 occupancy
+ *           grid yet gets one, all -1, as pp_map_set_cells gives it.
+ *  Superset. Between two samples the reference point moves at most `spacing`, a disc centre at most spacing * (1 + kappa_max * rho) (rho = the largest
+ *           |(ox_i, oy_i)|, kappa_max = 1 / min_turning_radius).  So margin >= 0.5 * spacing * (1 + kappa_max * rho) + res * sqrt(2) / 2 makes the stamp a
+ *           superset of every cell the discs touch while they sweep the plan.  The library does not choose a margin for the caller.
+ *  Afterwards. What every occupancy writer does: the target's occupancy views are rebuilt (heuristic-clearance views and the tile form's bit rows of
+ *           anyone using the target go stale and rebuild as they do after pp_map_set_cells), and the target's stream is drained before the call returns.
+ *           The cells written are unknown to the ordered edit record of PP_GVD_REFERENCE_ORDER: the record is dropped and the next update in that mode
+ *           re-seeds from the device grid ("every occupied cell, row-major").  The distance grid, the squared distances and the path cost are NOT touched:
+ *           the caller runs pp_map_update_gvd[_ex] on the target when it wants the fields to follow.
+ *  - target == NULL: the pipeline's own map.  Otherwise any pp_map of the same context, of any geometry.  Stamping another map than the pipeline's own is
+ *    legal beside queries in flight (stamp reservation map B while the grid searches map A): the launch runs on the pipeline's control stream with a
+ *    copy of the search arguments, only that stream and the target's are synchronised, and a held slot is not written until it is released.
+ *  - PP_ERR_INVALID, nothing launched, nothing written, the pipeline usable as before, the message naming the first offending ticket or argument:
+ *    n < 0 or n > capacity; a ticket that is unknown, released, still in flight or given twice; a target of another context; NULL params, a spacing that
+ *    is not finite and > 0, a margin that is not finite and >= 0; a negative value; a NaN in a window array; the pipeline's OWN map as the target while
+ *    pp_pipeline_in_flight() > 0 (the field launches in flight read the occupancy views this call rewrites; held slots do not count).  n == 0 is PP_OK:
+ *    nothing is touched.
+ *  - The pipeline owns the slot list, the per-ticket arguments and the result buffer (4 + 24 + 32 bytes per ticket of the largest call so far), kept
+ *    aside like the post-processing buffers when they have to grow beside queries in flight. */
+typedef struct pp_stamp_params {
+	double  spacing;  /* > 0, finite, metres */
+	float   margin;   /* >= 0, finite */
+	int32_t reserved;
+} pp_stamp_params;
+typedef struct pp_stamp_result {
+	int32_t status;      /* 0 stamped (n_samples may be 0); -1 no plan; -4 path longer than the planner's path capacity */
+	int32_t n_samples;   /* samples inside the window */
+	int32_t cell_box[4]; /* row_min, row_max, col_min, col_max of the cells this plan COVERS inside the target, whatever they held before;
+	                        row_min > row_max: none */
+	double  length;      /* pp_revalidate_result::length, bit for bit */
+} pp_stamp_result;
+int pp_pipeline_stamp(pp_pipeline* pipeline, pp_map* target /* NULL: the pipeline's own map */, int32_t n, const uint64_t* tickets, const int32_t* values,
+	const double* from_length, const double* to_length, const pp_stamp_params* params, pp_stamp_result* results_host /* may be NULL */);
+/* The same kernel over the first n_queries queries of the planner's last batch (identity slots), on the planner's stream, with the planner's
+ * footprint if it has one.  PP_ERR_INVALID as above, and for a planner that is a pipeline's buffer set (pp_pipeline_stamp knows which slots are held). */
+int pp_planner_stamp(pp_planner* planner, pp_map* target /* NULL: own map */, int32_t n_queries, const int32_t* values, const double* from_length,
+	const double* to_length, const pp_stamp_params* params, pp_stamp_result* results_host);
 /* Diagnostics: waves of the search grid that are alive right now (a blocking device-to-host copy; -1 on error). */
 int pp_pipeline_alive_waves(pp_pipeline* pipeline);
 pp_planner* pp_pipeline_planner(pp_pipeline* pipeline);           /* the buffer set: set_nonholo_table, set_primitives, get_path(slot), ... */

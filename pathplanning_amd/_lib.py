@@ -87,6 +87,17 @@ class RevalidateResult(C.Structure):
                 ("length", C.c_double)]
 
 
+class StampParams(C.Structure):
+    """pp_stamp_params: sample spacing along the plan (> 0, metres) and the margin added to every disc radius (>= 0)"""
+    _fields_ = [("spacing", C.c_double), ("margin", C.c_float), ("reserved", C.c_int32)]
+
+
+class StampResult(C.Structure):
+    """pp_stamp_result: status 0 stamped, -1 no plan, -4 path beyond the path capacity; cell_box = (row_min, row_max, col_min, col_max) of the
+    cells the plan covers inside the target (row_min > row_max: none)"""
+    _fields_ = [("status", C.c_int32), ("n_samples", C.c_int32), ("cell_box", C.c_int32 * 4), ("length", C.c_double)]
+
+
 class GridResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("n_path", C.c_int32), ("n_expanded", C.c_int32), ("n_expanded_reverse", C.c_int32), ("cost", C.c_double)]
 
@@ -211,6 +222,8 @@ def load():
     L.pp_pipeline_get_processed_paths.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, C.c_int32]
     L.pp_pipeline_revalidate.argtypes = [vp, vp, C.c_int32, vp, vp]
     L.pp_planner_revalidate.argtypes = [vp, vp, C.c_int32, vp]
+    L.pp_pipeline_stamp.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, C.POINTER(StampParams), vp]
+    L.pp_planner_stamp.argtypes = [vp, vp, C.c_int32, vp, vp, vp, C.POINTER(StampParams), vp]
     L.pp_pipeline_timings.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.pp_pipeline_backlog.argtypes = [vp, vp, vp]
     L.pp_pipeline_planner.argtypes = [vp]

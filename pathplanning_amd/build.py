@@ -107,6 +107,33 @@ def build_pipeline_revalidate_test(verbose=True):
     return out
 
 
+def build_pipeline_stamp_test(verbose=True):
+    """tests/cpp/test_pipeline_stamp.cpp: Stamp(tickets) of HybridAStarPipeline against the plan's path objects sampled and rasterised one by one (run on the GPU box)."""
+    build()
+    out = os.path.join(LIB_DIR, "test_pipeline_stamp")
+    src = os.path.join(HERE, "..", "tests", "cpp", "test_pipeline_stamp.cpp")
+    cmd = ["g++", "-O2", "-std=c++17", src, "-o", out, "-L" + LIB_DIR, "-lpphip", "-Wl,-rpath,$ORIGIN"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return out
+
+
+def build_stamp_rule_test(verbose=True):
+    """tests/cpp/test_stamp_rule.cpp: the stamp's sample schedule and cell rule (csrc/pp_stamp_rule.hpp) alone, on the CPU, under the address and
+    undefined-behaviour sanitizers; without contraction, as the library is built."""
+    os.makedirs(LIB_DIR, exist_ok=True)
+    out = os.path.join(LIB_DIR, "test_stamp_rule")
+    src = os.path.join(HERE, "..", "tests", "cpp", "test_stamp_rule.cpp")
+    if os.path.exists(out) and os.path.getmtime(out) > max(os.path.getmtime(src), os.path.getmtime(os.path.join(CSRC, "pp_stamp_rule.hpp"))):
+        return out
+    cmd = ["g++", "-std=c++17", "-g", "-O1", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC, src, "-o", out]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return out
+
+
 def build_ticket_table_test(verbose=True):
     """tests/cpp/test_ticket_table.cpp: the pipeline's slot and ticket bookkeeping (csrc/pp_ticket_table.hpp) alone, on the CPU, under the address and
     undefined-behaviour sanitizers."""
@@ -143,5 +170,7 @@ if __name__ == "__main__":
     print(build_pipeline_footprint_test())
     print(build_pipeline_postprocess_test())
     print(build_pipeline_revalidate_test())
+    print(build_pipeline_stamp_test())
+    print(build_stamp_rule_test())
     print(build_ticket_table_test())
     print(build_row_test())

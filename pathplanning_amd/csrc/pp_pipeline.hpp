@@ -221,6 +221,11 @@ struct pp_pipeline {
 	pph::Dev<int32_t> revSlots;
 	pph::Dev<pp_revalidate_result> revOut;
 	size_t revRows = 0;
+	// pp_pipeline_stamp (k_stamp_tickets): the slot list, the values and windows, and the results of a call, by compact index
+	pph::Dev<int32_t> stampSlots;
+	pph::Dev<StampArg> stampArgs;
+	pph::Dev<pp_stamp_result> stampOut;
+	size_t stampRows = 0;
 	int nWf = 2;      // wavefront streams in use: consecutive submissions' launches overlap (the tail of one under the head of the next)
 	int wfBlocks = 0; // workgroups per wavefront launch (<= the resident number): the wavefront kernel's share of the chip
 };
@@ -635,7 +640,7 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 			return PP_ERR_INVALID;
 		}
 	}
-	// an empty dispatch of the kernels pp_pipeline_postprocess and pp_pipeline_revalidate launch, on the stream they use: the queue allocates their scratch here,
+	// an empty dispatch of the kernels pp_pipeline_postprocess, pp_pipeline_revalidate and pp_pipeline_stamp launch, on the stream they use: the queue allocates their scratch here,
 	// where a failure is an error code (see warm_up_kernels)
 	auto warmUp = [&](const char* what, auto&& launchEmpty) -> int {
 		launchEmpty();
@@ -655,6 +660,10 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 	if (int rc = warmUp("pipeline re-validation kernel warm-up (scratch allocation)", [&] {
 			hipLaunchKernelGGL(k_revalidate_tickets, dim3(1), dim3(64), 0, P->ctlStream, pl->args, Footprint {}, 0, (const int32_t*)nullptr, (const PathRec*)nullptr,
 				(const RsLogEntry*)nullptr, (const DevResult*)nullptr, (pp_revalidate_result*)nullptr);
+		}))
+		return rc;
+	if (int rc = warmUp("pipeline stamp kernel warm-up (scratch allocation)", [&] {
+			(void)launch_stamp(P->ctlStream, pl->args, Footprint {}, nullptr, 0, nullptr, nullptr, pl, nullptr, nullptr);
 		}))
 		return rc;
 	std::memset(P->done, 0, ring * sizeof(PipeDone));
@@ -1235,6 +1244,54 @@ int pp_pipeline_revalidate(pp_pipeline* P, pp_map* target, int32_t n, const uint
 			hipLaunchKernelGGL(k_revalidate_tickets, dim3(count), dim3(64), 0, P->ctlStream, args, foot, count, slotsDev, pl->paths.get(), pl->rsLogs.get(), pl->results.get(),
 				P->revOut.get());
 		}))
+		return rc;
+	records_out(host, results_host);
+	return PP_OK;
+}
+
+/// The plans of n completed, held queries stamped into `target`'s occupancy grid (include/pp_hip.h).  The kernel runs on the control stream under the
+/// target's view of this moment; the views of the target are refreshed on the target's own stream once the control stream has been drained, i.e. behind the stamp.
+int pp_pipeline_stamp(pp_pipeline* P, pp_map* target, int32_t n, const uint64_t* tickets, const int32_t* values, const double* from_length, const double* to_length,
+	const pp_stamp_params* params, pp_stamp_result* results_host)
+{
+	if (int rc = pipe_check(P))
+		return rc;
+	if (n < 0 || n > P->capacity || (n > 0 && !tickets)) {
+		set_error("invalid arguments (0 <= n <= capacity = " + std::to_string(P->capacity) + ", got n = " + std::to_string(n) + ")");
+		return PP_ERR_INVALID;
+	}
+	pp_planner* pl = P->pl;
+	pp_map* const map = target ? target : pl->map;
+	std::vector<StampArg> plans;
+	if (int rc = stamp_check(pl->map, map, n, values, from_length, to_length, params, [&](int i) { return "ticket " + std::to_string(tickets[i]); }, plans))
+		return rc;
+	std::vector<int32_t> slots;
+	if (int rc = pipe_resolve(P, n, tickets, "stamped", true, slots))
+		return rc;
+	if (map == pl->map && P->nSubmitted != P->doneHead) {
+		// the field launches of the queries in flight read the occupancy views this call rewrites (held slots do not count: their fields are built)
+		set_error("the target is the pipeline's own map and the pipeline has " + std::to_string(P->nSubmitted - P->doneHead) +
+			" queries in flight: poll them all first, or stamp another map of the context");
+		return PP_ERR_INVALID;
+	}
+	if (n == 0)
+		return PP_OK;
+	PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
+	if (int rc = stamp_prepare_target(map))
+		return rc;
+	PP_HIP_TRY(pipe_grow(P, P->stampRows, (size_t)n,
+		{ { &P->stampSlots, (size_t)n * 4 }, { &P->stampArgs, (size_t)n * sizeof(StampArg) }, { &P->stampOut, (size_t)n * sizeof(pp_stamp_result) } }));
+	const Footprint discs = stamp_discs(P->footprint, pl->map);
+	std::vector<pp_stamp_result> host;
+	hipError_t staged = hipSuccess;
+	if (int rc = pipe_run_held(P, slots, map->view(), P->stampSlots.get(), P->stampOut.get(), host, [&](const SearchArgs& args, const Footprint&, int count, const int32_t* slotsDev) {
+			staged = hipMemcpyAsync(P->stampArgs.get(), plans.data(), (size_t)count * sizeof(StampArg), hipMemcpyHostToDevice, P->ctlStream); // (pageable: staged at once)
+			if (staged == hipSuccess)
+				(void)launch_stamp(P->ctlStream, args, discs, params, count, slotsDev, P->stampArgs.get(), pl, map->occ32.get(), P->stampOut.get());
+		}))
+		return rc;
+	PP_HIP_TRY(staged);
+	if (int rc = stamp_finish_target(map))
 		return rc;
 	records_out(host, results_host);
 	return PP_OK;

@@ -17,6 +17,7 @@
 // the discrete outcomes (cells, validity); continuous poses agree to ~1e-15.
 #include "pp_search_device.hpp"
 #include "pp_row_primitives.hpp"
+#include "pp_stamp_rule.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -298,6 +299,8 @@ struct PipeView {
 #undef PP_POST_TICKETS
 // re-validation of plans against a changed map (one wave per plan; PostEdge / load_edge of the file above)
 #include "pp_revalidate.hpp"
+// held plans stamped into a map's occupancy grid (one wave per plan; the same PostEdge / load_edge)
+#include "pp_stamp.hpp"
 
 } // namespace
 
@@ -362,6 +365,8 @@ struct pp_planner {
 	int postPoints = 0; // the last call's max_points: its sample limit and the buffers' per-query stride
 	std::vector<pp_post_result> hostPost;
 	pph::Dev<pp_revalidate_result> revOut; // [maxBatch], allocated at the first pp_planner_revalidate
+	pph::Dev<StampArg> stampArgs;          // [maxBatch], allocated at the first pp_planner_stamp
+	pph::Dev<pp_stamp_result> stampOut;    // [maxBatch]
 };
 
 namespace {
@@ -426,6 +431,15 @@ hipError_t launch_search_rows_footprint(pp_planner* p, hipStream_t s, const Sear
 	return hipGetLastError();
 }
 
+/// k_stamp_tickets over `count` plans of buffer set p (count = 0 on a grid of one: the warm-up, which dereferences nothing)
+hipError_t launch_stamp(hipStream_t s, const SearchArgs& args, const Footprint& foot, const pp_stamp_params* params, int count, const int32_t* slotsDev, const StampArg* argsDev,
+	pp_planner* p, int32_t* occ, pp_stamp_result* outDev)
+{
+	hipLaunchKernelGGL(k_stamp_tickets, dim3(count > 0 ? count : 1), dim3(kStampLanes), stamp_lds_bytes(args.maxPath), s, args, foot, params ? params->spacing : 1.0,
+		params ? params->margin : 0.0f, count, slotsDev, argsDev, p->paths.get(), p->rsLogs.get(), p->results.get(), occ, outDev);
+	return hipGetLastError();
+}
+
 /// Empty dispatches of the three kernels a batch launches, on the planner's stream, then a synchronisation: the queue
 /// allocates their scratch here, where a failure is an error code, not at the first batch, where it is an abort.
 int warm_up_kernels(pp_planner* p, pp_map* map)
@@ -457,6 +471,8 @@ int warm_up_kernels(pp_planner* p, pp_map* map)
 			(const DevResult*)nullptr, (pp_revalidate_result*)nullptr);
 		e = hipGetLastError();
 	}
+	if (e == hipSuccess)
+		e = launch_stamp(s, p->args, Footprint {}, nullptr, 0, nullptr, nullptr, p, nullptr, nullptr);
 	if (e == hipSuccess)
 		e = hipStreamSynchronize(s);
 	if (e != hipSuccess)
@@ -502,6 +518,83 @@ int revalidate_check_target(const pp_map* own, const pp_map* target)
 		set_error("the target map has no distance grid: pp_map_upload_dist2, pp_map_upload_distance or pp_map_update_gvd first");
 		return PP_ERR_INVALID;
 	}
+	return PP_OK;
+}
+
+/// The arguments of a stamp that do not depend on who holds the plans (pp_planner_stamp, pp_pipeline_stamp): the target's context, the
+/// parameters, and the per-plan values and windows, which go into `plans` (what(i) names plan i in a refusal)
+template <typename Name>
+int stamp_check(const pp_map* own, const pp_map* target, int n, const int32_t* values, const double* from_length, const double* to_length, const pp_stamp_params* params,
+	Name what, std::vector<StampArg>& plans)
+{
+	if (target->ctx != own->ctx) {
+		set_error("the target map belongs to another context than the planner's map");
+		return PP_ERR_INVALID;
+	}
+	if (!params) {
+		set_error("invalid arguments (null params: a pp_stamp_params with spacing > 0 is needed)");
+		return PP_ERR_INVALID;
+	}
+	if (!std::isfinite(params->spacing) || !(params->spacing > 0.0)) {
+		set_error("invalid arguments (the stamp's spacing is finite and > 0 metres)");
+		return PP_ERR_INVALID;
+	}
+	if (!std::isfinite(params->margin) || params->margin < 0.0f) {
+		set_error("invalid arguments (the stamp's margin is finite and >= 0 metres)");
+		return PP_ERR_INVALID;
+	}
+	plans.resize((size_t)n);
+	for (int i = 0; i < n; i++) {
+		StampArg& a = plans[(size_t)i];
+		a.from = from_length ? from_length[i] : -HUGE_VAL;
+		a.to = to_length ? to_length[i] : HUGE_VAL;
+		a.value = values ? values[i] : 0;
+		a.pad = 0;
+		if (a.value < 0) {
+			set_error(what(i) + " has the negative value " + std::to_string(a.value) + ": a stamp writes occupancy ids >= 0 (-1 is a free cell)");
+			return PP_ERR_INVALID;
+		}
+		if (a.from != a.from || a.to != a.to) {
+			set_error(what(i) + " has a NaN in its window");
+			return PP_ERR_INVALID;
+		}
+	}
+	return PP_OK;
+}
+
+/// the discs a stamp uses: the holder's footprint, or the point validator seen as one -- the disc (0, 0, minSafeRadius) of the holder's OWN map
+Footprint stamp_discs(const pp_footprint* fp, const pp_map* own)
+{
+	if (fp)
+		return fp->fp;
+	Footprint f {};
+	f.n = 1;
+	f.r[0] = own->minSafeRadius;
+	return f;
+}
+
+/// a target without an int32 occupancy grid gets one, all -1 (as pp_map_set_cells does), complete before the call's stream goes on
+int stamp_prepare_target(pp_map* map)
+{
+	if (map->occ32)
+		return PP_OK;
+	const size_t n = map->cells();
+	PP_HIP_TRY(map->occ32.ensure(n * 4));
+	PP_HIP_TRY(hipMemsetAsync(map->occ32, 0xFF, n * 4, map->ctx->stream));
+	PP_HIP_TRY(hipStreamSynchronize(map->ctx->stream));
+	return PP_OK;
+}
+
+/// What every occupancy writer does afterwards, behind a stamp that is complete: the views (occVersion goes up; clearance views and bit rows follow as
+/// they do today), and the edit journal, which does not know the cells written -- the next reference-order update re-seeds from the device grid
+int stamp_finish_target(pp_map* map)
+{
+	map->journal.clear();
+	map->journal.shrink_to_fit();
+	map->journalLost = true;
+	if (int rc = pph::refresh_occupancy_views(map, map->ctx->stream))
+		return rc;
+	PP_HIP_TRY(hipStreamSynchronize(map->ctx->stream));
 	return PP_OK;
 }
 
@@ -1371,6 +1464,43 @@ int pp_planner_revalidate(pp_planner* planner, pp_map* target, int32_t n_queries
 	std::vector<pp_revalidate_result> host((size_t)n_queries);
 	PP_HIP_TRY(hipMemcpyAsync(host.data(), planner->revOut, (size_t)n_queries * sizeof(pp_revalidate_result), hipMemcpyDeviceToHost, s));
 	PP_HIP_TRY(hipStreamSynchronize(s));
+	records_out(host, results_host);
+	return PP_OK;
+}
+
+int pp_planner_stamp(pp_planner* planner, pp_map* target, int32_t n_queries, const int32_t* values, const double* from_length, const double* to_length,
+	const pp_stamp_params* params, pp_stamp_result* results_host)
+{
+	if (!planner || n_queries < 0 || n_queries > planner->lastBatch) {
+		set_error("invalid arguments (0 <= n_queries <= last batch)");
+		return PP_ERR_INVALID;
+	}
+	if (planner->pipelineOwned) {
+		set_error("this planner is a pipeline's buffer set: pp_pipeline_stamp stamps its held tickets");
+		return PP_ERR_INVALID;
+	}
+	pp_map* const map = target ? target : planner->map;
+	std::vector<StampArg> plans;
+	if (int rc = stamp_check(planner->map, map, n_queries, values, from_length, to_length, params, [](int i) { return "query " + std::to_string(i); }, plans))
+		return rc;
+	if (n_queries == 0)
+		return PP_OK;
+	PP_HIP_TRY(hipSetDevice(planner->map->ctx->device));
+	hipStream_t s = planner->map->ctx->stream; // (the target's too: one context)
+	if (int rc = stamp_prepare_target(map))
+		return rc;
+	PP_HIP_TRY(planner->stampArgs.ensure((size_t)planner->maxBatch * sizeof(StampArg)));
+	PP_HIP_TRY(planner->stampOut.ensure((size_t)planner->maxBatch * sizeof(pp_stamp_result)));
+	SearchArgs args = planner->args; // a copy: the planner's own arguments keep its own map's view
+	args.m = map->view();
+	PP_HIP_TRY(hipMemcpyAsync(planner->stampArgs, plans.data(), (size_t)n_queries * sizeof(StampArg), hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(launch_stamp(s, args, stamp_discs(planner->footprint, planner->map), params, n_queries, nullptr, planner->stampArgs.get(), planner, map->occ32.get(),
+		planner->stampOut.get()));
+	std::vector<pp_stamp_result> host((size_t)n_queries);
+	PP_HIP_TRY(hipMemcpyAsync(host.data(), planner->stampOut, (size_t)n_queries * sizeof(pp_stamp_result), hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipStreamSynchronize(s));
+	if (int rc = stamp_finish_target(map))
+		return rc;
 	records_out(host, results_host);
 	return PP_OK;
 }

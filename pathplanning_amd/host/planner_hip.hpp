@@ -328,6 +328,14 @@ public:
 		m_hostStale = true;
 		m_fieldsBuilt = false;
 	}
+	/// the device occupancy grid was written by a call that does not go through this class (HybridAStarPipeline::Stamp): the device holds the newer
+	/// grid, the fields are behind it
+	void OccupancyWrittenOnDevice()
+	{
+		m_onDevice = true;
+		m_hostStale = true;
+		m_fieldsBuilt = false;
+	}
 	/// Voronoi data of the last BuildFields (host copies), row-major
 	struct VoronoiGrids {
 		std::vector<int32_t> d2, nearestEdge, nearestObstacle;
@@ -1010,6 +1018,7 @@ struct RRTStarParameters {
 /// samples and smooths them on the device (pp_pipeline_postprocess, legal while others are in flight), GetPath(ticket) is then what
 /// HybridAStar::GetPath() returns for that query, GetSmoothingStatus(ticket) its Stats::smoothingStatus; Release(tickets) frees the slots.
 /// Revalidate(tickets) asks whether held plans are still collision-free after the map changed (pp_pipeline_revalidate).
+/// Stamp(tickets, into, spacing) writes the cells held plans sweep into a map's occupancy grid (pp_pipeline_stamp): the reservation map of the next vehicle.
 class HybridAStarPipeline {
 public:
 	struct Result {
@@ -1195,6 +1204,53 @@ public:
 			out[i].blockedEdge = r[i].blocked_edge;
 			out[i].blockedRatio = r[i].blocked_ratio;
 			out[i].validLength = r[i].valid_length;
+			out[i].length = r[i].length;
+		}
+		return out;
+	}
+	/// What Stamp says about one held plan (pp_stamp_result)
+	struct Stamped {
+		enum class Status { Stamped = 0, NoPlan = -1, PathTooLong = -4 };
+		Status status = Status::NoPlan;
+		int numSamples = 0;                                 // samples inside the window
+		int rowMin = 0, rowMax = -1, colMin = 0, colMax = -1; // the cells the plan covers inside the target; rowMin > rowMax: none
+		double length = 0.0;                                // length of the composite path
+		bool Empty() const { return rowMin > rowMax; }
+	};
+	/// Stamps the graph-search plans of held queries into the occupancy grid of `into`'s map (pp_pipeline_stamp; include/pp_hip.h has the definition):
+	/// every cell whose centre lies within a disc's radius + `margin` of a disc centre at a sample pose -- every `spacing` metres along the plan,
+	/// inside [fromLength[i], toLength[i]] -- becomes max(cell, values[i]).  The discs are the validator's footprint as the pipeline holds it, else the
+	/// point validator's disc.  `into`: nullptr is the pipeline's own validator (refused with queries in flight); another validator's map may have any
+	/// geometry and is legal beside queries in flight.  values / fromLength / toLength: empty, or one entry per ticket (empty: 0 / -inf / +inf).
+	/// The map's fields are NOT rebuilt: they are outdated afterwards, and the next search, re-validation or GVD::Update on that map builds them.
+	std::vector<Stamped> Stamp(const std::vector<uint64_t>& tickets, const Ref<StateValidatorOccupancyMap>& into, double spacing, float margin = 0.0f,
+		const std::vector<int32_t>& values = {}, const std::vector<double>& fromLength = {}, const std::vector<double>& toLength = {})
+	{
+		for (uint64_t t : tickets)
+			HeldOf(t); // (throws for a ticket that is not held)
+		const size_t n = tickets.size();
+		if ((!values.empty() && values.size() != n) || (!fromLength.empty() && fromLength.size() != n) || (!toLength.empty() && toLength.size() != n))
+			throw std::invalid_argument("Stamp: values, fromLength and toLength are empty or hold one entry per ticket");
+		std::vector<Stamped> out(n);
+		if (!m_pipe)
+			return out;
+		const Ref<StateValidatorOccupancyMap>& v = into ? into : m_validator;
+		pp_map* const target = v->Device(); // pushes host-side grids
+		if (InFlight() == 0)
+			SyncFootprint();
+		const pp_stamp_params sp { spacing, margin, 0 };
+		std::vector<pp_stamp_result> r(n);
+		ppCheck(pp_pipeline_stamp(m_pipe, target, (int32_t)n, tickets.data(), values.empty() ? nullptr : values.data(), fromLength.empty() ? nullptr : fromLength.data(),
+			toLength.empty() ? nullptr : toLength.data(), &sp, r.data()));
+		if (n > 0)
+			v->GetOccupancyMap()->OccupancyWrittenOnDevice();
+		for (size_t i = 0; i < n; i++) {
+			out[i].status = (Stamped::Status)r[i].status;
+			out[i].numSamples = r[i].n_samples;
+			out[i].rowMin = r[i].cell_box[0];
+			out[i].rowMax = r[i].cell_box[1];
+			out[i].colMin = r[i].cell_box[2];
+			out[i].colMax = r[i].cell_box[3];
 			out[i].length = r[i].length;
 		}
 		return out;

@@ -413,6 +413,18 @@ PYBIND11_MODULE(pyplanning, m)
 				return out;
 			},
 			py::arg("tickets"), py::arg("validator") = Ref<StateValidatorOccupancyMap>())
+		// held plans stamped into a map's occupancy grid: (status, n_samples, (row_min, row_max, col_min, col_max), length) per ticket.  validator=None: the
+		// pipeline's own validator's map (refused with queries in flight)
+		.def("stamp",
+			[](HybridAStarPipeline& h, const std::vector<uint64_t>& tickets, const Ref<StateValidatorOccupancyMap>& validator, double spacing, float margin,
+				const std::vector<int32_t>& values, const std::vector<double>& fromLength, const std::vector<double>& toLength) {
+				py::list out;
+				for (const auto& r : h.Stamp(tickets, validator, spacing, margin, values, fromLength, toLength))
+					out.append(py::make_tuple((int)r.status, r.numSamples, py::make_tuple(r.rowMin, r.rowMax, r.colMin, r.colMax), r.length));
+				return out;
+			},
+			py::arg("tickets"), py::arg("validator") = Ref<StateValidatorOccupancyMap>(), py::arg("spacing") = 0.1, py::arg("margin") = 0.0f,
+			py::arg("values") = std::vector<int32_t>(), py::arg("from_length") = std::vector<double>(), py::arg("to_length") = std::vector<double>())
 		.def("get_path", &HybridAStarPipeline::GetPath, py::arg("ticket"))
 		.def("get_graph_search_path", &HybridAStarPipeline::GetGraphSearchPath, py::arg("ticket"))
 		.def("get_smoothing_status", &HybridAStarPipeline::GetSmoothingStatus, py::arg("ticket"))

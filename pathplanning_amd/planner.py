@@ -12,7 +12,8 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import RS_PATH_DTYPE, FootprintDisc, HybridParams, MapDesc, PostResult, QueryResult, RevalidateResult, SmootherParams, check, ptr
+from ._lib import (RS_PATH_DTYPE, FootprintDisc, HybridParams, MapDesc, PostResult, QueryResult, RevalidateResult, SmootherParams, StampParams, StampResult, check,
+                   ptr)
 
 
 class Status:
@@ -690,6 +691,14 @@ class HybridAStarBatch:
         check(self.lib.pp_planner_revalidate(self.h, map_set.h if map_set is not None else None, n, out))
         return list(out)[:n]
 
+    def stamp(self, n_queries=None, map_set=None, values=None, from_length=None, to_length=None, spacing=0.1, margin=0.0):
+        """Stamps the plans of the first n queries of the last batch into the int32 occupancy grid of `map_set` (None: the planner's own
+        map): pp_planner_stamp, the batch form of HybridAStarPipeline.stamp, with the planner's footprint if it has one.  Returns one
+        StampResult per query."""
+        n = len(self._results) if n_queries is None else int(n_queries)
+        return _stamp(n, values, from_length, to_length, spacing, margin,
+                      lambda v, a, b, sp, out: self.lib.pp_planner_stamp(self.h, map_set.h if map_set is not None else None, n, ptr(v), ptr(a), ptr(b), C.byref(sp), out))
+
     def certify_lattice(self, q):
         """SURVEY 7.3 H2 as a contract (pp_planner_certify_lattice): created nodes and logged lattice-line children of query q recomputed on
         the host with glibc; returns (checked, cell mismatches, unverified events, largest pose difference).  mismatches == unverified == 0
@@ -1002,6 +1011,20 @@ class HybridAStarPipeline:
         check(self.lib.pp_pipeline_revalidate(self.h, map_set.h if map_set is not None else None, len(t), ptr(t), out))
         return list(out)[:len(t)]
 
+    def stamp(self, tickets, map_set=None, values=None, from_length=None, to_length=None, spacing=0.1, margin=0.0):
+        """Stamps the plans of the completed, HELD queries `tickets` into the int32 occupancy grid of `map_set` (an OccupancyMapSet of the
+        same context, any geometry; None: the pipeline's own map, refused with queries in flight): pp_pipeline_stamp, whose definition is in
+        include/pp_hip.h.  Every cell whose centre lies within r_i + margin of disc i's centre at a sample pose becomes max(cell, values[k]);
+        the samples lie every `spacing` metres along each edge (both ends included) inside [from_length[k], to_length[k]] metres from the
+        start (None: the whole plan).  The discs are the pipeline's footprint, else (0, 0, min_safe_radius) of the pipeline's own map.
+        Stamping another map than the pipeline's own is legal while other queries are in flight.  The target's distance fields are NOT
+        rebuilt: run update_gvd on it when they are to follow.  Returns one StampResult per ticket (status, n_samples, cell_box, length).
+        Raises PPError, with nothing launched or written, for a ticket that is unknown, released, in flight or given twice, a negative
+        value, a NaN in a window, a spacing that is not > 0 or a margin that is not >= 0."""
+        t = np.ascontiguousarray(tickets, dtype=np.uint64).reshape(-1)
+        return _stamp(len(t), values, from_length, to_length, spacing, margin,
+                      lambda v, a, b, sp, out: self.lib.pp_pipeline_stamp(self.h, map_set.h if map_set is not None else None, len(t), ptr(t), ptr(v), ptr(a), ptr(b), C.byref(sp), out))
+
     def get_expanded_of(self, ticket):
         """expansion sequence (log_expansions=True) of a completed query polled with release=False"""
         slot = self.lib.pp_pipeline_slot_of(self.h, C.c_uint64(int(ticket)))
@@ -1032,6 +1055,20 @@ class HybridAStarPipeline:
             self.close()
         except Exception:
             pass
+
+
+def _stamp(n, values, from_length, to_length, spacing, margin, call):
+    """the per-plan arrays of a stamp call as the C ABI takes them (None stays NULL; a scalar is given to every plan), the call, its records"""
+    def per_plan(x, dtype):
+        if x is None:
+            return None
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=dtype), (n,)) if np.ndim(x) == 0 else x, dtype=dtype).reshape(-1)
+        if len(a) != n:
+            raise ValueError("one entry per plan: got %d for %d plans" % (len(a), n))
+        return a
+    out = (StampResult * max(n, 1))()
+    check(call(per_plan(values, np.int32), per_plan(from_length, np.float64), per_plan(to_length, np.float64), StampParams(float(spacing), float(margin), 0), out))
+    return list(out)[:n]
 
 
 class _RRTBase:
