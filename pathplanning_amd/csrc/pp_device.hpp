@@ -242,7 +242,13 @@ struct Arc {
 /// The same arc with sin/cos of the initial heading supplied (they are stored with the node that is
 /// being expanded) and sin/cos of the interpolated heading returned: one sincos per sample instead of
 /// four libm calls.  A zero travelled distance returns the initial pose (x + 1/k*(sin t - sin t) = x).
-struct ArcSC {
+/// SinCos: who evaluates sincos(t) -- SinCosInline expands it at every use (the default: ArcSC); a kernel whose loop holds several uses
+/// may name a policy that calls ONE out-of-line copy instead (same function, same argument, same bits: pp_rows_rs.hpp).
+struct SinCosInline {
+	PPD_INLINE static void eval(double t, double& s, double& c) { sincos(t, &s, &c); }
+};
+template <typename SinCos>
+struct ArcSCT {
 	Pose init;
 	double sinF, cosF;
 	double kappa;
@@ -261,7 +267,7 @@ struct ArcSC {
 			return to;
 		if (fabs(kappa) > 1e-9) {
 			to.t += d * kappa;
-			sincos(to.t, &s, &c);
+			SinCos::eval(to.t, s, c);
 			to.x += invKappa * (s - sinF);
 			to.y += invKappa * (-c + cosF);
 		} else {
@@ -276,6 +282,7 @@ struct ArcSC {
 		return interpolate_sc(ratio, s, c);
 	}
 };
+using ArcSC = ArcSCT<SinCosInline>;
 
 /// An R2 segment seen as an SE2 path with theta = 0 (paths/path_r2.cpp:11-16)
 struct Segment {

@@ -224,7 +224,8 @@ PPD_INLINE float fp_border_sc(const MapView& m, const Footprint& fp, double x, d
 /// The same march over a constant-steer arc whose start pose has been checked already (is_path_valid_from): firstClearance is the
 /// footprint's clearance at the start pose, < 0 when that pose is invalid; sin / cos of every sample's heading come with the sample.
 /// Counts the first sample like is_path_valid_fp.
-PPD_INLINE bool is_arc_valid_fp_from(const MapView& m, const Footprint& fp, float gain, const ArcSC& path, float firstClearance, float& last, int& checks)
+template <typename SinCos>
+PPD_INLINE bool is_arc_valid_fp_from(const MapView& m, const Footprint& fp, float gain, const ArcSCT<SinCos>& path, float firstClearance, float& last, int& checks)
 {
 	const double pathLength = path.length;
 	if (pathLength == 0.0) {

@@ -284,6 +284,7 @@ struct PipeView {
 
 // The rows kernel's text is compiled twice (see the head of pp_planner_rows.hpp): k_hybrid_search_rows<kPiped>, then
 // k_hybrid_search_rows_footprint<kPiped>, of which only the pipeline form is instantiated (pp_pipeline_set_footprint).
+#include "pp_rows_rs.hpp" // their out-of-line pieces: the Reeds-Shepp attempt, a claimed query's initialisation
 #define PP_ROWS_FOOTPRINT 0
 #include "pp_planner_rows.hpp"
 #undef PP_ROWS_FOOTPRINT

@@ -23,6 +23,10 @@
 // Reeds-Shepp path valid" routed through it (pp_footprint_device.hpp; Node::dist0 and c_d0 then hold the footprint's clearance instead of
 // the obstacle distance).  The two differ in preprocessor branches only, so the point kernels' text is what it was before the second
 // kernel existed (a shared __device__ function template moved their spills: DESIGN.md section 4.8b).
+//
+// What a row enters rarely is NOT in this text: the Reeds-Shepp attempt (rows_rs_attempt), a claimed query's initialisation (rows_claim_init) and the
+// one copy of the arcs' f64 sincos (rows_arc_sincos) are called functions in pp_rows_rs.hpp, which also holds the staging struct they share with the
+// kernel.  The expansion loop is what eight waves per pair of compute units run out of one instruction cache; tests/test_search_code_layout.py gates its size.
 #ifndef PP_ROWS_FOOTPRINT
 #error "pp_planner_rows.hpp is the body of the rows kernels of pp_planner.hip, which defines PP_ROWS_FOOTPRINT before each include"
 #endif
@@ -124,21 +128,7 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 
 	// staging of the children of the node being expanded (per row); kept until the next expansion so that a child popped
 	// right away is read back from LDS instead of HBM
-	constexpr int kS = kRowsPerWave * kRowSlots;
-	struct WaveLds {
-		double c_x[kS], c_y[kS], c_t[kS], c_cost[kS], c_total[kS], c_len[kS], c_h[kS], c_sin[kS], c_cos[kS];
-		double f_x[kS], f_y[kS], f_t[kS], f_tot[kS]; // open-list node already in the child's cell (shortcut test)
-		HeapEntry spill[kRowsPerWave][kRowLanes];
-		// f-bands of the open list (pp_search_device.hpp): entries per ring slot, four u8 counters per word
-		uint32_t bandCnt[kRowsPerWave][kBands / 4];
-		uint32_t c_key[kS], c_state[kS], f_for[kS];
-		float c_d0[kS]; // obstacle distance at the child's pose (< 0: invalid state), see Node::dist0
-		int rsChecks[kRowsPerWave];
-		double rsPre[kRowsPerWave][24]; // rs::Path::make_prefix of the row's Reeds-Shepp attempt (23 doubles)
-		int16_t c_action[kS];
-		uint8_t c_flags[kS], c_valid[kS]; // flags: 1 = valid child, 2 = an earlier child of the batch shares its cell
-	};
-	static_assert(offsetof(WaveLds, bandCnt) % 16 == 0 && sizeof(WaveLds) % 16 == 0, "band counters are copied as uint4");
+	using WaveLds = RowsWaveLds; // (pp_rows_rs.hpp: the out-of-line pieces stage into it)
 	__shared__ __attribute__((aligned(16))) WaveLds s_wave[kW];
 	WaveLds& W = s_wave[threadIdx.x >> 6];
 	double *const c_x = W.c_x, *const c_y = W.c_y, *const c_t = W.c_t, *const c_cost = W.c_cost, *const c_total = W.c_total, *const c_len = W.c_len, *const c_h = W.c_h,
@@ -205,7 +195,7 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 			}
 		}
 		uint32_t hm = row_bits(__ballot(toHeap), lane);
-		if (hm) {
+		if (__builtin_expect(hm != 0u, false)) { // (heap overflow: 0.65 % of the entries)
 			wave_vmem_sync(); // earlier heap writes
 			if (rl == 0) {
 				int hs = heapSize;
@@ -262,6 +252,7 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 		// lowest non-empty band: ring scan from the window's bottom, every lane looks at four slots (one word) per step
 		long long bAbs = 0x7FFFFFFFFFFFFFFFll;
 		const int w0 = (int)(bandLo >> 2);
+#pragma unroll 1
 		for (int step = 0; step < kBands / 64; step++) {
 			const uint32_t w = bandCnt[(w0 + step * kRowLanes + rl) & (kBands / 4 - 1)];
 			const uint32_t hit = row_bits(__ballot(w != 0u), lane);
@@ -302,7 +293,7 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 		lowK = ~0ull;
 		lowS = ~0u;
 		// heap entries that come before the buffer's last entry (or, with an empty buffer, the heap's best) move in
-		while (heapSize > 0 && (frontCount == 0 || key_before(heapTop.ckey, heapTop.nseq, row_read64(front.ckey, lane, frontCount - 1), row_read(front.nseq, lane, frontCount - 1)))) {
+		while (__builtin_expect(heapSize > 0 && (frontCount == 0 || key_before(heapTop.ckey, heapTop.nseq, row_read64(front.ckey, lane, frontCount - 1), row_read(front.nseq, lane, frontCount - 1))), false)) {
 			wave_vmem_sync();
 			const HeapEntry he = heap_pop_row(ROW_HEAP, heapSize, rl, lane, heapTop);
 			wave_vmem_sync();
@@ -402,9 +393,17 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 #else
 #define ROWS_STAMP(ph)
 #endif
+	// finish() has ONE copy, at the head of the loop: a row whose query ends sets these three and jumps there.  They are assigned right before the
+	// jump and read right after it, so they are no row state and hold no register across the expansion loop.
+	int endStatus, endNode;
+	double endCost;
 	for (;;) {
+		if (false) {
+		row_query_ends:
+			finish(endStatus, endNode, endCost);
+		}
 		// ================= rows without a query take the next one =================
-		if (!act && !done) {
+		if (__builtin_expect(!act && !done, false)) {
 			bool none = false;
 			if (piped) {
 				// the ring's head entry, if it carries the stamp of its position (the wavefront kernel stores an entry after reserving its
@@ -444,23 +443,9 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 				if (order)
 					q = order[q]; // probable longest first (written by the wavefront kernel's last workgroup)
 				field = costFields + (size_t)q * A.fieldElems;
-				{ // the slot's key map still holds the previous query of this row
-					const size_t n = A.ks.size(), n4 = n / 4;
-					const uint4 z = { 0, 0, 0, 0 };
-					if ((((uintptr_t)keymap) & 15) == 0) {
-						for (size_t i = rl; i < n4; i += kRowLanes)
-							reinterpret_cast<uint4*>(keymap)[i] = z;
-						for (size_t i = n4 * 4 + rl; i < n; i += kRowLanes)
-							keymap[i] = 0;
-					} else {
-						for (size_t i = rl; i < n; i += kRowLanes)
-							keymap[i] = 0;
-					}
-					wave_vmem_sync();
-				}
-				// goal / start poses go through the Pose2d constructor on the caller's side (theta wrapped)
-				const Pose start = { starts[3 * q], starts[3 * q + 1], wrap_theta(starts[3 * q + 2]) };
-				goal = { goals[3 * q], goals[3 * q + 1], wrap_theta(goals[3 * q + 2]) };
+				// key map, band counters, engine state and root node of the slot: out of line (pp_rows_rs.hpp), once per query
+				const RowsClaim claim = rows_claim_init<PP_ROWS_FOOTPRINT != 0>(q, field, nodes, keymap, ROW_MT, bandCnt, starts, goals, seeds, rows_kernarg_segment());
+				goal = { claim.gx, claim.gy, claim.gt };
 				// ---- InitializeSearch, a_star.h:350-364
 				myNode = -1;
 				rsNode = -1;
@@ -476,10 +461,6 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 				bandLoSet = false;
 				lowK = ~0ull;
 				lowS = ~0u;
-				wave_lds_sync();
-				for (int i = rl; i < kBands / 4; i += kRowLanes)
-					bandCnt[i] = 0u;
-				wave_lds_sync();
 				heapTop.ckey = ~0ull;
 				heapTop.nseq = ~0u;
 				heapTop.node = 0;
@@ -487,47 +468,9 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 				seq = 1;
 				nExpanded = nRngDraws = nRsAttempts = nRsLog = 0;
 				laneStateChecks = lanePathChecks = rsStateChecks = rsPathChecks = 0;
-				if (rl == 0)
-					Mt64::seed(ROW_MT, seeds[q]);
 				mtIdx = Mt64::N; // engine freshly seeded: first draw twists
-				double rs_, rc_;
-				sincos(start.t, &rs_, &rc_);
-				int ix, iy, it;
-				const bool startOnBoundary = discretize_pose(start, A.rp.lat, A.rp.headingAlias, ix, iy, it);
 				if (rl == 0)
-					lanePathChecks += (long long)startOnBoundary << kGuardShift; // (guard band, pp_device.hpp: the count shares this counter's upper bits)
-				uint32_t key = kNoKey;
-				const bool ok = A.ks.pack(ix, iy, it, key);
-				if (rl == 0) {
-					Node root;
-					root.x = start.x;
-					root.y = start.y;
-					root.t = start.t;
-					root.pathCost = 0.0;
-					root.totalCost = 0.0;
-					root.length = 0.0;
-					root.h = combined_heuristic_sc(A.heur, m, field, goal, start, rs_, rc_);
-					root.sinT = rs_;
-					root.cosT = rc_;
-					root.parent = -1;
-					root.key = ok ? key : kNoKey;
-					root.action = -1;
-					root.dead = 0;
-#if PP_ROWS_FOOTPRINT
-					{
-						float cl, bd;
-						root.dist0 = fp_state_valid_sc(m, foot, start.x, start.y, start.t, rs_, rc_, cl, bd) ? cl : -1.0f;
-					}
-#else
-					{
-						float d0;
-						root.dist0 = is_state_valid(m, start.x, start.y, start.t, d0) ? d0 : -1.0f;
-					}
-#endif
-					nodes[0] = root;
-					if (ok)
-						keymap[key] = kExplored; // the root is inserted in the explored set at init (a_star.h:361)
-				}
+					lanePathChecks += (long long)claim.boundary << kGuardShift; // (guard band, pp_device.hpp: the count shares this counter's upper bits)
 				HeapEntry e;
 				e.ckey = cost_key(0.0);
 				e.nseq = 0xFFFFFFFFu;
@@ -545,7 +488,7 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 			statIter[__popcll(actMask) / kRowLanes]++;
 #endif
 		ROWS_STAMP(0) // taking queries
-		if (!actMask) {
+		if (__builtin_expect(!actMask, false)) {
 			if (!piped)
 				break; // every row has run out of queries
 			// ---- pipeline: every row is idle.  Leave when the host says so, when every submitted query has been claimed (a later
@@ -590,14 +533,14 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 			continue;
 
 		// ================= one step of SearchPath's main loop (a_star.h:337-345) for every active row =================
-		if (!(frontCount > 0 || nOutside > 0)) {
-			finish(-1, -1, __builtin_huge_val()); // open list exhausted: status -1
-			continue;
+		if (__builtin_expect(!(frontCount > 0 || nOutside > 0), false)) {
+			endStatus = -1, endNode = -1, endCost = __builtin_huge_val(); // open list exhausted: status -1
+			goto row_query_ends;
 		}
 		// ---- setting a query aside: once it has reached `suspendAfter` expansions its open list goes entirely into the heap,
 		// the scalars into a SuspendRec for the one-query-per-wave kernel, and the row continues with the next query in a spare slot
 		const bool capHit = !piped && suspendAfter > 0 && nExpanded >= suspendAfter && !noSuspend;
-		if (capHit) {
+		if (__builtin_expect(capHit, false)) {
 			int sp = 0;
 			if (rl == 0)
 				sp = atomicAdd(spareCount, 1);
@@ -660,12 +603,22 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 			}
 		}
 		ROWS_STAMP(1) // set-aside logic
+#if PP_ROWS_EAGER_REFILL
+		// refill() has ONE copy in the loop's text (1.7 k instructions): the pass before the pop refills an empty front buffer (nOutside > 0 then:
+		// the open list is not exhausted), the pass after it refills now rather than at the next pop, so that the prefetch below knows the
+		// probable next node
+		HeapEntry top;
+#pragma unroll 1
+		for (int pass = 0; pass < 2; pass++) {
+			if (frontCount == 0 && nOutside > 0)
+				refill();
+			if (pass == 0)
+				top = front_pop_row(front, frontCount, lane); // the front buffer holds the globally best entries
+		}
+#else
 		if (frontCount == 0)
 			refill();
 		const HeapEntry top = front_pop_row(front, frontCount, lane); // the front buffer holds the globally best entries
-#if PP_ROWS_EAGER_REFILL
-		if (frontCount == 0 && nOutside > 0)
-			refill(); // now rather than at the next pop: the prefetch below then knows the probable next node
 #endif
 		ROWS_STAMP(2) // pop + refill
 		const int ni = (int)top.node;
@@ -690,6 +643,11 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 				pDist0 = c_d0[sb + slot];
 			} else if (ni == pfNode) {
 				// lane k of the row holds the k-th 8-byte word of the record (see the prefetch below)
+				// (the lane index goes through an empty asm: the eleven source-lane addresses below are then computed here, one `or` each -- as
+				// loop invariants they were hoisted, held eleven registers across the whole loop and came back as eleven scratch loads)
+				int laneHere = lane;
+				asm volatile("" : "+v"(laneHere));
+				const int lane = laneHere;
 				auto d64 = [&](int k) { return __longlong_as_double((long long)row_read64(pf64, lane, k)); };
 				px = d64(0);
 				py = d64(1);
@@ -719,9 +677,9 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 		if (pDead)
 			continue; // entry of a node replaced by ProcessPossibleShortcut
 		const Pose ppose = { px, py, pt };
-		if (identical_poses(ppose, goal)) { // IsSolution, hybrid_a_star.h:193-196
-			finish(0, ni, pPathCost);
-			continue;
+		if (__builtin_expect(identical_poses(ppose, goal), false)) { // IsSolution, hybrid_a_star.h:193-196
+			endStatus = 0, endNode = ni, endCost = pPathCost;
+			goto row_query_ends;
 		}
 		// ---- Expand, a_star.h:377-409
 		if (rl == 0) {
@@ -753,7 +711,7 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 			double gcost = 0.0, total = 0.0, len = 0.0, hh = 0.0;
 			float d0 = -1.0f;
 			if (p < P) {
-				ArcSC a;
+				RowsArc a;
 				a.init = ppose;
 				a.sinF = pSin;
 				a.cosF = pCos;
@@ -994,9 +952,9 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 			}
 		}
 		ROWS_STAMP(9) // node records
-		if (capacity) {
-			finish(-4, -1, __builtin_huge_val());
-			continue;
+		if (__builtin_expect(capacity, false)) {
+			endStatus = -4, endNode = -1, endCost = __builtin_huge_val();
+			goto row_query_ends;
 		}
 
 		// ---- Reeds-Shepp analytic expansion, gated (hybrid_a_star.cpp:81-88): the RNG is drawn only when hCost >= 10
@@ -1014,114 +972,18 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 			nRngDraws++;
 			tryRs = u < 10.0 / (hCost * hCost);
 		}
-		if (tryRs) {
+		if (__builtin_expect(tryRs, false)) { // (0.9 % of the expansions: the call and the saves around it lie outside the fall-through path)
 			nRsAttempts++;
-			// GetOptimalPath (reeds_shepp.cpp:654-683): lane l evaluates words l, l + 16, l + 32
-			Pose rel;
-			{
-				// goal - start (geometry/2dplane.h:65-79) with the stored sin/cos of the node's heading
-				const double dx = goal.x - ppose.x, dy = goal.y - ppose.y;
-				const double s = -pSin, c = pCos;
-				rel.x = c * dx + (-s) * dy;
-				rel.y = s * dx + c * dy;
-				rel.t = wrap_theta(wrap_theta(goal.t - ppose.t));
-			}
-			rel.x = rel.x / A.rmin;
-			rel.y = rel.y / A.rmin;
-			float wcost = __builtin_huge_valf();
-			int wword = 0x7FFFFFFF;
-			double wt = 0, wu = 0, wv = 0;
-			for (int k = 0; k < rs::kNumWords / kRowLanes; k++) {
-				const int w = rl + kRowLanes * k;
-				double gx, gy, gt, t_, u_, v_;
-				rs::goal_variant(rel, w % 4, gx, gy, gt);
-				const double length = rs::base_lengths(w / 4, gx, gy, gt, t_, u_, v_);
-				if (!(length == rs::inf())) {
-					rs::Segment sg;
-					rs::word_segment(w, t_, u_, v_, sg);
-					const float cst = rs::compute_cost(sg, A.rmin, A.rsRev, A.rsFwd, A.rsSw);
-					// NaN and +inf never win a `cost < optimalCost` test; words ascend, so the first strict minimum is kept
-					if (cst < __builtin_huge_valf() && cst < wcost) {
-						wcost = cst;
-						wword = w;
-						wt = t_;
-						wu = u_;
-						wv = v_;
-					}
-				}
-			}
-			// first strictly-lowest float cost in word order (costs are >= 0: their bit patterns order like the values)
-			const uint32_t bestBits = row_min_u32(__float_as_uint(wcost));
-			const bool mine = wword != 0x7FFFFFFF && __float_as_uint(wcost) == bestBits;
-			const uint32_t wsel = row_min_u32(mine ? (uint32_t)wword : 0xFFFFFFFFu);
-			const int word = wsel == 0xFFFFFFFFu ? -1 : (int)wsel;
+			// the attempt itself -- GetOptimalPath over the 48 words, the winner's march, the candidate child's cost, heuristic and staging in slot
+			// kRowRs -- is a called function (pp_rows_rs.hpp): between one and four rows of the wave enter it, each whole
+			const RowsRsResult rsr = rows_rs_attempt<PP_ROWS_FOOTPRINT != 0>(px, py, pt, pSin, pCos, goal.x, goal.y, goal.t, pPathCost, field, keymap, &W, rows_kernarg_segment());
+			const int word = rsr.word;
 			if (word >= 0) {
-				const int owner = word & (kRowLanes - 1);
-				const double bt = row_read_f64(wt, lane, owner), bu = row_read_f64(wu, lane, owner), bv = row_read_f64(wv, lane, owner);
-				// the winner's path is validated by one lane (the adaptive march is sequential)
-				if (rl == 0) {
-					rs::Path path;
-					path.init = ppose;
-					rs::word_segment(word, bt, bu, bv, path.seg);
-					path.rmin = A.rmin;
-					path.length = path.seg.length * A.rmin; // PathSegment::GetLength
-					float lastRatio;
-					int checks = 0;
-					// every sample of the march continues from the stored start of its motion instead of walking the word from its
-					// beginning (same operations on the same values: rs::Path::make_prefix)
-					double* const pre = W.rsPre[lane >> 4];
-					path.make_prefix(pre);
-					const rs::PrefixedPath ppath = { path, pre, path.length };
-#if PP_ROWS_FOOTPRINT
-					const bool valid = is_path_valid_fp(m, foot, fp_gain(foot, 1.0 / A.rmin), ppath, path.init, lastRatio, checks);
-#else
-					const bool valid = is_path_valid(m, ppath, path.init, lastRatio, checks);
-#endif
-					c_valid[sb + kRowRs] = 0;
-					s_rsChecks[lane >> 4] = checks;
-					if (valid) {
-						const double pathAndSwitchingCosts = (double)rs::compute_cost(path.seg, A.rmin, A.rsRev, A.rsFwd, A.rsSw); // PathReedsShepp::ComputeCost
-						const Pose child = ppath.interpolate(1.0);
-						int ix, iy, it;
-						lanePathChecks += (long long)discretize_pose(child, A.rp.lat, A.rp.headingAlias, ix, iy, it) << kGuardShift;
-						const double voro = voronoi_cost(m, ppath, A.rp.voroDiagRes, A.rp.voronoiMult);
-						const double cost = pathAndSwitchingCosts + voro;
-						uint32_t key;
-						if (A.ks.pack(ix, iy, it, key)) {
-							double s_, c_;
-							sincos(child.t, &s_, &c_);
-							const double hh = combined_heuristic_sc(A.heur, m, field, goal, child, s_, c_);
-							c_valid[sb + kRowRs] = 1;
-							c_key[sb + kRowRs] = key;
-							c_x[sb + kRowRs] = child.x;
-							c_y[sb + kRowRs] = child.y;
-							c_t[sb + kRowRs] = child.t;
-							c_cost[sb + kRowRs] = pPathCost + cost;
-							c_total[sb + kRowRs] = (pPathCost + cost) + hh;
-							c_len[sb + kRowRs] = path.length;
-							c_h[sb + kRowRs] = hh;
-							c_sin[sb + kRowRs] = s_;
-							c_cos[sb + kRowRs] = c_;
-#if PP_ROWS_FOOTPRINT
-							{
-								float rd0, rb;
-								c_d0[sb + kRowRs] = fp_state_valid_sc(m, foot, child.x, child.y, child.t, s_, c_, rd0, rb) ? rd0 : -1.0f;
-							}
-#else
-							{
-								float rd0;
-								c_d0[sb + kRowRs] = is_state_valid(m, child.x, child.y, child.t, rd0) ? rd0 : -1.0f;
-							}
-#endif
-							c_state[sb + kRowRs] = keymap[key];
-							c_action[sb + kRowRs] = (int16_t)(1000 + word);
-						}
-					}
-				}
-				wave_lds_sync();
+				const double bt = rsr.t, bu = rsr.u, bv = rsr.v;
+				lanePathChecks += (long long)rsr.boundary << kGuardShift;
 				rsPathChecks++;
-				rsStateChecks += (long long)s_rsChecks[lane >> 4];
-				if (c_valid[sb + kRowRs]) {
+				rsStateChecks += (long long)rsr.checks;
+				if (rsr.valid) {
 					const uint32_t ckey = c_key[sb + kRowRs];
 					const uint32_t cst = c_state[sb + kRowRs];
 					bool push = false;
@@ -1155,8 +1017,8 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 					}
 					if (push) {
 						if (nNodes >= maxNodes) {
-							finish(-4, -1, __builtin_huge_val());
-							continue;
+							endStatus = -4, endNode = -1, endCost = __builtin_huge_val();
+							goto row_query_ends;
 						}
 						const int idx = nNodes++;
 						if (rl == 0) {

@@ -14,23 +14,39 @@ namespace rs {
 	constexpr int kFwd = 0, kBwd = 1, kNoMotion = 2;
 
 	PPD_INLINE double inf() { return __builtin_huge_val(); }
+
+	/// Math: who evaluates the libm calls of the formulas below.  MathInline (the default everywhere) expands them at every use; a kernel that
+	/// wants the solver's text small names a policy whose members call one out-of-line copy of each (pp_rows_rs.hpp) -- the same functions on
+	/// the same arguments, hence the same bits.
+	struct MathInline {
+		PPD_INLINE static double sin(double x) { return ::sin(x); }
+		PPD_INLINE static double cos(double x) { return ::cos(x); }
+		PPD_INLINE static double atan2(double y, double x) { return ::atan2(y, x); }
+		PPD_INLINE static double acos(double x) { return ::acos(x); }
+		PPD_INLINE static double asin(double x) { return ::asin(x); }
+		PPD_INLINE static double fmod(double x, double y) { return ::fmod(x, y); }
+	};
+
+	template <typename Math = MathInline>
 	PPD_INLINE double modulo(double in, double mod)
 	{
 		// utils/maths.h:9-16
-		double out = fmod(in, mod);
+		double out = Math::fmod(in, mod);
 		if (out < 0)
 			out += mod;
 		return out;
 	}
 	PPD_INLINE bool angle_invalid(double th) { return th < 0 || th > kPi; }          // reeds_shepp.cpp:11-14
-	PPD_INLINE double wrap_angle(double th) { return modulo(th + kPi, 2 * kPi) - kPi; } // reeds_shepp.cpp:16-19
+	template <typename Math = MathInline>
+	PPD_INLINE double wrap_angle(double th) { return modulo<Math>(th + kPi, 2 * kPi) - kPi; } // reeds_shepp.cpp:16-19
 
 	/// SE(2) `lhs - rhs`, geometry/2dplane.h:65-79
+	template <typename Math = MathInline>
 	PPD_INLINE Pose between(const Pose& lhs, const Pose& rhs)
 	{
 		const double dx = lhs.x - rhs.x, dy = lhs.y - rhs.y;
 		const double a = -rhs.t;
-		const double s = sin(a), c = cos(a);
+		const double s = Math::sin(a), c = Math::cos(a);
 		Pose out;
 		out.x = c * dx + (-s) * dy;
 		out.y = s * dx + c * dy;
@@ -38,9 +54,10 @@ namespace rs {
 		return out;
 	}
 	/// SE(2) `lhs + rhs`, geometry/2dplane.h:49-62 (rhs.t already wrapped by its constructor)
+	template <typename Math = MathInline>
 	PPD_INLINE Pose compose(const Pose& lhs, const Pose& rhs)
 	{
-		const double s = sin(lhs.t), c = cos(lhs.t);
+		const double s = Math::sin(lhs.t), c = Math::cos(lhs.t);
 		Pose out;
 		out.x = c * rhs.x + (-s) * rhs.y;
 		out.y = s * rhs.x + c * rhs.y;
@@ -52,9 +69,10 @@ namespace rs {
 	}
 
 	/// The twelve base-word formulas, reeds_shepp.cpp:21-304.  family = word / 4.
+	template <typename Math = MathInline>
 	PPD_INLINE double base_lengths(int family, double gx, double gy, double gt, double& t, double& u, double& v)
 	{
-		const double sg = sin(gt), cg = cos(gt);
+		const double sg = Math::sin(gt), cg = Math::cos(gt);
 		// families 0,2,3,4,7,9 use (x - sin, y - 1 + cos); the others (x + sin, y - 1 - cos)
 		const bool minusForm = (family == 0 || family == 2 || family == 3 || family == 4 || family == 7 || family == 9);
 		const double xi = minusForm ? gx - sg : gx + sg;
@@ -62,19 +80,19 @@ namespace rs {
 		switch (family) {
 		case 0: { // LfSfLf
 			u = sqrt(xi * xi + eta * eta);
-			t = atan2(eta, xi);
-			v = wrap_angle(gt - t);
+			t = Math::atan2(eta, xi);
+			v = wrap_angle<Math>(gt - t);
 			if (angle_invalid(t) || angle_invalid(v))
 				return inf();
 			return t + u + v;
 		}
 		case 1: { // LfSfRf -- the `u1squared < 4` test has no return in the reference (NaN flows on)
 			double u1squared = xi * xi + eta * eta;
-			double t1 = atan2(eta, xi);
+			double t1 = Math::atan2(eta, xi);
 			u = sqrt(u1squared - 4);
-			double phi = atan2(2.0, u);
-			t = wrap_angle(t1 + phi);
-			v = wrap_angle(t - gt);
+			double phi = Math::atan2(2.0, u);
+			t = wrap_angle<Math>(t1 + phi);
+			v = wrap_angle<Math>(t - gt);
 			if (angle_invalid(t) || angle_invalid(v))
 				return inf();
 			return t + u + v;
@@ -83,8 +101,8 @@ namespace rs {
 			double u1 = sqrt(xi * xi + eta * eta);
 			if (u1 > 4)
 				return inf();
-			double phi = atan2(eta, xi);
-			double alpha = acos(u1 / 4.0);
+			double phi = Math::atan2(eta, xi);
+			double alpha = Math::acos(u1 / 4.0);
 			t = modulo(kPi2 + alpha + phi, 2 * kPi);
 			u = modulo(kPi - 2 * alpha, 2 * kPi);
 			v = modulo(gt - t - u, 2 * kPi);
@@ -96,8 +114,8 @@ namespace rs {
 			double u1 = sqrt(xi * xi + eta * eta);
 			if (u1 > 4)
 				return inf();
-			double phi = atan2(eta, xi);
-			double alpha = acos(u1 / 4.0);
+			double phi = Math::atan2(eta, xi);
+			double alpha = Math::acos(u1 / 4.0);
 			t = modulo(kPi2 + alpha + phi, 2 * kPi);
 			u = modulo(kPi - 2 * alpha, 2 * kPi);
 			v = modulo(t + u - gt, 2 * kPi);
@@ -107,10 +125,10 @@ namespace rs {
 			double u1 = sqrt(xi * xi + eta * eta);
 			if (u1 > 4)
 				return inf();
-			double phi = atan2(eta, xi);
-			u = acos((8 - u1 * u1) / 8.0);
-			double va = sin(u);
-			double alpha = asin(2 * va / u1);
+			double phi = Math::atan2(eta, xi);
+			u = Math::acos((8 - u1 * u1) / 8.0);
+			double va = Math::sin(u);
+			double alpha = Math::asin(2 * va / u1);
 			t = modulo(kPi2 - alpha + phi, 2 * kPi);
 			v = modulo(t - u - gt, 2 * kPi);
 			return t + u + v;
@@ -119,14 +137,14 @@ namespace rs {
 			double u1 = sqrt(xi * xi + eta * eta);
 			if (u1 > 4)
 				return inf();
-			double phi = atan2(eta, xi);
+			double phi = Math::atan2(eta, xi);
 			if (u1 > 2) {
-				double alpha = acos(u1 / 4 - 0.5);
+				double alpha = Math::acos(u1 / 4 - 0.5);
 				t = modulo(kPi2 + phi - alpha, 2 * kPi);
 				u = modulo(kPi - alpha, 2 * kPi);
 				v = modulo(gt - t + 2 * u, 2 * kPi);
 			} else {
-				double alpha = acos(u1 / 4 + 0.5);
+				double alpha = Math::acos(u1 / 4 + 0.5);
 				t = modulo(kPi2 + phi + alpha, 2 * kPi);
 				u = modulo(alpha, 2 * kPi);
 				v = modulo(gt - t + 2 * u, 2 * kPi);
@@ -137,13 +155,13 @@ namespace rs {
 			double u1 = sqrt(xi * xi + eta * eta);
 			if (u1 > 6)
 				return inf();
-			double phi = atan2(eta, xi);
+			double phi = Math::atan2(eta, xi);
 			double va1 = 1.25 - u1 * u1 / 16;
 			if (va1 < 0 || va1 > 1)
 				return inf();
-			u = acos(va1);
-			double va2 = sin(u);
-			double alpha = asin(2 * va2 / u1);
+			u = Math::acos(va1);
+			double va2 = Math::sin(u);
+			double alpha = Math::asin(2 * va2 / u1);
 			t = modulo(kPi2 + phi + alpha, 2 * kPi);
 			v = modulo(t - gt, 2 * kPi);
 			return t + u + u + v;
@@ -152,11 +170,11 @@ namespace rs {
 			double u1squared = xi * xi + eta * eta;
 			if (u1squared < 4)
 				return inf();
-			double phi = atan2(eta, xi);
+			double phi = Math::atan2(eta, xi);
 			u = sqrt(u1squared - 4) - 2;
 			if (u < 0)
 				return inf();
-			double alpha = atan2(2.0, u + 2);
+			double alpha = Math::atan2(2.0, u + 2);
 			t = modulo(kPi2 + phi + alpha, 2 * kPi);
 			v = modulo(t + kPi2 - gt, 2 * kPi);
 			return t + kPi2 + u + v;
@@ -165,7 +183,7 @@ namespace rs {
 			double u1 = sqrt(xi * xi + eta * eta);
 			if (u1 < 2)
 				return inf();
-			double phi = atan2(eta, xi);
+			double phi = Math::atan2(eta, xi);
 			t = modulo(kPi2 + phi, 2 * kPi);
 			u = u1 - 2;
 			v = modulo(gt - t - kPi2, 2 * kPi);
@@ -175,11 +193,11 @@ namespace rs {
 			double u1squared = xi * xi + eta * eta;
 			if (u1squared < 4)
 				return inf();
-			double phi = atan2(eta, xi);
+			double phi = Math::atan2(eta, xi);
 			u = sqrt(u1squared - 4) - 2;
 			if (u < 0)
 				return inf();
-			double alpha = atan2(u + 2, 2.0);
+			double alpha = Math::atan2(u + 2, 2.0);
 			t = modulo(kPi2 + phi - alpha, 2 * kPi);
 			v = modulo(t - kPi2 - gt, 2 * kPi);
 			return t + u + kPi2 + v;
@@ -188,7 +206,7 @@ namespace rs {
 			double u1 = sqrt(xi * xi + eta * eta);
 			if (u1 < 2)
 				return inf();
-			double phi = atan2(eta, xi);
+			double phi = Math::atan2(eta, xi);
 			t = modulo(phi, 2 * kPi);
 			u = u1 - 2;
 			v = modulo(-t - kPi2 + gt, 2 * kPi);
@@ -198,11 +216,11 @@ namespace rs {
 			double u1squared = xi * xi + eta * eta;
 			if (u1squared < 16)
 				return inf();
-			double phi = atan2(eta, xi);
+			double phi = Math::atan2(eta, xi);
 			u = sqrt(u1squared - 4) - 4;
 			if (u < 0)
 				return inf();
-			double alpha = atan2(2.0, u + 4);
+			double alpha = Math::atan2(2.0, u + 4);
 			t = modulo(kPi2 + phi + alpha, 2 * kPi);
 			v = modulo(t - gt, 2 * kPi);
 			return t + u + v + kPi;
@@ -310,7 +328,8 @@ namespace rs {
 	}
 
 	/// PathReedsShepp with Interpolate / Straight / Turn, paths/path_reeds_shepp.cpp:12-47,123-153
-	struct Path {
+	template <typename Math>
+	struct PathT {
 		Pose init;
 		Segment seg;
 		double rmin;
@@ -322,8 +341,8 @@ namespace rs {
 				len = -len;
 			len *= rmin;
 			Pose e;
-			e.x = start.x + len * cos(start.t);
-			e.y = start.y + len * sin(start.t);
+			e.x = start.x + len * Math::cos(start.t);
+			e.y = start.y + len * Math::sin(start.t);
 			e.t = wrap_theta(start.t);
 			return e;
 		}
@@ -332,8 +351,8 @@ namespace rs {
 			if (dir == kBwd)
 				turnAngle = -turnAngle;
 			double phi = turnAngle / 2;
-			double cosPhi = cos(phi);
-			double sinPhi = sin(phi);
+			double cosPhi = Math::cos(phi);
+			double sinPhi = Math::sin(phi);
 			double L = 2 * sinPhi * rmin;
 			double x = L * cosPhi;
 			double y = L * sinPhi;
@@ -345,7 +364,7 @@ namespace rs {
 			rel.x = x;
 			rel.y = y;
 			rel.t = wrap_theta(turnAngle);
-			return compose(start, rel);
+			return compose<Math>(start, rel);
 		}
 		PPD_INLINE Pose interpolate(double ratio) const
 		{
@@ -509,6 +528,7 @@ namespace rs {
 			return count;
 		}
 	};
+	using Path = PathT<MathInline>;
 
 	/// ReedsShepp::Solver::GetOptimalPath, reeds_shepp.cpp:654-683: one thread, all 48 words.
 	/// Returns the word (-1 if none); tuv/cost/segLength of the winner.
@@ -544,12 +564,14 @@ namespace rs {
 	}
 
 /// a Path seen through its prefix (Path::make_prefix): what is_path_valid / voronoi_cost need -- `length` and `interpolate`
-struct PrefixedPath {
-	const Path& path;
+template <typename Math>
+struct PrefixedPathT {
+	const PathT<Math>& path;
 	const double* pre;
 	double length;
 	PPD_INLINE Pose interpolate(double ratio) const { return path.interpolate_prefix(pre, ratio); }
 };
+using PrefixedPath = PrefixedPathT<MathInline>;
 
 } // namespace rs
 } // namespace ppd
