@@ -607,6 +607,61 @@ int pp_pipeline_stamp(pp_pipeline* pipeline, pp_map* target /* NULL: the pipelin
  * footprint if it has one.  PP_ERR_INVALID as above, and for a planner that is a pipeline's buffer set (pp_pipeline_stamp knows which slots are held). */
 int pp_planner_stamp(pp_planner* planner, pp_map* target /* NULL: own map */, int32_t n_queries, const int32_t* values, const double* from_length,
 	const double* to_length, const pp_stamp_params* params, pp_stamp_result* results_host);
+/* ---- locating vehicles on held plans, by ticket -----------------------------------------------------------------------------------------
+ * To LOCATE a vehicle on a plan is to find the point of the plan closest to the vehicle's pose: its arc length (what windows pp_pipeline_stamp and
+ * what pp_revalidate_result::valid_length is read against), the edge and ratio, the path pose there, the cross-track and heading errors a controller
+ * steers on, and the travel direction.  One wave per plan (k_locate_tickets) reads the plan where the search left it.  It reads no map and writes
+ * nothing but its own result records, so the call is legal beside queries in flight without exception.  All arithmetic below is in double, in the
+ * order written (the library is built without contraction).
+ *  Inputs.  poses_host[n][3]: the vehicle poses (x, y, theta), one per ticket.  from_length / to_length: per-ticket windows of arc length with the
+ *           stamp's meaning (NULL array: -inf / +inf).  params: spacing (finite, > 0, metres) and heading_weight w (finite, >= 0, metres per radian).
+ *  Samples. The stamp's schedule, exactly: edges 1 .. n_path - 1 root first; S_e the sequential root-first sum, so `length` has
+ *           pp_revalidate_result::length's bits; edge e of length L has n = L > 0 ? (int)ceil(L / spacing) : 0 steps (capped at 2^19) and the samples
+ *           (double)k / (double)n for k = 0 .. n, at arc length s = S_e + ratio * L; a sample takes part iff from <= s <= to.  A one-pose plan has one
+ *           sample: its pose, at s = 0.
+ *  Cost.    Of a path pose P = (px, py, ptheta) for the vehicle V = (vx, vy, vtheta): ex = vx - px, ey = vy - py; dtheta = a - TWO_PI * rint(a / TWO_PI)
+ *           with a = vtheta - ptheta and TWO_PI = 6.283185307179586; c = (ex ex + ey ey) + (w dtheta)(w dtheta).  Candidates are ordered by (c, s): the
+ *           smaller c wins, on equal c the smaller s.  One point of the plan has one name: a junction pose is sampled twice, as the end of edge e
+ *           (ratio 1) and as the start of edge e + 1 (ratio 0), at one arc length; the second is the candidate, the first only counts in n_samples
+ *           (the two poses are equal up to rounding, which must not choose the edge).  A candidate equal in c and s to the best so far does not
+ *           replace it (the stage-1 winner stays against the lattice point under it: the same edge, ratio and pose).  The heading term chooses between
+ *           the two branches at a cusp or a self-crossing; the window does the same for a caller that knows roughly where the vehicle was.
+ *  Stage 1. The winner among the samples inside the window, at arc length s1.  No sample inside the window: status 1.
+ *  Stage 2. (Skipped for a one-pose plan.)  delta = spacing / 32, i0 = (int64) floor(s1 / delta).  For i = i0 - 32 .. i0 + 33: u = (double)i * delta is
+ *           a candidate iff 0 <= u <= length and from <= u <= to.  Its edge is the largest e with S_e <= u, its ratio L_e > 0 ? (u - S_e) / L_e : 0,
+ *           capped at 1, its pose the edge's interpolation at that ratio, its s is u itself.  The lattice i * delta is global, not centred on s1: two
+ *           near-equal stage-1 winners next to each other refine over the same points.
+ *  Result.  The minimum over the stage-1 winner and the stage-2 candidates.  The resolution along the plan is spacing / 32 where the cost has one
+ *           minimum within `spacing` of the best sample.  The library picks no spacing for the caller.
+ *  - PP_ERR_INVALID, nothing launched, the pipeline usable as before, the message naming the first offending ticket or argument: n < 0 or
+ *    n > capacity; a ticket that is unknown, released, still in flight or given twice; NULL poses_host or NULL params with n > 0; a spacing that is not
+ *    finite and > 0, a heading_weight that is not finite and >= 0; a vehicle pose that is not finite; a NaN in a window array.  n == 0 is PP_OK.
+ *  - The pipeline owns the slot list, the per-ticket arguments and the result buffer (4 + 40 + 96 bytes per ticket of the largest call so far), kept
+ *    aside like the post-processing buffers when they have to grow beside queries in flight. */
+typedef struct pp_locate_params {
+	double spacing;        /* > 0, finite, metres: the sample spacing of stage 1; the result's resolution is spacing / 32 */
+	double heading_weight; /* >= 0, finite, metres per radian */
+} pp_locate_params;
+typedef struct pp_locate_result {
+	int32_t status;        /* 0 located; 1 no sample in the window; -1 no plan; -4 path longer than the planner's path capacity */
+	int32_t edge;          /* 1 .. n_path - 1, root first; 0 for a one-pose plan */
+	int32_t direction;     /* +1 forward, -1 reverse: the travel direction of the edge at the ratio */
+	int32_t n_samples;     /* stage-1 samples inside the window */
+	double  s;             /* arc length of the located point, metres from the start */
+	double  ratio;         /* position on the edge, 0 .. 1 */
+	double  distance;      /* sqrt(ex ex + ey ey) */
+	double  along;         /* cos(ptheta) ex + sin(ptheta) ey */
+	double  lateral;       /* cos(ptheta) ey - sin(ptheta) ex: positive, the vehicle is to the left of the path pose */
+	double  heading_error; /* dtheta */
+	double  length;        /* pp_revalidate_result::length, bit for bit */
+	double  pose[3];       /* the path pose, theta as interpolated */
+} pp_locate_result;        /* 96 bytes; for status != 0 every field but status, n_samples and length is zero */
+int pp_pipeline_locate(pp_pipeline* pipeline, int32_t n, const uint64_t* tickets, const double* poses_host, const double* from_length, const double* to_length,
+	const pp_locate_params* params, pp_locate_result* results_host /* may be NULL */);
+/* The same kernel over the first n_queries queries of the planner's last batch (identity slots), on the planner's stream.  PP_ERR_INVALID as above,
+ * and for a planner that is a pipeline's buffer set (pp_pipeline_locate knows which slots are held). */
+int pp_planner_locate(pp_planner* planner, int32_t n_queries, const double* poses_host, const double* from_length, const double* to_length,
+	const pp_locate_params* params, pp_locate_result* results_host);
 /* Diagnostics: waves of the search grid that are alive right now (a blocking device-to-host copy; -1 on error). */
 int pp_pipeline_alive_waves(pp_pipeline* pipeline);
 pp_planner* pp_pipeline_planner(pp_pipeline* pipeline);           /* the buffer set: set_nonholo_table, set_primitives, get_path(slot), ... */

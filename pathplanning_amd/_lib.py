@@ -98,6 +98,20 @@ class StampResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("n_samples", C.c_int32), ("cell_box", C.c_int32 * 4), ("length", C.c_double)]
 
 
+class LocateParams(C.Structure):
+    """pp_locate_params: sample spacing of stage 1 along the plan (> 0, metres; the result's resolution is spacing / 32) and the weight of the
+    heading difference in the cost (>= 0, metres per radian)"""
+    _fields_ = [("spacing", C.c_double), ("heading_weight", C.c_double)]
+
+
+class LocateResult(C.Structure):
+    """pp_locate_result: status 0 located, 1 no sample in the window, -1 no plan, -4 path beyond the path capacity; the located point's edge
+    (1 .. n_path - 1; 0 for a one-pose plan), travel direction (+1 / -1), arc length s, ratio on the edge and path pose; the vehicle's distance,
+    along / lateral offsets in the path pose's frame (lateral > 0: left of it) and heading error; for status != 0 all of these are zero"""
+    _fields_ = [("status", C.c_int32), ("edge", C.c_int32), ("direction", C.c_int32), ("n_samples", C.c_int32), ("s", C.c_double), ("ratio", C.c_double),
+                ("distance", C.c_double), ("along", C.c_double), ("lateral", C.c_double), ("heading_error", C.c_double), ("length", C.c_double), ("pose", C.c_double * 3)]
+
+
 class GridResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("n_path", C.c_int32), ("n_expanded", C.c_int32), ("n_expanded_reverse", C.c_int32), ("cost", C.c_double)]
 
@@ -224,6 +238,8 @@ def load():
     L.pp_planner_revalidate.argtypes = [vp, vp, C.c_int32, vp]
     L.pp_pipeline_stamp.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, C.POINTER(StampParams), vp]
     L.pp_planner_stamp.argtypes = [vp, vp, C.c_int32, vp, vp, vp, C.POINTER(StampParams), vp]
+    L.pp_pipeline_locate.argtypes = [vp, C.c_int32, vp, vp, vp, vp, C.POINTER(LocateParams), vp]
+    L.pp_planner_locate.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(LocateParams), vp]
     L.pp_pipeline_timings.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.pp_pipeline_backlog.argtypes = [vp, vp, vp]
     L.pp_pipeline_planner.argtypes = [vp]

@@ -134,6 +134,34 @@ def build_stamp_rule_test(verbose=True):
     return out
 
 
+def build_pipeline_locate_test(verbose=True):
+    """tests/cpp/test_pipeline_locate.cpp: Locate(tickets, poses) of HybridAStarPipeline against the plan's path objects searched point by point (run on the GPU box)."""
+    build()
+    out = os.path.join(LIB_DIR, "test_pipeline_locate")
+    src = os.path.join(HERE, "..", "tests", "cpp", "test_pipeline_locate.cpp")
+    cmd = ["g++", "-O2", "-std=c++17", src, "-o", out, "-L" + LIB_DIR, "-lpphip", "-Wl,-rpath,$ORIGIN"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return out
+
+
+def build_locate_rule_test(verbose=True):
+    """tests/cpp/test_locate_rule.cpp: the wrap, the cost, the order, the lattice and the arc length -> (edge, ratio) mapping of a locate call
+    (csrc/pp_locate_rule.hpp) alone, on the CPU, under the address and undefined-behaviour sanitizers; without contraction, as the library is built."""
+    os.makedirs(LIB_DIR, exist_ok=True)
+    out = os.path.join(LIB_DIR, "test_locate_rule")
+    src = os.path.join(HERE, "..", "tests", "cpp", "test_locate_rule.cpp")
+    headers = [os.path.join(CSRC, "pp_locate_rule.hpp"), os.path.join(CSRC, "pp_stamp_rule.hpp")]
+    if os.path.exists(out) and os.path.getmtime(out) > max(os.path.getmtime(f) for f in [src] + headers):
+        return out
+    cmd = ["g++", "-std=c++17", "-g", "-O1", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC, src, "-o", out]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return out
+
+
 def build_ticket_table_test(verbose=True):
     """tests/cpp/test_ticket_table.cpp: the pipeline's slot and ticket bookkeeping (csrc/pp_ticket_table.hpp) alone, on the CPU, under the address and
     undefined-behaviour sanitizers."""
@@ -172,5 +200,7 @@ if __name__ == "__main__":
     print(build_pipeline_revalidate_test())
     print(build_pipeline_stamp_test())
     print(build_stamp_rule_test())
+    print(build_pipeline_locate_test())
+    print(build_locate_rule_test())
     print(build_ticket_table_test())
     print(build_row_test())

@@ -226,6 +226,11 @@ struct pp_pipeline {
 	pph::Dev<StampArg> stampArgs;
 	pph::Dev<pp_stamp_result> stampOut;
 	size_t stampRows = 0;
+	// pp_pipeline_locate (k_locate_tickets): the slot list, the vehicle poses and windows, and the results of a call, by compact index
+	pph::Dev<int32_t> locateSlots;
+	pph::Dev<LocateArg> locateArgs;
+	pph::Dev<pp_locate_result> locateOut;
+	size_t locateRows = 0;
 	int nWf = 2;      // wavefront streams in use: consecutive submissions' launches overlap (the tail of one under the head of the next)
 	int wfBlocks = 0; // workgroups per wavefront launch (<= the resident number): the wavefront kernel's share of the chip
 };
@@ -640,7 +645,7 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 			return PP_ERR_INVALID;
 		}
 	}
-	// an empty dispatch of the kernels pp_pipeline_postprocess, pp_pipeline_revalidate and pp_pipeline_stamp launch, on the stream they use: the queue allocates their scratch here,
+	// an empty dispatch of the kernels pp_pipeline_postprocess, pp_pipeline_revalidate, pp_pipeline_stamp and pp_pipeline_locate launch, on the stream they use: the queue allocates their scratch here,
 	// where a failure is an error code (see warm_up_kernels)
 	auto warmUp = [&](const char* what, auto&& launchEmpty) -> int {
 		launchEmpty();
@@ -665,6 +670,8 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 	if (int rc = warmUp("pipeline stamp kernel warm-up (scratch allocation)", [&] {
 			(void)launch_stamp(P->ctlStream, pl->args, Footprint {}, nullptr, 0, nullptr, nullptr, pl, nullptr, nullptr);
 		}))
+		return rc;
+	if (int rc = warmUp("pipeline locate kernel warm-up (scratch allocation)", [&] { (void)launch_locate(P->ctlStream, pl->args, nullptr, 0, nullptr, nullptr, pl, nullptr); }))
 		return rc;
 	std::memset(P->done, 0, ring * sizeof(PipeDone));
 	std::memset(P->errFlags, 0, 64);
@@ -1293,6 +1300,43 @@ int pp_pipeline_stamp(pp_pipeline* P, pp_map* target, int32_t n, const uint64_t*
 	PP_HIP_TRY(staged);
 	if (int rc = stamp_finish_target(map))
 		return rc;
+	records_out(host, results_host);
+	return PP_OK;
+}
+
+/// The vehicles of n completed, held queries located on their plans (include/pp_hip.h).  The kernel reads the held slots' plan records and writes its own
+/// result records: no map is read or written, so the view the launch travels with is the pipeline's own and the call is legal beside queries in flight.
+int pp_pipeline_locate(pp_pipeline* P, int32_t n, const uint64_t* tickets, const double* poses_host, const double* from_length, const double* to_length,
+	const pp_locate_params* params, pp_locate_result* results_host)
+{
+	if (int rc = pipe_check(P))
+		return rc;
+	if (n < 0 || n > P->capacity || (n > 0 && !tickets)) {
+		set_error("invalid arguments (0 <= n <= capacity = " + std::to_string(P->capacity) + ", got n = " + std::to_string(n) + ")");
+		return PP_ERR_INVALID;
+	}
+	pp_planner* pl = P->pl;
+	std::vector<LocateArg> plans;
+	if (int rc = locate_check(n, poses_host, from_length, to_length, params, [&](int i) { return "ticket " + std::to_string(tickets[i]); }, plans))
+		return rc;
+	std::vector<int32_t> slots;
+	if (int rc = pipe_resolve(P, n, tickets, "located", true, slots))
+		return rc;
+	if (n == 0)
+		return PP_OK;
+	PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
+	PP_HIP_TRY(pipe_grow(P, P->locateRows, (size_t)n,
+		{ { &P->locateSlots, (size_t)n * 4 }, { &P->locateArgs, (size_t)n * sizeof(LocateArg) }, { &P->locateOut, (size_t)n * sizeof(pp_locate_result) } }));
+	std::vector<pp_locate_result> host;
+	hipError_t staged = hipSuccess;
+	if (int rc = pipe_run_held(P, slots, P->viewValid ? P->lastView : pl->map->view(), P->locateSlots.get(), P->locateOut.get(), host,
+			[&](const SearchArgs& args, const Footprint&, int count, const int32_t* slotsDev) {
+				staged = hipMemcpyAsync(P->locateArgs.get(), plans.data(), (size_t)count * sizeof(LocateArg), hipMemcpyHostToDevice, P->ctlStream); // (pageable: staged at once)
+				if (staged == hipSuccess)
+					(void)launch_locate(P->ctlStream, args, params, count, slotsDev, P->locateArgs.get(), pl, P->locateOut.get());
+			}))
+		return rc;
+	PP_HIP_TRY(staged);
 	records_out(host, results_host);
 	return PP_OK;
 }

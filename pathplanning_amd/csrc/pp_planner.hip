@@ -18,6 +18,7 @@
 #include "pp_search_device.hpp"
 #include "pp_row_primitives.hpp"
 #include "pp_stamp_rule.hpp"
+#include "pp_locate_rule.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -302,6 +303,8 @@ struct PipeView {
 #include "pp_revalidate.hpp"
 // held plans stamped into a map's occupancy grid (one wave per plan; the same PostEdge / load_edge)
 #include "pp_stamp.hpp"
+// vehicles located on their held plans (one wave per plan; the same PostEdge / load_edge and the stamp's sample schedule)
+#include "pp_locate.hpp"
 
 } // namespace
 
@@ -368,6 +371,8 @@ struct pp_planner {
 	pph::Dev<pp_revalidate_result> revOut; // [maxBatch], allocated at the first pp_planner_revalidate
 	pph::Dev<StampArg> stampArgs;          // [maxBatch], allocated at the first pp_planner_stamp
 	pph::Dev<pp_stamp_result> stampOut;    // [maxBatch]
+	pph::Dev<LocateArg> locateArgs;        // [maxBatch], allocated at the first pp_planner_locate
+	pph::Dev<pp_locate_result> locateOut;  // [maxBatch]
 };
 
 namespace {
@@ -441,6 +446,15 @@ hipError_t launch_stamp(hipStream_t s, const SearchArgs& args, const Footprint& 
 	return hipGetLastError();
 }
 
+/// k_locate_tickets over `count` plans of buffer set p (count = 0 on a grid of one: the warm-up, which dereferences nothing)
+hipError_t launch_locate(hipStream_t s, const SearchArgs& args, const pp_locate_params* params, int count, const int32_t* slotsDev, const LocateArg* argsDev, pp_planner* p,
+	pp_locate_result* outDev)
+{
+	hipLaunchKernelGGL(k_locate_tickets, dim3(count > 0 ? count : 1), dim3(kLocateLanes), locate_lds_bytes(args.maxPath), s, args, params ? params->spacing : 1.0,
+		params ? params->heading_weight : 0.0, count, slotsDev, argsDev, p->paths.get(), p->rsLogs.get(), p->results.get(), outDev);
+	return hipGetLastError();
+}
+
 /// Empty dispatches of the three kernels a batch launches, on the planner's stream, then a synchronisation: the queue
 /// allocates their scratch here, where a failure is an error code, not at the first batch, where it is an abort.
 int warm_up_kernels(pp_planner* p, pp_map* map)
@@ -474,6 +488,8 @@ int warm_up_kernels(pp_planner* p, pp_map* map)
 	}
 	if (e == hipSuccess)
 		e = launch_stamp(s, p->args, Footprint {}, nullptr, 0, nullptr, nullptr, p, nullptr, nullptr);
+	if (e == hipSuccess)
+		e = launch_locate(s, p->args, nullptr, 0, nullptr, nullptr, p, nullptr);
 	if (e == hipSuccess)
 		e = hipStreamSynchronize(s);
 	if (e != hipSuccess)
@@ -596,6 +612,46 @@ int stamp_finish_target(pp_map* map)
 	if (int rc = pph::refresh_occupancy_views(map, map->ctx->stream))
 		return rc;
 	PP_HIP_TRY(hipStreamSynchronize(map->ctx->stream));
+	return PP_OK;
+}
+
+/// The arguments of a locate call that do not depend on who holds the plans (pp_planner_locate, pp_pipeline_locate): the parameters, the
+/// vehicle poses and the windows, which go into `plans` (what(i) names plan i in a refusal)
+template <typename Name>
+int locate_check(int n, const double* poses, const double* from_length, const double* to_length, const pp_locate_params* params, Name what, std::vector<LocateArg>& plans)
+{
+	if (n > 0 && !params) {
+		set_error("invalid arguments (null params: a pp_locate_params with spacing > 0 is needed)");
+		return PP_ERR_INVALID;
+	}
+	if (params && (!std::isfinite(params->spacing) || !(params->spacing > 0.0))) {
+		set_error("invalid arguments (the locate call's spacing is finite and > 0 metres)");
+		return PP_ERR_INVALID;
+	}
+	if (params && (!std::isfinite(params->heading_weight) || !(params->heading_weight >= 0.0))) {
+		set_error("invalid arguments (the locate call's heading_weight is finite and >= 0 metres per radian)");
+		return PP_ERR_INVALID;
+	}
+	if (n > 0 && !poses) {
+		set_error("invalid arguments (null poses_host: one vehicle pose (x, y, theta) per plan is needed)");
+		return PP_ERR_INVALID;
+	}
+	plans.resize((size_t)n);
+	for (int i = 0; i < n; i++) {
+		LocateArg& a = plans[(size_t)i];
+		for (int k = 0; k < 3; k++)
+			a.pose[k] = poses[(size_t)i * 3 + k];
+		a.from = from_length ? from_length[i] : -HUGE_VAL;
+		a.to = to_length ? to_length[i] : HUGE_VAL;
+		if (!std::isfinite(a.pose[0]) || !std::isfinite(a.pose[1]) || !std::isfinite(a.pose[2])) {
+			set_error(what(i) + " has a vehicle pose that is not finite");
+			return PP_ERR_INVALID;
+		}
+		if (a.from != a.from || a.to != a.to) {
+			set_error(what(i) + " has a NaN in its window");
+			return PP_ERR_INVALID;
+		}
+	}
 	return PP_OK;
 }
 
@@ -1502,6 +1558,35 @@ int pp_planner_stamp(pp_planner* planner, pp_map* target, int32_t n_queries, con
 	PP_HIP_TRY(hipStreamSynchronize(s));
 	if (int rc = stamp_finish_target(map))
 		return rc;
+	records_out(host, results_host);
+	return PP_OK;
+}
+
+int pp_planner_locate(pp_planner* planner, int32_t n_queries, const double* poses_host, const double* from_length, const double* to_length, const pp_locate_params* params,
+	pp_locate_result* results_host)
+{
+	if (!planner || n_queries < 0 || n_queries > planner->lastBatch) {
+		set_error("invalid arguments (0 <= n_queries <= last batch)");
+		return PP_ERR_INVALID;
+	}
+	if (planner->pipelineOwned) {
+		set_error("this planner is a pipeline's buffer set: pp_pipeline_locate locates vehicles on its held tickets");
+		return PP_ERR_INVALID;
+	}
+	std::vector<LocateArg> plans;
+	if (int rc = locate_check(n_queries, poses_host, from_length, to_length, params, [](int i) { return "query " + std::to_string(i); }, plans))
+		return rc;
+	if (n_queries == 0)
+		return PP_OK;
+	PP_HIP_TRY(hipSetDevice(planner->map->ctx->device));
+	hipStream_t s = planner->map->ctx->stream;
+	PP_HIP_TRY(planner->locateArgs.ensure((size_t)planner->maxBatch * sizeof(LocateArg)));
+	PP_HIP_TRY(planner->locateOut.ensure((size_t)planner->maxBatch * sizeof(pp_locate_result)));
+	PP_HIP_TRY(hipMemcpyAsync(planner->locateArgs, plans.data(), (size_t)n_queries * sizeof(LocateArg), hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(launch_locate(s, planner->args, params, n_queries, nullptr, planner->locateArgs.get(), planner, planner->locateOut.get()));
+	std::vector<pp_locate_result> host((size_t)n_queries);
+	PP_HIP_TRY(hipMemcpyAsync(host.data(), planner->locateOut, (size_t)n_queries * sizeof(pp_locate_result), hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipStreamSynchronize(s));
 	records_out(host, results_host);
 	return PP_OK;
 }

@@ -1019,6 +1019,7 @@ struct RRTStarParameters {
 /// HybridAStar::GetPath() returns for that query, GetSmoothingStatus(ticket) its Stats::smoothingStatus; Release(tickets) frees the slots.
 /// Revalidate(tickets) asks whether held plans are still collision-free after the map changed (pp_pipeline_revalidate).
 /// Stamp(tickets, into, spacing) writes the cells held plans sweep into a map's occupancy grid (pp_pipeline_stamp): the reservation map of the next vehicle.
+/// Locate(tickets, poses, spacing) finds each vehicle on its held plan (pp_pipeline_locate): the arc length that windows Stamp, the errors a controller steers on.
 class HybridAStarPipeline {
 public:
 	struct Result {
@@ -1252,6 +1253,63 @@ public:
 			out[i].colMin = r[i].cell_box[2];
 			out[i].colMax = r[i].cell_box[3];
 			out[i].length = r[i].length;
+		}
+		return out;
+	}
+	/// What Locate says about one vehicle and its held plan (pp_locate_result)
+	struct Located {
+		enum class Status { Located = 0, NoSampleInWindow = 1, NoPlan = -1, PathTooLong = -4 };
+		Status status = Status::NoPlan;
+		int edge = 0;            // 1 .. nodes - 1, root first; 0 for a one-pose plan
+		int direction = 0;       // +1 forward, -1 reverse
+		int numSamples = 0;      // stage-1 samples inside the window
+		double s = 0.0;          // arc length of the located point
+		double ratio = 0.0;      // position on the edge
+		double distance = 0.0;   // vehicle to path pose
+		double along = 0.0;      // the vehicle in the path pose's frame: ahead of it ...
+		double lateral = 0.0;    // ... and to its left
+		double headingError = 0.0;
+		double length = 0.0;     // length of the composite path
+		Pose2d pose;             // the path pose (theta wrapped by Pose2d, as PathSE2Base::Interpolate returns it)
+	};
+	/// Finds vehicle i, at poses[i], on the graph-search plan of the held query tickets[i] (pp_pipeline_locate; include/pp_hip.h has the definition): the
+	/// point of the plan with the least (ex^2 + ey^2) + (headingWeight * dtheta)^2 among the samples every `spacing` metres inside
+	/// [fromLength[i], toLength[i]] and the lattice of spacing / 32 around the best of them.  fromLength / toLength: empty, or one entry per ticket
+	/// (empty: -inf / +inf).  No map is read or written; legal beside queries in flight.
+	std::vector<Located> Locate(const std::vector<uint64_t>& tickets, const std::vector<Pose2d>& poses, double spacing, double headingWeight = 0.0,
+		const std::vector<double>& fromLength = {}, const std::vector<double>& toLength = {})
+	{
+		for (uint64_t t : tickets)
+			HeldOf(t); // (throws for a ticket that is not held)
+		const size_t n = tickets.size();
+		if (poses.size() != n || (!fromLength.empty() && fromLength.size() != n) || (!toLength.empty() && toLength.size() != n))
+			throw std::invalid_argument("Locate: one pose per ticket; fromLength and toLength are empty or hold one entry per ticket");
+		std::vector<Located> out(n);
+		if (!m_pipe)
+			return out;
+		std::vector<double> v(3 * n);
+		for (size_t i = 0; i < n; i++) {
+			v[3 * i] = poses[i].x();
+			v[3 * i + 1] = poses[i].y();
+			v[3 * i + 2] = poses[i].theta;
+		}
+		const pp_locate_params lp { spacing, headingWeight };
+		std::vector<pp_locate_result> r(n);
+		ppCheck(pp_pipeline_locate(m_pipe, (int32_t)n, tickets.data(), v.data(), fromLength.empty() ? nullptr : fromLength.data(), toLength.empty() ? nullptr : toLength.data(), &lp,
+			r.data()));
+		for (size_t i = 0; i < n; i++) {
+			out[i].status = (Located::Status)r[i].status;
+			out[i].edge = r[i].edge;
+			out[i].direction = r[i].direction;
+			out[i].numSamples = r[i].n_samples;
+			out[i].s = r[i].s;
+			out[i].ratio = r[i].ratio;
+			out[i].distance = r[i].distance;
+			out[i].along = r[i].along;
+			out[i].lateral = r[i].lateral;
+			out[i].headingError = r[i].heading_error;
+			out[i].length = r[i].length;
+			out[i].pose = Pose2d(r[i].pose[0], r[i].pose[1], r[i].pose[2]);
 		}
 		return out;
 	}

@@ -425,6 +425,17 @@ PYBIND11_MODULE(pyplanning, m)
 			},
 			py::arg("tickets"), py::arg("validator") = Ref<StateValidatorOccupancyMap>(), py::arg("spacing") = 0.1, py::arg("margin") = 0.0f,
 			py::arg("values") = std::vector<int32_t>(), py::arg("from_length") = std::vector<double>(), py::arg("to_length") = std::vector<double>())
+		// vehicles located on their held plans: (status, edge, direction, n_samples, s, ratio, distance, along, lateral, heading_error, length, pose) per ticket
+		.def("locate",
+			[](HybridAStarPipeline& h, const std::vector<uint64_t>& tickets, const std::vector<Pose2d>& poses, double spacing, double headingWeight,
+				const std::vector<double>& fromLength, const std::vector<double>& toLength) {
+				py::list out;
+				for (const auto& r : h.Locate(tickets, poses, spacing, headingWeight, fromLength, toLength))
+					out.append(py::make_tuple((int)r.status, r.edge, r.direction, r.numSamples, r.s, r.ratio, r.distance, r.along, r.lateral, r.headingError, r.length, r.pose));
+				return out;
+			},
+			py::arg("tickets"), py::arg("poses"), py::arg("spacing") = 0.1, py::arg("heading_weight") = 0.0, py::arg("from_length") = std::vector<double>(),
+			py::arg("to_length") = std::vector<double>())
 		.def("get_path", &HybridAStarPipeline::GetPath, py::arg("ticket"))
 		.def("get_graph_search_path", &HybridAStarPipeline::GetGraphSearchPath, py::arg("ticket"))
 		.def("get_smoothing_status", &HybridAStarPipeline::GetSmoothingStatus, py::arg("ticket"))

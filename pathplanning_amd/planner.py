@@ -12,8 +12,8 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import (RS_PATH_DTYPE, FootprintDisc, HybridParams, MapDesc, PostResult, QueryResult, RevalidateResult, SmootherParams, StampParams, StampResult, check,
-                   ptr)
+from ._lib import (RS_PATH_DTYPE, FootprintDisc, HybridParams, LocateParams, LocateResult, MapDesc, PostResult, QueryResult, RevalidateResult, SmootherParams,
+                   StampParams, StampResult, check, ptr)
 
 
 class Status:
@@ -699,6 +699,13 @@ class HybridAStarBatch:
         return _stamp(n, values, from_length, to_length, spacing, margin,
                       lambda v, a, b, sp, out: self.lib.pp_planner_stamp(self.h, map_set.h if map_set is not None else None, n, ptr(v), ptr(a), ptr(b), C.byref(sp), out))
 
+    def locate(self, poses, n_queries=None, from_length=None, to_length=None, spacing=0.1, heading_weight=0.0):
+        """Locates the vehicle poses `poses` [n, 3] on the plans of the first n queries of the last batch: pp_planner_locate, the batch form of
+        HybridAStarPipeline.locate.  Returns one LocateResult per query."""
+        n = len(self._results) if n_queries is None else int(n_queries)
+        return _locate(n, poses, from_length, to_length, spacing, heading_weight,
+                       lambda v, a, b, lp, out: self.lib.pp_planner_locate(self.h, n, ptr(v), ptr(a), ptr(b), C.byref(lp), out))
+
     def certify_lattice(self, q):
         """SURVEY 7.3 H2 as a contract (pp_planner_certify_lattice): created nodes and logged lattice-line children of query q recomputed on
         the host with glibc; returns (checked, cell mismatches, unverified events, largest pose difference).  mismatches == unverified == 0
@@ -1025,6 +1032,20 @@ class HybridAStarPipeline:
         return _stamp(len(t), values, from_length, to_length, spacing, margin,
                       lambda v, a, b, sp, out: self.lib.pp_pipeline_stamp(self.h, map_set.h if map_set is not None else None, len(t), ptr(t), ptr(v), ptr(a), ptr(b), C.byref(sp), out))
 
+    def locate(self, tickets, poses, from_length=None, to_length=None, spacing=0.1, heading_weight=0.0):
+        """Where is vehicle k, at pose poses[k] = (x, y, theta), on the plan of the completed, HELD query tickets[k]?  pp_pipeline_locate, whose
+        definition is in include/pp_hip.h: the point of the plan closest to the vehicle under the cost (ex^2 + ey^2) + (heading_weight * dtheta)^2,
+        searched over the samples every `spacing` metres along each edge (the stamp's schedule) inside [from_length[k], to_length[k]] metres from the
+        start (None: the whole plan), then over the lattice i * spacing / 32 around the best sample.  heading_weight > 0 (metres per radian) chooses
+        between the branches of a cusp or a self-crossing; so does a window.  No map is read and nothing but the records is written: legal while
+        other queries are in flight.  Returns one LocateResult per ticket (status, edge, direction, n_samples, s, ratio, distance, along, lateral,
+        heading_error, length, pose); r.s is what stamp's from_length takes and what revalidate's valid_length is read against.
+        Raises PPError, with nothing launched, for a ticket that is unknown, released, in flight or given twice, a pose that is not finite, a NaN
+        in a window, a spacing that is not > 0 or a heading_weight that is not >= 0."""
+        t = np.ascontiguousarray(tickets, dtype=np.uint64).reshape(-1)
+        return _locate(len(t), poses, from_length, to_length, spacing, heading_weight,
+                       lambda v, a, b, lp, out: self.lib.pp_pipeline_locate(self.h, len(t), ptr(t), ptr(v), ptr(a), ptr(b), C.byref(lp), out))
+
     def get_expanded_of(self, ticket):
         """expansion sequence (log_expansions=True) of a completed query polled with release=False"""
         slot = self.lib.pp_pipeline_slot_of(self.h, C.c_uint64(int(ticket)))
@@ -1068,6 +1089,24 @@ def _stamp(n, values, from_length, to_length, spacing, margin, call):
         return a
     out = (StampResult * max(n, 1))()
     check(call(per_plan(values, np.int32), per_plan(from_length, np.float64), per_plan(to_length, np.float64), StampParams(float(spacing), float(margin), 0), out))
+    return list(out)[:n]
+
+
+def _locate(n, poses, from_length, to_length, spacing, heading_weight, call):
+    """the per-plan arrays of a locate call as the C ABI takes them (a window of None stays NULL; a scalar is given to every plan), the call, its records"""
+    v = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    if len(v) != n:
+        raise ValueError("one vehicle pose per plan: got %d for %d plans" % (len(v), n))
+
+    def per_plan(x):
+        if x is None:
+            return None
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float64), (n,)) if np.ndim(x) == 0 else x, dtype=np.float64).reshape(-1)
+        if len(a) != n:
+            raise ValueError("one entry per plan: got %d for %d plans" % (len(a), n))
+        return a
+    out = (LocateResult * max(n, 1))()
+    check(call(v, per_plan(from_length), per_plan(to_length), LocateParams(float(spacing), float(heading_weight)), out))
     return list(out)[:n]
 
 
