@@ -1,0 +1,144 @@
+// pp_held_plans -- who holds finished plans, and the one host route by which a service reaches them.  Included by pp_planner.hip behind the kernels (it
+// names their argument types) and in front of pp_planner and pp_pipeline, which both keep one buffer group per service.
+//
+// Finished plans (path records, Reeds-Shepp log, result record) are held by a batch planner, as queries 0 .. n-1 of its last batch, or by a pipeline, as
+// the slots of held tickets.  A service over them -- post-processing, re-validation, the stamp, the locate call -- has one core (post_process_plans,
+// revalidate_plans, stamp_plans, locate_plans in pp_planner.hip) that takes a HeldPlans and goes through held_grow and held_run; its two extern "C"
+// entries check what is the holder's own and describe the holder (batch_plans, pipe_plans).
+#pragma once
+
+#include <initializer_list>
+#include <type_traits>
+#include <unordered_map>
+
+struct pp_planner;
+
+namespace {
+
+struct HeldPlans {
+	pp_planner* pl = nullptr;              // the buffer set: paths, rsLogs, results, args
+	hipStream_t stream = nullptr;          // the stream the call runs on and alone synchronises: the context's (batch planner), the control stream (pipeline)
+	const pp_footprint* footprint = nullptr; // the holder's footprint, or none
+	ppd::MapView ownView {};               // the view of the holder's own map its plans travel with when the service has no target map
+	int n = 0;                             // plans of this call
+	bool byTicket = false;                 // false: the identity over n queries (no slot list is copied, the kernel gets nullptr)
+	const uint64_t* tickets = nullptr;     // by ticket: the call's tickets ...
+	std::vector<int32_t> slots;            // ... and their resolved slots, in call order
+	size_t rows = 0;                       // plans a buffer group is made to hold: the call's n, or a batch planner's maxBatch
+	std::vector<pph::DeviceMem>* parked = nullptr; // null: outgrown buffers are freed at once; else the place they are parked while mayFree is false
+	bool mayFree = true;                   // a pipeline frees nothing with queries in flight: hipFree waits for every stream of the device, i.e. for the grid
+
+	Footprint foot() const { return footprint ? footprint->fp : Footprint {}; } // (n = 0: the point validator)
+	std::string name(int i) const { return byTicket ? "ticket " + std::to_string(tickets[i]) : "query " + std::to_string(i); } // plan i in a refusal
+};
+
+/// a service without per-plan arguments
+struct NoPlanArg {};
+
+/// The buffers of one service: the slot list (by ticket only), the per-plan arguments, the result records, by the index of a plan in the call
+template <typename Arg, typename Rec>
+struct HeldBuffers {
+	pph::Dev<int32_t> slots;
+	pph::Dev<Arg> args;
+	pph::Dev<Rec> out;
+	size_t rows = 0; // plans they hold; 0 until every one of them exists
+};
+
+/// Post-processing's buffers and what it keeps of its last call.  A batch planner indexes them by query with a stride of `points`, a pipeline by the
+/// compact index of a ticket in the last call's list.
+struct PostGroup {
+	pph::Dev<double> ratios, resampled, smoothed, edgeEnd;
+	pph::Dev<uint8_t> cusp, optimise;
+	HeldBuffers<NoPlanArg, pp_post_result> rec; // the slot list and the result records
+	size_t samples = 0;  // samples the five sample buffers hold (58 bytes each); 0 until every one of them exists
+	size_t edgeRows = 0; // plans edgeEnd holds
+	int points = 0;     // the last call's max_points: its sample limit and the buffers' per-plan stride
+	std::vector<pp_post_result> host;                  // the last call's results
+	std::unordered_map<uint64_t, int32_t> indexOfTicket; // by ticket: tickets of the last call that are still held -> compact index
+
+	PostBuffers buffers() const { return PostBuffers { ratios, resampled, smoothed, cusp, optimise, edgeEnd, rec.out }; }
+	/// `count` samples from sample index `from` of the buffers to sample index `to` of the caller's arrays (those it wants), on stream s
+	hipError_t copy_out(size_t from, size_t count, size_t to, double* sampledHost, uint8_t* cuspHost, double* smoothedHost, hipStream_t s) const
+	{
+		hipError_t e = hipSuccess;
+		if (sampledHost && count)
+			e = hipMemcpyAsync(sampledHost + to * 3, resampled + from * 3, count * 24, hipMemcpyDeviceToHost, s);
+		if (cuspHost && count && e == hipSuccess)
+			e = hipMemcpyAsync(cuspHost + to, cusp + from, count, hipMemcpyDeviceToHost, s);
+		if (smoothedHost && count && e == hipSuccess)
+			e = hipMemcpyAsync(smoothedHost + to * 3, smoothed + from * 3, count * 24, hipMemcpyDeviceToHost, s);
+		return e;
+	}
+};
+
+/// Buffers that hold `capacity` units are made to hold `wanted` ({buffer, bytes}; 0 bytes: the holder does not use it).  A holder that may not free now
+/// parks a buffer that has to grow, and the parked ones go when a call finds that it may.  The capacity is 0 until every buffer exists again: a failed
+/// allocation must not leave a stale capacity behind.
+inline hipError_t held_grow(const HeldPlans& h, size_t& capacity, size_t wanted, std::initializer_list<std::pair<pph::DeviceMem*, size_t>> buffers)
+{
+	if (h.mayFree && h.parked)
+		h.parked->clear();
+	if (capacity >= wanted)
+		return hipSuccess;
+	capacity = 0;
+	for (const auto& [buffer, bytes] : buffers) {
+		if (bytes == 0)
+			continue;
+		if (!h.mayFree && buffer->get())
+			h.parked->emplace_back(std::move(*buffer));
+		if (const hipError_t e = buffer->alloc(bytes))
+			return e;
+	}
+	capacity = wanted;
+	return hipSuccess;
+}
+
+template <typename Arg, typename Rec>
+hipError_t held_grow(const HeldPlans& h, HeldBuffers<Arg, Rec>& b)
+{
+	return held_grow(h, b.rows, h.rows,
+		{ { &b.slots, h.byTicket ? h.rows * 4 : 0 }, { &b.args, std::is_empty<Arg>::value ? 0 : h.rows * sizeof(Arg) }, { &b.out, h.rows * sizeof(Rec) } });
+}
+
+/// ... post-processing's sample and edge buffers, for max_points samples per plan; the last call's results go with buffers that are given up
+inline hipError_t held_grow(const HeldPlans& h, PostGroup& g, int maxPoints, int maxPath)
+{
+	const size_t samples = h.rows * (size_t)maxPoints;
+	if (g.samples < samples) {
+		g.host.clear();
+		g.indexOfTicket.clear();
+	}
+	if (const hipError_t e = held_grow(h, g.samples, samples,
+			{ { &g.ratios, samples * 8 }, { &g.resampled, samples * 24 }, { &g.smoothed, samples * 24 }, { &g.cusp, samples }, { &g.optimise, samples } }))
+		return e;
+	return held_grow(h, g.edgeRows, h.rows, { { &g.edgeEnd, h.rows * (size_t)(maxPath + 1) * 8 } });
+}
+
+/// One kernel over the plans of `h`, and its h.n result records back: the service's buffers made large enough, the slot list up (by ticket), the per-plan
+/// arguments up (`plans`, if the service has any), launch(slotsDev) -> hipError_t, the records down, and the holder's stream -- no other -- synchronised; then the
+/// records to the caller (and into *keep, for a service that keeps them).  Legal on a pipeline with queries in flight: the row that finished a slot wrote its path
+/// records, Reeds-Shepp log and result record BEFORE its completion record (finish() in pp_planner_rows.hpp), the host saw that record with an acquire load in
+/// pp_pipeline_poll, and nothing writes the slot again until it is released and refilled.
+template <typename Arg, typename Rec, typename Launch>
+int held_run(const HeldPlans& h, HeldBuffers<Arg, Rec>& b, const std::vector<Arg>& plans, Rec* resultsHost, Launch launch, std::vector<Rec>* keep = nullptr)
+{
+	const size_t n = (size_t)h.n;
+	hipStream_t s = h.stream;
+	PP_HIP_TRY(held_grow(h, b));
+	// (pageable sources: staged before the calls return)
+	if (h.byTicket)
+		PP_HIP_TRY(hipMemcpyAsync(b.slots, h.slots.data(), n * 4, hipMemcpyHostToDevice, s));
+	if (!plans.empty())
+		PP_HIP_TRY(hipMemcpyAsync(b.args, plans.data(), n * sizeof(Arg), hipMemcpyHostToDevice, s));
+	PP_HIP_TRY(launch(h.byTicket ? (const int32_t*)b.slots : nullptr));
+	std::vector<Rec> host(n);
+	PP_HIP_TRY(hipMemcpyAsync(host.data(), b.out, n * sizeof(Rec), hipMemcpyDeviceToHost, s));
+	PP_HIP_TRY(hipStreamSynchronize(s));
+	if (resultsHost) // (a caller may not want them)
+		std::copy(host.begin(), host.end(), resultsHost);
+	if (keep)
+		keep->swap(host);
+	return PP_OK;
+}
+
+} // namespace

@@ -25,7 +25,6 @@
 #include <chrono>
 #include <cstring>
 #include <deque>
-#include <unordered_map>
 
 namespace {
 
@@ -203,34 +202,13 @@ struct pp_pipeline {
 	unsigned long long idleTicks = 250000ull; // idle loop passes of ~4 us: about 1 s.  (50 ms until round 4: shorter than the ~100 ms the first fields of a run take, so the
 	                                         // grid's waves left before their first work arrived and came back by the luck of the top-up launches.)  Idle waves leave at once when
 	                                         // the host has polled every result (PipeCtl::quiesce), so the time-out only matters when a producer really cannot run.
-	// pp_pipeline_postprocess (k_postprocess_tickets): outputs at the compact index of a ticket in the last call's list.  The sample buffers hold
-	// postSamples = the largest n x max_points asked so far (58 bytes per sample), never capacity x max_points.
-	pph::Dev<double> postRatios, postResampled, postSmoothed, postEdgeEnd;
-	pph::Dev<uint8_t> postCusp, postOptimise;
-	pph::Dev<pp_post_result> postOut;
-	pph::Dev<int32_t> postSlots;
-	size_t postSamples = 0; // samples the five sample buffers hold; 0 until every one of them exists
-	size_t postRows = 0;    // plans postEdgeEnd / postOut / postSlots hold
-	std::vector<pph::DeviceMem> heldParked; // buffers of the held-plan services (post-processing, re-validation) outgrown while queries were in flight: hipFree
-	                                        // waits for the whole device (the persistent grid included), so they are kept until a call finds nothing in flight
-	                                        // (or the pipeline goes): pipe_grow
-	int postPoints = 0;     // the last call's max_points: its sample limit and the buffers' per-plan stride
-	std::vector<pp_post_result> postHost;                  // the last call's results, by compact index
-	std::unordered_map<uint64_t, int32_t> postIndexOfTicket; // tickets of the last call that are still held -> compact index
-	// pp_pipeline_revalidate (k_revalidate_tickets): the slot list and the results of a call, by compact index; revRows = tickets they hold
-	pph::Dev<int32_t> revSlots;
-	pph::Dev<pp_revalidate_result> revOut;
-	size_t revRows = 0;
-	// pp_pipeline_stamp (k_stamp_tickets): the slot list, the values and windows, and the results of a call, by compact index
-	pph::Dev<int32_t> stampSlots;
-	pph::Dev<StampArg> stampArgs;
-	pph::Dev<pp_stamp_result> stampOut;
-	size_t stampRows = 0;
-	// pp_pipeline_locate (k_locate_tickets): the slot list, the vehicle poses and windows, and the results of a call, by compact index
-	pph::Dev<int32_t> locateSlots;
-	pph::Dev<LocateArg> locateArgs;
-	pph::Dev<pp_locate_result> locateOut;
-	size_t locateRows = 0;
+	// the services over held plans (pp_held_plans.hpp): outputs at the compact index of a ticket in the call's list, buffers sized by the largest call so far
+	PostGroup post;
+	HeldBuffers<NoPlanArg, pp_revalidate_result> reval;
+	HeldBuffers<StampArg, pp_stamp_result> stamp;
+	HeldBuffers<LocateArg, pp_locate_result> locate;
+	std::vector<pph::DeviceMem> heldParked; // their buffers outgrown while queries were in flight: hipFree waits for the whole device (the persistent grid
+	                                        // included), so they are kept until a call finds nothing in flight (or the pipeline goes): held_grow
 	int nWf = 2;      // wavefront streams in use: consecutive submissions' launches overlap (the tail of one under the head of the next)
 	int wfBlocks = 0; // workgroups per wavefront launch (<= the resident number): the wavefront kernel's share of the chip
 };
@@ -398,8 +376,9 @@ int pipe_check(const pp_pipeline* P)
 	return pipe_dead(P) ? PP_ERR_HIP : PP_OK;
 }
 
-// ---- held plans by ticket.  A service that works on held plans (post-processing, re-validation, the next one) resolves its tickets with pipe_resolve, sizes its
-// buffers with pipe_grow and launches through pipe_run_held; whatever it keeps per ticket is dropped in pipe_release, the one route by which a slot is freed.
+// ---- held plans by ticket.  An entry of a service over held plans describes the pipeline as the holder with pipe_plans, resolves its tickets with pipe_resolve
+// and calls the service's core (pp_held_plans.hpp, pp_planner.hip); whatever a service keeps per ticket is dropped in pipe_release, the one route by which a
+// slot is freed.
 
 /// the slots of n held tickets (pph::TicketTable::resolve), or its refusal as the library's error
 int pipe_resolve(const pp_pipeline* P, int n, const uint64_t* tickets, const char* verb, bool distinct, std::vector<int32_t>& slots)
@@ -424,52 +403,32 @@ int pipe_refuse(const pp_pipeline* P, uint64_t ticket, const char* verb)
 /// that frees a slot says so all the same).  false: the ticket is not held
 bool pipe_release(pp_pipeline* P, uint64_t ticket)
 {
-	P->postIndexOfTicket.erase(ticket);
+	P->post.indexOfTicket.erase(ticket);
 	return P->tickets.release(ticket);
 }
 
-/// Buffers of a held-plan service that hold `capacity` units are made to hold `wanted`.  Nothing is freed while queries are in flight: hipFree waits for every
-/// stream of the device, i.e. for the searches in flight and the grid's idle waves.  A buffer that has to grow then is parked instead, and the parked ones go
-/// when a call finds the pipeline idle.  The capacity is 0 until every buffer exists again: a failed allocation must not leave a stale capacity behind.
-hipError_t pipe_grow(pp_pipeline* P, size_t& capacity, size_t wanted, std::initializer_list<std::pair<pph::DeviceMem*, size_t>> buffers)
+/// The pipeline as the holder of the plans of n tickets (h.slots: pipe_resolve), behind what the by-ticket services refuse first: a null or dead pipeline, a
+/// count outside 0 .. capacity, a missing ticket list.  A call runs on the control stream and synchronises that stream alone; the plans travel with the pipeline's
+/// footprint and, where the service has no target map, with the view of the last submission (held slots exist only after a submission, which cached the view).
+/// Nothing is freed while queries are in flight.
+int pipe_plans(pp_pipeline* P, int n, const uint64_t* tickets, HeldPlans& h)
 {
-	const bool idle = P->nSubmitted == P->doneHead;
-	if (idle)
-		P->heldParked.clear();
-	if (capacity >= wanted)
-		return hipSuccess;
-	capacity = 0;
-	for (const auto& [buffer, bytes] : buffers) {
-		if (!idle && buffer->get())
-			P->heldParked.emplace_back(std::move(*buffer));
-		if (const hipError_t e = buffer->alloc(bytes))
-			return e;
+	if (int rc = pipe_check(P))
+		return rc;
+	if (n < 0 || n > P->capacity || (n > 0 && !tickets)) {
+		set_error("invalid arguments (0 <= n <= capacity = " + std::to_string(P->capacity) + ", got n = " + std::to_string(n) + ")");
+		return PP_ERR_INVALID;
 	}
-	capacity = wanted;
-	return hipSuccess;
-}
-
-/// One kernel over the held plans in `slots`, and its n result records back.  Legal with queries in flight: the row that finished a slot wrote its path records,
-/// Reeds-Shepp log and result record BEFORE its completion record (finish() in pp_planner_rows.hpp), the host saw that record with an acquire load in
-/// pp_pipeline_poll, and nothing writes the slot again until it is released and refilled.  The launch goes on the control stream with a COPY of the search arguments
-/// under the caller's map view -- the buffer set's `args`, which the grid's top-up launches read, is not written -- and with the pipeline's footprint (or none:
-/// Footprint::n = 0); only the control stream is synchronised.  launch(args, footprint, n, slotsDev) dispatches the kernel on P->ctlStream.
-template <typename Rec, typename Launch>
-int pipe_run_held(pp_pipeline* P, const std::vector<int32_t>& slots, const ppd::MapView& view, int32_t* slotsDev, const Rec* outDev, std::vector<Rec>& host, Launch launch)
-{
-	const int n = (int)slots.size();
-	SearchArgs args = P->pl->args;
-	args.m = view;
-	Footprint foot {};
-	if (P->footprint)
-		foot = P->footprint->fp;
-	hipStream_t s = P->ctlStream;
-	PP_HIP_TRY(hipMemcpyAsync(slotsDev, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, s)); // (pageable source: staged before the call returns)
-	launch(args, foot, n, (const int32_t*)slotsDev);
-	PP_HIP_TRY(hipGetLastError());
-	host.resize((size_t)n);
-	PP_HIP_TRY(hipMemcpyAsync(host.data(), outDev, (size_t)n * sizeof(Rec), hipMemcpyDeviceToHost, s));
-	PP_HIP_TRY(hipStreamSynchronize(s));
+	h.pl = P->pl;
+	h.stream = P->ctlStream;
+	h.footprint = P->footprint;
+	h.ownView = P->viewValid ? P->lastView : P->pl->map->view();
+	h.n = n;
+	h.byTicket = true;
+	h.tickets = tickets;
+	h.rows = (size_t)n;
+	h.parked = &P->heldParked;
+	h.mayFree = P->nSubmitted == P->doneHead;
 	return PP_OK;
 }
 
@@ -645,34 +604,13 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 			return PP_ERR_INVALID;
 		}
 	}
-	// an empty dispatch of the kernels pp_pipeline_postprocess, pp_pipeline_revalidate, pp_pipeline_stamp and pp_pipeline_locate launch, on the stream they use: the queue allocates their scratch here,
-	// where a failure is an error code (see warm_up_kernels)
-	auto warmUp = [&](const char* what, auto&& launchEmpty) -> int {
-		launchEmpty();
-		e = hipGetLastError();
-		if (e == hipSuccess)
-			e = hipStreamSynchronize(P->ctlStream);
-		if (e == hipSuccess)
-			return PP_OK;
+	// an empty dispatch of the kernels pp_pipeline_postprocess, pp_pipeline_revalidate, pp_pipeline_stamp and pp_pipeline_locate launch, on the stream they use
+	const char* service = "";
+	e = warm_up_held_kernels(pl, P->ctlStream, true, &service);
+	if (e != hipSuccess) {
 		free_pipeline(P);
-		return pph::hip_fail(e, what);
-	};
-	if (int rc = warmUp("pipeline post-processing kernel warm-up (scratch allocation)", [&] {
-			hipLaunchKernelGGL(k_postprocess_tickets, dim3(1), dim3(kPostThreads), 64, P->ctlStream, pl->args, PostParams {}, Footprint {}, 0, (const int32_t*)nullptr,
-				(const PathRec*)nullptr, (const RsLogEntry*)nullptr, (const DevResult*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, PostBuffers {});
-		}))
-		return rc;
-	if (int rc = warmUp("pipeline re-validation kernel warm-up (scratch allocation)", [&] {
-			hipLaunchKernelGGL(k_revalidate_tickets, dim3(1), dim3(64), 0, P->ctlStream, pl->args, Footprint {}, 0, (const int32_t*)nullptr, (const PathRec*)nullptr,
-				(const RsLogEntry*)nullptr, (const DevResult*)nullptr, (pp_revalidate_result*)nullptr);
-		}))
-		return rc;
-	if (int rc = warmUp("pipeline stamp kernel warm-up (scratch allocation)", [&] {
-			(void)launch_stamp(P->ctlStream, pl->args, Footprint {}, nullptr, 0, nullptr, nullptr, pl, nullptr, nullptr);
-		}))
-		return rc;
-	if (int rc = warmUp("pipeline locate kernel warm-up (scratch allocation)", [&] { (void)launch_locate(P->ctlStream, pl->args, nullptr, 0, nullptr, nullptr, pl, nullptr); }))
-		return rc;
+		return pph::hip_fail(e, ("pipeline " + std::string(service) + " kernel warm-up (scratch allocation)").c_str());
+	}
 	std::memset(P->done, 0, ring * sizeof(PipeDone));
 	std::memset(P->errFlags, 0, 64);
 	P->tickets.reset(capacity);
@@ -1114,16 +1052,13 @@ int pp_pipeline_get_paths(pp_pipeline* P, int32_t n, const uint64_t* tickets, in
 }
 
 /// HybridAStar::SearchPath's post-processing of n completed, held queries, in the order of `tickets` (include/pp_hip.h), under the map view of the last
-/// submission (pipe_run_held)
+/// submission (post_process_plans)
 int pp_pipeline_postprocess(pp_pipeline* P, int32_t n, const uint64_t* tickets, float path_interpolation, const pp_smoother_params* smoother, int32_t max_points,
 	pp_post_result* results_host)
 {
-	if (int rc = pipe_check(P))
+	HeldPlans h;
+	if (int rc = pipe_plans(P, n, tickets, h))
 		return rc;
-	if (n < 0 || n > P->capacity || (n > 0 && !tickets)) {
-		set_error("invalid arguments (0 <= n <= capacity = " + std::to_string(P->capacity) + ", got n = " + std::to_string(n) + ")");
-		return PP_ERR_INVALID;
-	}
 	if (max_points < 8 || max_points > 8 * kPostThreads) {
 		set_error("invalid arguments (8 <= max_points <= 2048, got " + std::to_string(max_points) + ")");
 		return PP_ERR_INVALID;
@@ -1132,39 +1067,17 @@ int pp_pipeline_postprocess(pp_pipeline* P, int32_t n, const uint64_t* tickets, 
 		set_error("invalid arguments (path_interpolation > 0)");
 		return PP_ERR_INVALID;
 	}
-	pp_planner* pl = P->pl;
-	pp_map* map = pl->map;
-	if (int rc = post_check_grids(map))
+	if (int rc = post_check_grids(P->pl->map))
 		return rc;
-	std::vector<int32_t> slots;
-	if (int rc = pipe_resolve(P, n, tickets, "post-processed", true, slots))
+	if (int rc = pipe_resolve(P, n, tickets, "post-processed", true, h.slots))
 		return rc;
 	// the last call's results end here (also for n == 0), whatever happens below
-	P->postIndexOfTicket.clear();
-	P->postHost.clear();
-	if (n == 0)
-		return PP_OK;
-	PP_HIP_TRY(hipSetDevice(map->ctx->device));
-	const size_t samples = (size_t)n * (size_t)max_points;
-	PP_HIP_TRY(pipe_grow(P, P->postSamples, samples,
-		{ { &P->postRatios, samples * 8 }, { &P->postResampled, samples * 24 }, { &P->postSmoothed, samples * 24 }, { &P->postCusp, samples }, { &P->postOptimise, samples } }));
-	PP_HIP_TRY(pipe_grow(P, P->postRows, (size_t)n,
-		{ { &P->postEdgeEnd, (size_t)n * (size_t)(pl->maxPath + 1) * 8 }, { &P->postOut, (size_t)n * sizeof(pp_post_result) }, { &P->postSlots, (size_t)n * 4 } }));
-	const PostBuffers post { P->postRatios, P->postResampled, P->postSmoothed, P->postCusp, P->postOptimise, P->postEdgeEnd, P->postOut };
-	const PostParams pp = post_params(path_interpolation, smoother, pl->params.min_turning_radius, max_points);
-	std::vector<pp_post_result> host;
-	// (held slots exist only after a submission, which cached the view)
-	if (int rc = pipe_run_held(P, slots, P->viewValid ? P->lastView : map->view(), P->postSlots.get(), P->postOut.get(), host,
-			[&](const SearchArgs& args, const Footprint& foot, int count, const int32_t* slotsDev) {
-				hipLaunchKernelGGL(k_postprocess_tickets, dim3(count), dim3(kPostThreads), (size_t)max_points * 16, P->ctlStream, args, pp, foot, count, slotsDev, pl->paths.get(),
-					pl->rsLogs.get(), pl->results.get(), map->obstLabel[map->obstResult].get(), map->voroLabel[map->voroResult].get(), post);
-			}))
+	P->post.indexOfTicket.clear();
+	P->post.host.clear();
+	if (int rc = post_process_plans(h, P->post, path_interpolation, smoother, max_points, results_host))
 		return rc;
-	P->postHost.swap(host);
-	P->postPoints = max_points;
 	for (int i = 0; i < n; i++)
-		P->postIndexOfTicket[tickets[i]] = i;
-	records_out(P->postHost, results_host);
+		P->post.indexOfTicket[tickets[i]] = i;
 	return PP_OK;
 }
 
@@ -1180,8 +1093,8 @@ int pp_pipeline_get_processed_paths(pp_pipeline* P, int32_t n, const uint64_t* t
 		return PP_ERR_HIP;
 	std::vector<int32_t> index((size_t)n);
 	for (int i = 0; i < n; i++) {
-		auto it = P->postIndexOfTicket.find(tickets[i]);
-		if (it == P->postIndexOfTicket.end() || P->tickets.slot_of(tickets[i]) < 0) {
+		auto it = P->post.indexOfTicket.find(tickets[i]);
+		if (it == P->post.indexOfTicket.end() || P->tickets.slot_of(tickets[i]) < 0) {
 			set_error("ticket " + std::to_string(tickets[i]) + " has no post-processed path: not in the last pp_pipeline_postprocess call, or released since");
 			return PP_ERR_INVALID;
 		}
@@ -1191,32 +1104,18 @@ int pp_pipeline_get_processed_paths(pp_pipeline* P, int32_t n, const uint64_t* t
 		return PP_OK;
 	PP_HIP_TRY(hipSetDevice(P->pl->map->ctx->device));
 	hipStream_t s = P->ctlStream;
-	const size_t cap = (size_t)P->postPoints, stride = (size_t)max_points;
+	const size_t cap = (size_t)P->post.points, stride = (size_t)max_points;
 	bool consecutive = stride == cap;
 	for (int i = 1; i < n && consecutive; i++)
 		consecutive = index[(size_t)i] == index[0] + i;
 	for (int i = 0; i < n; i++)
-		n_points_host[i] = P->postHost[(size_t)index[(size_t)i]].n_points;
+		n_points_host[i] = P->post.host[(size_t)index[(size_t)i]].n_points;
 	if (consecutive) { // the caller's layout is the buffers': one copy per array (rows beyond n_points are unspecified either way)
-		const size_t first = (size_t)index[0] * cap, count = (size_t)n * cap;
-		if (sampled_host)
-			PP_HIP_TRY(hipMemcpyAsync(sampled_host, P->postResampled + first * 3, count * 24, hipMemcpyDeviceToHost, s));
-		if (cusp_host)
-			PP_HIP_TRY(hipMemcpyAsync(cusp_host, P->postCusp + first, count, hipMemcpyDeviceToHost, s));
-		if (smoothed_host)
-			PP_HIP_TRY(hipMemcpyAsync(smoothed_host, P->postSmoothed + first * 3, count * 24, hipMemcpyDeviceToHost, s));
+		PP_HIP_TRY(P->post.copy_out((size_t)index[0] * cap, (size_t)n * cap, 0, sampled_host, cusp_host, smoothed_host, s));
 	} else {
 		for (int i = 0; i < n; i++) {
-			const size_t from = (size_t)index[(size_t)i] * cap, to = (size_t)i * stride;
 			const size_t np = (size_t)n_points_host[i] < stride ? (size_t)n_points_host[i] : stride;
-			if (np == 0)
-				continue;
-			if (sampled_host)
-				PP_HIP_TRY(hipMemcpyAsync(sampled_host + to * 3, P->postResampled + from * 3, np * 24, hipMemcpyDeviceToHost, s));
-			if (cusp_host)
-				PP_HIP_TRY(hipMemcpyAsync(cusp_host + to, P->postCusp + from, np, hipMemcpyDeviceToHost, s));
-			if (smoothed_host)
-				PP_HIP_TRY(hipMemcpyAsync(smoothed_host + to * 3, P->postSmoothed + from * 3, np * 24, hipMemcpyDeviceToHost, s));
+			PP_HIP_TRY(P->post.copy_out((size_t)index[(size_t)i] * cap, np, (size_t)i * stride, sampled_host, cusp_host, smoothed_host, s));
 		}
 	}
 	PP_HIP_TRY(hipStreamSynchronize(s));
@@ -1225,120 +1124,56 @@ int pp_pipeline_get_processed_paths(pp_pipeline* P, int32_t n, const uint64_t* t
 	return PP_OK;
 }
 
-/// Are the plans of n completed, held queries still collision-free on `target` as it is now (include/pp_hip.h)?  The map view is the target's of this moment
-/// (every writer of a map's grids has drained the map's stream before it returned, so the view is current).  Nothing of the last post-processing call is touched.
+/// Are the plans of n completed, held queries still collision-free on `target` as it is now (include/pp_hip.h; revalidate_plans)?  Nothing of the last
+/// post-processing call is touched.
 int pp_pipeline_revalidate(pp_pipeline* P, pp_map* target, int32_t n, const uint64_t* tickets, pp_revalidate_result* results_host)
 {
-	if (int rc = pipe_check(P))
+	HeldPlans h;
+	if (int rc = pipe_plans(P, n, tickets, h))
 		return rc;
-	if (n < 0 || n > P->capacity || (n > 0 && !tickets)) {
-		set_error("invalid arguments (0 <= n <= capacity = " + std::to_string(P->capacity) + ", got n = " + std::to_string(n) + ")");
-		return PP_ERR_INVALID;
-	}
-	pp_planner* pl = P->pl;
-	pp_map* const map = target ? target : pl->map;
-	if (int rc = revalidate_check_target(pl->map, map))
+	pp_map* const map = target ? target : P->pl->map;
+	if (int rc = revalidate_check_target(P->pl->map, map))
 		return rc;
-	std::vector<int32_t> slots;
-	if (int rc = pipe_resolve(P, n, tickets, "re-validated", true, slots))
+	if (int rc = pipe_resolve(P, n, tickets, "re-validated", true, h.slots))
 		return rc;
-	if (n == 0)
-		return PP_OK;
-	PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
-	PP_HIP_TRY(pipe_grow(P, P->revRows, (size_t)n, { { &P->revSlots, (size_t)n * 4 }, { &P->revOut, (size_t)n * sizeof(pp_revalidate_result) } }));
-	std::vector<pp_revalidate_result> host;
-	if (int rc = pipe_run_held(P, slots, map->view(), P->revSlots.get(), P->revOut.get(), host, [&](const SearchArgs& args, const Footprint& foot, int count, const int32_t* slotsDev) {
-			hipLaunchKernelGGL(k_revalidate_tickets, dim3(count), dim3(64), 0, P->ctlStream, args, foot, count, slotsDev, pl->paths.get(), pl->rsLogs.get(), pl->results.get(),
-				P->revOut.get());
-		}))
-		return rc;
-	records_out(host, results_host);
-	return PP_OK;
+	return revalidate_plans(h, P->reval, map, results_host);
 }
 
-/// The plans of n completed, held queries stamped into `target`'s occupancy grid (include/pp_hip.h).  The kernel runs on the control stream under the
-/// target's view of this moment; the views of the target are refreshed on the target's own stream once the control stream has been drained, i.e. behind the stamp.
+/// The plans of n completed, held queries stamped into `target`'s occupancy grid (include/pp_hip.h; stamp_plans)
 int pp_pipeline_stamp(pp_pipeline* P, pp_map* target, int32_t n, const uint64_t* tickets, const int32_t* values, const double* from_length, const double* to_length,
 	const pp_stamp_params* params, pp_stamp_result* results_host)
 {
-	if (int rc = pipe_check(P))
+	HeldPlans h;
+	if (int rc = pipe_plans(P, n, tickets, h))
 		return rc;
-	if (n < 0 || n > P->capacity || (n > 0 && !tickets)) {
-		set_error("invalid arguments (0 <= n <= capacity = " + std::to_string(P->capacity) + ", got n = " + std::to_string(n) + ")");
-		return PP_ERR_INVALID;
-	}
-	pp_planner* pl = P->pl;
-	pp_map* const map = target ? target : pl->map;
+	pp_map* const map = target ? target : P->pl->map;
 	std::vector<StampArg> plans;
-	if (int rc = stamp_check(pl->map, map, n, values, from_length, to_length, params, [&](int i) { return "ticket " + std::to_string(tickets[i]); }, plans))
+	if (int rc = stamp_check(h, map, values, from_length, to_length, params, plans))
 		return rc;
-	std::vector<int32_t> slots;
-	if (int rc = pipe_resolve(P, n, tickets, "stamped", true, slots))
+	if (int rc = pipe_resolve(P, n, tickets, "stamped", true, h.slots))
 		return rc;
-	if (map == pl->map && P->nSubmitted != P->doneHead) {
+	if (map == P->pl->map && P->nSubmitted != P->doneHead) {
 		// the field launches of the queries in flight read the occupancy views this call rewrites (held slots do not count: their fields are built)
 		set_error("the target is the pipeline's own map and the pipeline has " + std::to_string(P->nSubmitted - P->doneHead) +
 			" queries in flight: poll them all first, or stamp another map of the context");
 		return PP_ERR_INVALID;
 	}
-	if (n == 0)
-		return PP_OK;
-	PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
-	if (int rc = stamp_prepare_target(map))
-		return rc;
-	PP_HIP_TRY(pipe_grow(P, P->stampRows, (size_t)n,
-		{ { &P->stampSlots, (size_t)n * 4 }, { &P->stampArgs, (size_t)n * sizeof(StampArg) }, { &P->stampOut, (size_t)n * sizeof(pp_stamp_result) } }));
-	const Footprint discs = stamp_discs(P->footprint, pl->map);
-	std::vector<pp_stamp_result> host;
-	hipError_t staged = hipSuccess;
-	if (int rc = pipe_run_held(P, slots, map->view(), P->stampSlots.get(), P->stampOut.get(), host, [&](const SearchArgs& args, const Footprint&, int count, const int32_t* slotsDev) {
-			staged = hipMemcpyAsync(P->stampArgs.get(), plans.data(), (size_t)count * sizeof(StampArg), hipMemcpyHostToDevice, P->ctlStream); // (pageable: staged at once)
-			if (staged == hipSuccess)
-				(void)launch_stamp(P->ctlStream, args, discs, params, count, slotsDev, P->stampArgs.get(), pl, map->occ32.get(), P->stampOut.get());
-		}))
-		return rc;
-	PP_HIP_TRY(staged);
-	if (int rc = stamp_finish_target(map))
-		return rc;
-	records_out(host, results_host);
-	return PP_OK;
+	return stamp_plans(h, P->stamp, map, plans, params, results_host);
 }
 
-/// The vehicles of n completed, held queries located on their plans (include/pp_hip.h).  The kernel reads the held slots' plan records and writes its own
-/// result records: no map is read or written, so the view the launch travels with is the pipeline's own and the call is legal beside queries in flight.
+/// The vehicles of n completed, held queries located on their plans (include/pp_hip.h; locate_plans): legal beside queries in flight
 int pp_pipeline_locate(pp_pipeline* P, int32_t n, const uint64_t* tickets, const double* poses_host, const double* from_length, const double* to_length,
 	const pp_locate_params* params, pp_locate_result* results_host)
 {
-	if (int rc = pipe_check(P))
+	HeldPlans h;
+	if (int rc = pipe_plans(P, n, tickets, h))
 		return rc;
-	if (n < 0 || n > P->capacity || (n > 0 && !tickets)) {
-		set_error("invalid arguments (0 <= n <= capacity = " + std::to_string(P->capacity) + ", got n = " + std::to_string(n) + ")");
-		return PP_ERR_INVALID;
-	}
-	pp_planner* pl = P->pl;
 	std::vector<LocateArg> plans;
-	if (int rc = locate_check(n, poses_host, from_length, to_length, params, [&](int i) { return "ticket " + std::to_string(tickets[i]); }, plans))
+	if (int rc = locate_check(h, poses_host, from_length, to_length, params, plans))
 		return rc;
-	std::vector<int32_t> slots;
-	if (int rc = pipe_resolve(P, n, tickets, "located", true, slots))
+	if (int rc = pipe_resolve(P, n, tickets, "located", true, h.slots))
 		return rc;
-	if (n == 0)
-		return PP_OK;
-	PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
-	PP_HIP_TRY(pipe_grow(P, P->locateRows, (size_t)n,
-		{ { &P->locateSlots, (size_t)n * 4 }, { &P->locateArgs, (size_t)n * sizeof(LocateArg) }, { &P->locateOut, (size_t)n * sizeof(pp_locate_result) } }));
-	std::vector<pp_locate_result> host;
-	hipError_t staged = hipSuccess;
-	if (int rc = pipe_run_held(P, slots, P->viewValid ? P->lastView : pl->map->view(), P->locateSlots.get(), P->locateOut.get(), host,
-			[&](const SearchArgs& args, const Footprint&, int count, const int32_t* slotsDev) {
-				staged = hipMemcpyAsync(P->locateArgs.get(), plans.data(), (size_t)count * sizeof(LocateArg), hipMemcpyHostToDevice, P->ctlStream); // (pageable: staged at once)
-				if (staged == hipSuccess)
-					(void)launch_locate(P->ctlStream, args, params, count, slotsDev, P->locateArgs.get(), pl, P->locateOut.get());
-			}))
-		return rc;
-	PP_HIP_TRY(staged);
-	records_out(host, results_host);
-	return PP_OK;
+	return locate_plans(h, P->locate, plans, params, results_host);
 }
 
 /// Launch durations seen so far (HIP events on the launching streams; harvested by pp_pipeline_poll) and reset.  Wavefront: one launch per

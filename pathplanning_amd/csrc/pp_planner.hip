@@ -308,6 +308,9 @@ struct PipeView {
 
 } // namespace
 
+// who holds finished plans, and the buffer groups and the one launch route of the services that work on them
+#include "pp_held_plans.hpp"
+
 // ---------------------------------------------------------------------------
 struct pp_planner {
 	pp_map* map = nullptr;
@@ -361,18 +364,11 @@ struct pp_planner {
 	pph::ClearanceViews clearance; // pp_planner_set_heuristic_clearance / pp_pipeline_set_heuristic_clearance: the occupancy the field launches read (radius 0: the map's own)
 	bool pipelineOwned = false; // the buffer set of a pp_pipeline (pp_pipeline_planner()): its rows and field slots belong to the pipeline's kernels
 	std::vector<DevResult> hostResults;
-	// post-processing (pp_postprocess.hpp), allocated at the first pp_planner_postprocess (the kernel takes them as a PostBuffers)
-	pph::Dev<double> postRatios, postResampled, postSmoothed, postEdgeEnd;
-	pph::Dev<uint8_t> postCusp, postOptimise;
-	pph::Dev<pp_post_result> postOut;
-	int postMaxPoints = 0, postDone = 0; // capacity of the buffers per query; queries of the last call
-	int postPoints = 0; // the last call's max_points: its sample limit and the buffers' per-query stride
-	std::vector<pp_post_result> hostPost;
-	pph::Dev<pp_revalidate_result> revOut; // [maxBatch], allocated at the first pp_planner_revalidate
-	pph::Dev<StampArg> stampArgs;          // [maxBatch], allocated at the first pp_planner_stamp
-	pph::Dev<pp_stamp_result> stampOut;    // [maxBatch]
-	pph::Dev<LocateArg> locateArgs;        // [maxBatch], allocated at the first pp_planner_locate
-	pph::Dev<pp_locate_result> locateOut;  // [maxBatch]
+	// the services over the plans of the last batch (pp_held_plans.hpp): buffers for maxBatch plans, allocated at a service's first call and indexed by query
+	PostGroup post;
+	HeldBuffers<NoPlanArg, pp_revalidate_result> reval;
+	HeldBuffers<StampArg, pp_stamp_result> stamp;
+	HeldBuffers<LocateArg, pp_locate_result> locate;
 };
 
 namespace {
@@ -455,7 +451,32 @@ hipError_t launch_locate(hipStream_t s, const SearchArgs& args, const pp_locate_
 	return hipGetLastError();
 }
 
-/// Empty dispatches of the three kernels a batch launches, on the planner's stream, then a synchronisation: the queue
+/// An empty dispatch of each kernel that works on held plans (post-processing in the holder's form), on stream s, which is drained behind each: the queue
+/// allocates their scratch here, where a failure is an error code (see warm_up_kernels).  *service names the service whose kernel failed.
+hipError_t warm_up_held_kernels(pp_planner* p, hipStream_t s, bool byTicket, const char** service)
+{
+	hipError_t e = hipSuccess;
+	auto ok = [&](const char* name, hipError_t launched) {
+		*service = name;
+		e = launched != hipSuccess ? launched : hipStreamSynchronize(s);
+		return e == hipSuccess;
+	};
+	if (byTicket)
+		hipLaunchKernelGGL(k_postprocess_tickets, dim3(1), dim3(kPostThreads), 64, s, p->args, PostParams {}, Footprint {}, 0, (const int32_t*)nullptr, (const PathRec*)nullptr,
+			(const RsLogEntry*)nullptr, (const DevResult*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, PostBuffers {});
+	else
+		hipLaunchKernelGGL(k_postprocess, dim3(1), dim3(kPostThreads), 64, s, p->args, PostParams {}, 0, (const PathRec*)nullptr, (const RsLogEntry*)nullptr, (const DevResult*)nullptr,
+			(const uint32_t*)nullptr, (const uint32_t*)nullptr, PostBuffers {});
+	if (!ok("post-processing", hipGetLastError()))
+		return e;
+	hipLaunchKernelGGL(k_revalidate_tickets, dim3(1), dim3(64), 0, s, p->args, Footprint {}, 0, (const int32_t*)nullptr, (const PathRec*)nullptr, (const RsLogEntry*)nullptr,
+		(const DevResult*)nullptr, (pp_revalidate_result*)nullptr);
+	if (ok("re-validation", hipGetLastError()) && ok("stamp", launch_stamp(s, p->args, Footprint {}, nullptr, 0, nullptr, nullptr, p, nullptr, nullptr)))
+		(void)ok("locate", launch_locate(s, p->args, nullptr, 0, nullptr, nullptr, p, nullptr));
+	return e;
+}
+
+/// Empty dispatches of the kernels a batch launches, on the planner's stream, then a synchronisation: the queue
 /// allocates their scratch here, where a failure is an error code, not at the first batch, where it is an abort.
 int warm_up_kernels(pp_planner* p, pp_map* map)
 {
@@ -476,20 +497,9 @@ int warm_up_kernels(pp_planner* p, pp_map* map)
 	}
 	if (e == hipSuccess)
 		e = launch_search<false>(p, s, 1, noQueries);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_postprocess, dim3(1), dim3(kPostThreads), 64, s, p->args, PostParams {}, 0, (const PathRec*)nullptr, (const RsLogEntry*)nullptr, (const DevResult*)nullptr,
-			(const uint32_t*)nullptr, (const uint32_t*)nullptr, PostBuffers {});
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_revalidate_tickets, dim3(1), dim3(64), 0, s, p->args, Footprint {}, 0, (const int32_t*)nullptr, (const PathRec*)nullptr, (const RsLogEntry*)nullptr,
-			(const DevResult*)nullptr, (pp_revalidate_result*)nullptr);
-		e = hipGetLastError();
-	}
+	const char* service = nullptr;
 	if (e == hipSuccess)
-		e = launch_stamp(s, p->args, Footprint {}, nullptr, 0, nullptr, nullptr, p, nullptr, nullptr);
-	if (e == hipSuccess)
-		e = launch_locate(s, p->args, nullptr, 0, nullptr, nullptr, p, nullptr);
+		e = warm_up_held_kernels(p, s, false, &service);
 	if (e == hipSuccess)
 		e = hipStreamSynchronize(s);
 	if (e != hipSuccess)
@@ -539,11 +549,12 @@ int revalidate_check_target(const pp_map* own, const pp_map* target)
 }
 
 /// The arguments of a stamp that do not depend on who holds the plans (pp_planner_stamp, pp_pipeline_stamp): the target's context, the
-/// parameters, and the per-plan values and windows, which go into `plans` (what(i) names plan i in a refusal)
-template <typename Name>
-int stamp_check(const pp_map* own, const pp_map* target, int n, const int32_t* values, const double* from_length, const double* to_length, const pp_stamp_params* params,
-	Name what, std::vector<StampArg>& plans)
+/// parameters, and the per-plan values and windows, which go into `plans` (h.name(i) names plan i in a refusal)
+int stamp_check(const HeldPlans& h, const pp_map* target, const int32_t* values, const double* from_length, const double* to_length, const pp_stamp_params* params,
+	std::vector<StampArg>& plans)
 {
+	const pp_map* const own = h.pl->map;
+	const int n = h.n;
 	if (target->ctx != own->ctx) {
 		set_error("the target map belongs to another context than the planner's map");
 		return PP_ERR_INVALID;
@@ -568,11 +579,11 @@ int stamp_check(const pp_map* own, const pp_map* target, int n, const int32_t* v
 		a.value = values ? values[i] : 0;
 		a.pad = 0;
 		if (a.value < 0) {
-			set_error(what(i) + " has the negative value " + std::to_string(a.value) + ": a stamp writes occupancy ids >= 0 (-1 is a free cell)");
+			set_error(h.name(i) + " has the negative value " + std::to_string(a.value) + ": a stamp writes occupancy ids >= 0 (-1 is a free cell)");
 			return PP_ERR_INVALID;
 		}
 		if (a.from != a.from || a.to != a.to) {
-			set_error(what(i) + " has a NaN in its window");
+			set_error(h.name(i) + " has a NaN in its window");
 			return PP_ERR_INVALID;
 		}
 	}
@@ -616,10 +627,10 @@ int stamp_finish_target(pp_map* map)
 }
 
 /// The arguments of a locate call that do not depend on who holds the plans (pp_planner_locate, pp_pipeline_locate): the parameters, the
-/// vehicle poses and the windows, which go into `plans` (what(i) names plan i in a refusal)
-template <typename Name>
-int locate_check(int n, const double* poses, const double* from_length, const double* to_length, const pp_locate_params* params, Name what, std::vector<LocateArg>& plans)
+/// vehicle poses and the windows, which go into `plans` (h.name(i) names plan i in a refusal)
+int locate_check(const HeldPlans& h, const double* poses, const double* from_length, const double* to_length, const pp_locate_params* params, std::vector<LocateArg>& plans)
 {
+	const int n = h.n;
 	if (n > 0 && !params) {
 		set_error("invalid arguments (null params: a pp_locate_params with spacing > 0 is needed)");
 		return PP_ERR_INVALID;
@@ -644,23 +655,126 @@ int locate_check(int n, const double* poses, const double* from_length, const do
 		a.from = from_length ? from_length[i] : -HUGE_VAL;
 		a.to = to_length ? to_length[i] : HUGE_VAL;
 		if (!std::isfinite(a.pose[0]) || !std::isfinite(a.pose[1]) || !std::isfinite(a.pose[2])) {
-			set_error(what(i) + " has a vehicle pose that is not finite");
+			set_error(h.name(i) + " has a vehicle pose that is not finite");
 			return PP_ERR_INVALID;
 		}
 		if (a.from != a.from || a.to != a.to) {
-			set_error(what(i) + " has a NaN in its window");
+			set_error(h.name(i) + " has a NaN in its window");
 			return PP_ERR_INVALID;
 		}
 	}
 	return PP_OK;
 }
 
-/// a call's result records to the caller, who may not want them (post-processing and re-validation, batch and by ticket)
-template <typename Rec>
-void records_out(const std::vector<Rec>& host, Rec* out)
+// ---- the services over held plans, one core each (pp_held_plans.hpp); both holders' extern "C" entries end here
+
+/// the plans of a batch planner's last batch: queries 0 .. n-1
+HeldPlans batch_plans(pp_planner* p, int n)
 {
-	if (out)
-		std::copy(host.begin(), host.end(), out);
+	HeldPlans h;
+	h.pl = p;
+	h.stream = p->map->ctx->stream;
+	h.footprint = p->footprint;
+	h.ownView = p->args.m;
+	h.n = n;
+	h.rows = (size_t)p->maxBatch;
+	return h;
+}
+
+/// what the batch entries refuse first: a null planner, a count outside the last batch, a pipeline's buffer set (`byTicket`: the pipeline's entry for it)
+int batch_check(const pp_planner* p, int n, const char* byTicket)
+{
+	if (!p || n < 0 || n > p->lastBatch) {
+		set_error("invalid arguments (0 <= n_queries <= last batch)");
+		return PP_ERR_INVALID;
+	}
+	if (p->pipelineOwned) {
+		set_error(std::string("this planner is a pipeline's buffer set: ") + byTicket);
+		return PP_ERR_INVALID;
+	}
+	return PP_OK;
+}
+
+/// a copy of the buffer set's search arguments under `view`: the set's own `args`, which a pipeline's top-up launches read, are not written
+SearchArgs held_args(const HeldPlans& h, const ppd::MapView& view)
+{
+	SearchArgs args = h.pl->args;
+	args.m = view;
+	return args;
+}
+
+/// HybridAStar::SearchPath's post-processing of the plans of h under h.ownView: k_postprocess over a batch planner's queries, k_postprocess_tickets (which
+/// also checks the smoothed path against the holder's footprint) over held slots.  The results stay in `g` for the getters.
+int post_process_plans(const HeldPlans& h, PostGroup& g, float path_interpolation, const pp_smoother_params* smoother, int max_points, pp_post_result* results_host)
+{
+	if (h.n == 0)
+		return PP_OK;
+	pp_planner* const pl = h.pl;
+	pp_map* const map = pl->map;
+	PP_HIP_TRY(hipSetDevice(map->ctx->device));
+	PP_HIP_TRY(held_grow(h, g, max_points, pl->maxPath));
+	const PostParams pp = post_params(path_interpolation, smoother, pl->params.min_turning_radius, max_points);
+	const SearchArgs args = held_args(h, h.ownView);
+	const uint32_t *obst = map->obstLabel[map->obstResult].get(), *voro = map->voroLabel[map->voroResult].get();
+	if (int rc = held_run(h, g.rec, {}, results_host, [&](const int32_t* slotsDev) {
+			const size_t lds = (size_t)max_points * 16;
+			if (slotsDev)
+				hipLaunchKernelGGL(k_postprocess_tickets, dim3(h.n), dim3(kPostThreads), lds, h.stream, args, pp, h.foot(), h.n, slotsDev, pl->paths.get(), pl->rsLogs.get(),
+					pl->results.get(), obst, voro, g.buffers());
+			else
+				hipLaunchKernelGGL(k_postprocess, dim3(h.n), dim3(kPostThreads), lds, h.stream, args, pp, h.n, pl->paths.get(), pl->rsLogs.get(), pl->results.get(), obst, voro,
+					g.buffers()); // (g.rec has been sized by now)
+			return hipGetLastError();
+		}, &g.host))
+		return rc;
+	g.points = max_points;
+	return PP_OK;
+}
+
+/// Are the plans of h still collision-free on `target` under its view of this moment (every writer of a map's grids has drained the map's stream before it returned)?
+int revalidate_plans(const HeldPlans& h, HeldBuffers<NoPlanArg, pp_revalidate_result>& b, pp_map* target, pp_revalidate_result* results_host)
+{
+	if (h.n == 0)
+		return PP_OK;
+	pp_planner* const pl = h.pl;
+	PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
+	const SearchArgs args = held_args(h, target->view());
+	return held_run(h, b, {}, results_host, [&](const int32_t* slotsDev) {
+		hipLaunchKernelGGL(k_revalidate_tickets, dim3(h.n), dim3(64), 0, h.stream, args, h.foot(), h.n, slotsDev, pl->paths.get(), pl->rsLogs.get(), pl->results.get(), b.out.get());
+		return hipGetLastError();
+	});
+}
+
+/// The plans of h stamped into `target`'s occupancy grid (`plans`: stamp_check's) under the target's view of this moment, with the holder's footprint or its
+/// own map's point-validator disc.  The target's views are refreshed on the target's own stream once the holder's stream has been drained, i.e. behind the stamp.
+int stamp_plans(const HeldPlans& h, HeldBuffers<StampArg, pp_stamp_result>& b, pp_map* target, const std::vector<StampArg>& plans, const pp_stamp_params* params,
+	pp_stamp_result* results_host)
+{
+	if (h.n == 0)
+		return PP_OK;
+	pp_planner* const pl = h.pl;
+	PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
+	if (int rc = stamp_prepare_target(target))
+		return rc;
+	const SearchArgs args = held_args(h, target->view());
+	const Footprint discs = stamp_discs(h.footprint, pl->map);
+	if (int rc = held_run(h, b, plans, results_host,
+			[&](const int32_t* slotsDev) { return launch_stamp(h.stream, args, discs, params, h.n, slotsDev, b.args.get(), pl, target->occ32.get(), b.out.get()); }))
+		return rc;
+	return stamp_finish_target(target);
+}
+
+/// The vehicles of `plans` (locate_check's) located on the plans of h.  The kernel reads and writes no map: the launch travels with the holder's own view.
+int locate_plans(const HeldPlans& h, HeldBuffers<LocateArg, pp_locate_result>& b, const std::vector<LocateArg>& plans, const pp_locate_params* params,
+	pp_locate_result* results_host)
+{
+	if (h.n == 0)
+		return PP_OK;
+	pp_planner* const pl = h.pl;
+	PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
+	const SearchArgs args = held_args(h, h.ownView);
+	return held_run(h, b, plans, results_host,
+		[&](const int32_t* slotsDev) { return launch_locate(h.stream, args, params, h.n, slotsDev, b.args.get(), pl, b.out.get()); });
 }
 
 void free_planner(pp_planner* p)
@@ -1438,157 +1552,61 @@ int pp_planner_postprocess(pp_planner* planner, int32_t n_queries, float path_in
 		set_error("invalid arguments (n_queries <= last batch, 8 <= max_points <= 2048, path_interpolation > 0)");
 		return PP_ERR_INVALID;
 	}
-	pp_map* map = planner->map;
-	if (int rc = post_check_grids(map))
+	if (int rc = post_check_grids(planner->map))
 		return rc;
 	if (n_queries == 0)
 		return PP_OK;
-	PP_HIP_TRY(hipSetDevice(map->ctx->device));
-	hipStream_t s = map->ctx->stream;
-	const size_t B = (size_t)planner->maxBatch;
-	if (planner->postMaxPoints < max_points) {
-		planner->postMaxPoints = planner->postDone = 0; // until every buffer below exists again: a failed allocation must not leave a stale capacity behind
-		PP_HIP_TRY(planner->postRatios.alloc(B * max_points * 8));
-		PP_HIP_TRY(planner->postResampled.alloc(B * max_points * 24));
-		PP_HIP_TRY(planner->postSmoothed.alloc(B * max_points * 24));
-		PP_HIP_TRY(planner->postCusp.alloc(B * max_points));
-		PP_HIP_TRY(planner->postOptimise.alloc(B * max_points));
-		planner->postMaxPoints = max_points;
-	}
-	PP_HIP_TRY(planner->postEdgeEnd.ensure(B * (size_t)(planner->maxPath + 1) * 8));
-	PP_HIP_TRY(planner->postOut.ensure(B * sizeof(pp_post_result)));
-	const PostBuffers post { planner->postRatios, planner->postResampled, planner->postSmoothed, planner->postCusp, planner->postOptimise, planner->postEdgeEnd, planner->postOut };
-	const PostParams P = post_params(path_interpolation, smoother, planner->params.min_turning_radius, max_points);
-	planner->args.m = map->view();
-	const size_t lds = (size_t)max_points * 16;
-	hipLaunchKernelGGL(k_postprocess, dim3(n_queries), dim3(kPostThreads), lds, s, planner->args, P, n_queries, planner->paths, planner->rsLogs, planner->results,
-		map->obstLabel[map->obstResult].get(), map->voroLabel[map->voroResult].get(), post);
-	PP_HIP_TRY(hipGetLastError());
-	planner->hostPost.resize(n_queries);
-	PP_HIP_TRY(hipMemcpyAsync(planner->hostPost.data(), planner->postOut, (size_t)n_queries * sizeof(pp_post_result), hipMemcpyDeviceToHost, s));
-	PP_HIP_TRY(hipStreamSynchronize(s));
-	planner->postDone = n_queries;
-	planner->postPoints = max_points;
-	records_out(planner->hostPost, results_host);
-	return PP_OK;
+	planner->args.m = planner->map->view(); // the planner's own map as it is now
+	return post_process_plans(batch_plans(planner, n_queries), planner->post, path_interpolation, smoother, max_points, results_host);
 }
 
 int pp_planner_get_processed_path(pp_planner* planner, int32_t q, double* sampled_host, uint8_t* cusp_host, double* smoothed_host)
 {
-	if (!planner || q < 0 || q >= planner->postDone) {
+	if (!planner || q < 0 || q >= (int)planner->post.host.size()) {
 		set_error("no post-processed result for this query (pp_planner_postprocess first)");
 		return PP_ERR_INVALID;
 	}
 	PP_HIP_TRY(hipSetDevice(planner->map->ctx->device));
-	const size_t n = (size_t)planner->hostPost[q].n_points, cap = (size_t)planner->postPoints;
-	if (n == 0)
-		return PP_OK;
-	if (sampled_host)
-		PP_HIP_TRY(hipMemcpy(sampled_host, planner->postResampled + (size_t)q * cap * 3, n * 24, hipMemcpyDeviceToHost));
-	if (cusp_host)
-		PP_HIP_TRY(hipMemcpy(cusp_host, planner->postCusp + (size_t)q * cap, n, hipMemcpyDeviceToHost));
-	if (smoothed_host)
-		PP_HIP_TRY(hipMemcpy(smoothed_host, planner->postSmoothed + (size_t)q * cap * 3, n * 24, hipMemcpyDeviceToHost));
+	const PostGroup& g = planner->post;
+	hipStream_t s = planner->map->ctx->stream;
+	PP_HIP_TRY(g.copy_out((size_t)q * (size_t)g.points, (size_t)g.host[q].n_points, 0, sampled_host, cusp_host, smoothed_host, s));
+	PP_HIP_TRY(hipStreamSynchronize(s));
 	return PP_OK;
 }
 
 int pp_planner_revalidate(pp_planner* planner, pp_map* target, int32_t n_queries, pp_revalidate_result* results_host)
 {
-	if (!planner || n_queries < 0 || n_queries > planner->lastBatch) {
-		set_error("invalid arguments (0 <= n_queries <= last batch)");
-		return PP_ERR_INVALID;
-	}
-	if (planner->pipelineOwned) {
-		set_error("this planner is a pipeline's buffer set: pp_pipeline_revalidate re-validates its held tickets");
-		return PP_ERR_INVALID;
-	}
+	if (int rc = batch_check(planner, n_queries, "pp_pipeline_revalidate re-validates its held tickets"))
+		return rc;
 	pp_map* const map = target ? target : planner->map;
 	if (int rc = revalidate_check_target(planner->map, map))
 		return rc;
-	if (n_queries == 0)
-		return PP_OK;
-	PP_HIP_TRY(hipSetDevice(planner->map->ctx->device));
-	hipStream_t s = planner->map->ctx->stream;
-	PP_HIP_TRY(planner->revOut.ensure((size_t)planner->maxBatch * sizeof(pp_revalidate_result)));
-	SearchArgs args = planner->args; // a copy: the planner's own arguments keep its own map's view
-	args.m = map->view();
-	Footprint foot {}; // n = 0: the point validator
-	if (planner->footprint)
-		foot = planner->footprint->fp;
-	hipLaunchKernelGGL(k_revalidate_tickets, dim3(n_queries), dim3(64), 0, s, args, foot, n_queries, (const int32_t*)nullptr, planner->paths.get(), planner->rsLogs.get(),
-		planner->results.get(), planner->revOut.get());
-	PP_HIP_TRY(hipGetLastError());
-	std::vector<pp_revalidate_result> host((size_t)n_queries);
-	PP_HIP_TRY(hipMemcpyAsync(host.data(), planner->revOut, (size_t)n_queries * sizeof(pp_revalidate_result), hipMemcpyDeviceToHost, s));
-	PP_HIP_TRY(hipStreamSynchronize(s));
-	records_out(host, results_host);
-	return PP_OK;
+	return revalidate_plans(batch_plans(planner, n_queries), planner->reval, map, results_host);
 }
 
 int pp_planner_stamp(pp_planner* planner, pp_map* target, int32_t n_queries, const int32_t* values, const double* from_length, const double* to_length,
 	const pp_stamp_params* params, pp_stamp_result* results_host)
 {
-	if (!planner || n_queries < 0 || n_queries > planner->lastBatch) {
-		set_error("invalid arguments (0 <= n_queries <= last batch)");
-		return PP_ERR_INVALID;
-	}
-	if (planner->pipelineOwned) {
-		set_error("this planner is a pipeline's buffer set: pp_pipeline_stamp stamps its held tickets");
-		return PP_ERR_INVALID;
-	}
+	if (int rc = batch_check(planner, n_queries, "pp_pipeline_stamp stamps its held tickets"))
+		return rc;
 	pp_map* const map = target ? target : planner->map;
+	const HeldPlans h = batch_plans(planner, n_queries);
 	std::vector<StampArg> plans;
-	if (int rc = stamp_check(planner->map, map, n_queries, values, from_length, to_length, params, [](int i) { return "query " + std::to_string(i); }, plans))
+	if (int rc = stamp_check(h, map, values, from_length, to_length, params, plans))
 		return rc;
-	if (n_queries == 0)
-		return PP_OK;
-	PP_HIP_TRY(hipSetDevice(planner->map->ctx->device));
-	hipStream_t s = planner->map->ctx->stream; // (the target's too: one context)
-	if (int rc = stamp_prepare_target(map))
-		return rc;
-	PP_HIP_TRY(planner->stampArgs.ensure((size_t)planner->maxBatch * sizeof(StampArg)));
-	PP_HIP_TRY(planner->stampOut.ensure((size_t)planner->maxBatch * sizeof(pp_stamp_result)));
-	SearchArgs args = planner->args; // a copy: the planner's own arguments keep its own map's view
-	args.m = map->view();
-	PP_HIP_TRY(hipMemcpyAsync(planner->stampArgs, plans.data(), (size_t)n_queries * sizeof(StampArg), hipMemcpyHostToDevice, s));
-	PP_HIP_TRY(launch_stamp(s, args, stamp_discs(planner->footprint, planner->map), params, n_queries, nullptr, planner->stampArgs.get(), planner, map->occ32.get(),
-		planner->stampOut.get()));
-	std::vector<pp_stamp_result> host((size_t)n_queries);
-	PP_HIP_TRY(hipMemcpyAsync(host.data(), planner->stampOut, (size_t)n_queries * sizeof(pp_stamp_result), hipMemcpyDeviceToHost, s));
-	PP_HIP_TRY(hipStreamSynchronize(s));
-	if (int rc = stamp_finish_target(map))
-		return rc;
-	records_out(host, results_host);
-	return PP_OK;
+	return stamp_plans(h, planner->stamp, map, plans, params, results_host);
 }
 
 int pp_planner_locate(pp_planner* planner, int32_t n_queries, const double* poses_host, const double* from_length, const double* to_length, const pp_locate_params* params,
 	pp_locate_result* results_host)
 {
-	if (!planner || n_queries < 0 || n_queries > planner->lastBatch) {
-		set_error("invalid arguments (0 <= n_queries <= last batch)");
-		return PP_ERR_INVALID;
-	}
-	if (planner->pipelineOwned) {
-		set_error("this planner is a pipeline's buffer set: pp_pipeline_locate locates vehicles on its held tickets");
-		return PP_ERR_INVALID;
-	}
-	std::vector<LocateArg> plans;
-	if (int rc = locate_check(n_queries, poses_host, from_length, to_length, params, [](int i) { return "query " + std::to_string(i); }, plans))
+	if (int rc = batch_check(planner, n_queries, "pp_pipeline_locate locates vehicles on its held tickets"))
 		return rc;
-	if (n_queries == 0)
-		return PP_OK;
-	PP_HIP_TRY(hipSetDevice(planner->map->ctx->device));
-	hipStream_t s = planner->map->ctx->stream;
-	PP_HIP_TRY(planner->locateArgs.ensure((size_t)planner->maxBatch * sizeof(LocateArg)));
-	PP_HIP_TRY(planner->locateOut.ensure((size_t)planner->maxBatch * sizeof(pp_locate_result)));
-	PP_HIP_TRY(hipMemcpyAsync(planner->locateArgs, plans.data(), (size_t)n_queries * sizeof(LocateArg), hipMemcpyHostToDevice, s));
-	PP_HIP_TRY(launch_locate(s, planner->args, params, n_queries, nullptr, planner->locateArgs.get(), planner, planner->locateOut.get()));
-	std::vector<pp_locate_result> host((size_t)n_queries);
-	PP_HIP_TRY(hipMemcpyAsync(host.data(), planner->locateOut, (size_t)n_queries * sizeof(pp_locate_result), hipMemcpyDeviceToHost, s));
-	PP_HIP_TRY(hipStreamSynchronize(s));
-	records_out(host, results_host);
-	return PP_OK;
+	const HeldPlans h = batch_plans(planner, n_queries);
+	std::vector<LocateArg> plans;
+	if (int rc = locate_check(h, poses_host, from_length, to_length, params, plans))
+		return rc;
+	return locate_plans(h, planner->locate, plans, params, results_host);
 }
 
 int pp_planner_last_timings(pp_planner* planner, float* wavefront_ms, float* search_ms)

@@ -658,12 +658,7 @@ class HybridAStarBatch:
         Smoother::Parameters fields to override (defaults: smoother.h:28-60, max_curvature = 1 / min_turning_radius).
         Returns one PostResult per query (n_points, smoothing_status, iterations, length)."""
         n = len(self._results) if n_queries is None else int(n_queries)
-        sp = None
-        if smoother is not None:
-            d = dict(step_tolerance=1e-3, max_iterations=2000, learning_rate=0.01, path_weight=0.0, smooth_weight=0.4, voronoi_weight=0.02, collision_weight=0.2,
-                     curvature_weight=0.4, collision_ratio=0.2, max_curvature=1.0 / self.params.min_turning_radius)
-            d.update(smoother)
-            sp = SmootherParams(**d)
+        sp = _smoother_params(smoother, self.params)
         out = (PostResult * max(n, 1))()
         check(self.lib.pp_planner_postprocess(self.h, n, C.c_float(path_interpolation), C.byref(sp) if sp is not None else None, int(max_points), out))
         self._post = list(out)[:n]
@@ -678,8 +673,7 @@ class HybridAStarBatch:
         cusp = np.empty(n, dtype=np.uint8)
         if n:
             check(self.lib.pp_planner_get_processed_path(self.h, q, ptr(sampled), ptr(cusp), ptr(smoothed)))
-        return dict(sampled=sampled, cusp=cusp.astype(bool), smoothed=smoothed, status=r.smoothing_status, iterations=r.iterations, length=r.length,
-                    path=smoothed if r.smoothing_status >= 0 else sampled)
+        return _processed_path(r, sampled, cusp, smoothed)
 
     def revalidate(self, n_queries=None, map_set=None):
         """Are the plans of the first n queries of the last batch still collision-free on `map_set` (an OccupancyMapSet of the same
@@ -938,12 +932,7 @@ class HybridAStarPipeline:
         postprocess(tickets) is the form by ticket: it works on the held queries named, with buffers sized by the call, may run with
         queries in flight, and checks the smoothed samples against the footprint."""
         n = self.capacity if n_slots is None else int(n_slots)
-        sp = None
-        if smoother is not None:
-            d = dict(step_tolerance=1e-3, max_iterations=2000, learning_rate=0.01, path_weight=0.0, smooth_weight=0.4, voronoi_weight=0.02, collision_weight=0.2,
-                     curvature_weight=0.4, collision_ratio=0.2, max_curvature=1.0 / self.params.min_turning_radius)
-            d.update(smoother)
-            sp = SmootherParams(**d)
+        sp = _smoother_params(smoother, self.params)
         out = (PostResult * max(n, 1))()
         check(self.lib.pp_planner_postprocess(self.planner_h, n, C.c_float(path_interpolation), C.byref(sp) if sp is not None else None, int(max_points), out))
         self._post = list(out)[:n]
@@ -959,8 +948,7 @@ class HybridAStarPipeline:
         cusp = np.empty(n, dtype=np.uint8)
         if n:
             check(self.lib.pp_planner_get_processed_path(self.planner_h, slot, ptr(sampled), ptr(cusp), ptr(smoothed)))
-        return dict(sampled=sampled, cusp=cusp.astype(bool), smoothed=smoothed, status=r.smoothing_status, iterations=r.iterations, length=r.length,
-                    path=smoothed if r.smoothing_status >= 0 else sampled)
+        return _processed_path(r, sampled, cusp, smoothed)
 
     def postprocess(self, tickets, path_interpolation=0.1, smoother=None, max_points=2048):
         """HybridAStar::SearchPath's post-processing (hybrid_a_star.cpp:260-304) of the completed, HELD queries `tickets`
@@ -969,12 +957,7 @@ class HybridAStarPipeline:
         against it: smoothing_status -2 when one fails, and the sampled path is then the result.  Raises PPError, with nothing launched,
         for a ticket that is unknown, released, in flight or given twice."""
         t = np.ascontiguousarray(tickets, dtype=np.uint64).reshape(-1)
-        sp = None
-        if smoother is not None:
-            d = dict(step_tolerance=1e-3, max_iterations=2000, learning_rate=0.01, path_weight=0.0, smooth_weight=0.4, voronoi_weight=0.02, collision_weight=0.2,
-                     curvature_weight=0.4, collision_ratio=0.2, max_curvature=1.0 / self.params.min_turning_radius)
-            d.update(smoother)
-            sp = SmootherParams(**d)
+        sp = _smoother_params(smoother, self.params)
         out = (PostResult * max(len(t), 1))()
         check(self.lib.pp_pipeline_postprocess(self.h, len(t), ptr(t), C.c_float(path_interpolation), C.byref(sp) if sp is not None else None, int(max_points), out))
         self._post_by_ticket = {int(x): out[i] for i, x in enumerate(t)}
@@ -996,9 +979,7 @@ class HybridAStarPipeline:
         out = []
         for i, x in enumerate(t):
             r, n = post[int(x)], int(n_points[i])
-            a, b = sampled[i, :n].copy(), smoothed[i, :n].copy()
-            out.append(dict(sampled=a, cusp=cusp[i, :n].astype(bool), smoothed=b, status=r.smoothing_status, iterations=r.iterations, length=r.length,
-                            path=b if r.smoothing_status >= 0 else a))
+            out.append(_processed_path(r, sampled[i, :n].copy(), cusp[i, :n], smoothed[i, :n].copy()))
         if release:
             for x in t:
                 self._held.pop(int(x), None)
@@ -1078,35 +1059,47 @@ class HybridAStarPipeline:
             pass
 
 
+def _smoother_params(smoother, params):
+    """Smoother::Parameters (smoother.h:28-60, max_curvature = 1 / min_turning_radius) with the fields of the dict `smoother` overridden; None stays NULL:
+    the library's defaults, which are the same"""
+    if smoother is None:
+        return None
+    d = dict(step_tolerance=1e-3, max_iterations=2000, learning_rate=0.01, path_weight=0.0, smooth_weight=0.4, voronoi_weight=0.02, collision_weight=0.2,
+             curvature_weight=0.4, collision_ratio=0.2, max_curvature=1.0 / params.min_turning_radius)
+    d.update(smoother)
+    return SmootherParams(**d)
+
+
+def _processed_path(r, sampled, cusp, smoothed):
+    """a processed path as the get_processed_path* calls return it, from its PostResult and arrays; `path` = what HybridAStar::GetPath() returns"""
+    return dict(sampled=sampled, cusp=cusp.astype(bool), smoothed=smoothed, status=r.smoothing_status, iterations=r.iterations, length=r.length,
+                path=smoothed if r.smoothing_status >= 0 else sampled)
+
+
+def _per_plan(x, n, dtype=np.float64):
+    """a per-plan array of a held-plan call as the C ABI takes it: None stays NULL, a scalar is given to every plan"""
+    if x is None:
+        return None
+    a = np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=dtype), (n,)) if np.ndim(x) == 0 else x, dtype=dtype).reshape(-1)
+    if len(a) != n:
+        raise ValueError("one entry per plan: got %d for %d plans" % (len(a), n))
+    return a
+
+
 def _stamp(n, values, from_length, to_length, spacing, margin, call):
-    """the per-plan arrays of a stamp call as the C ABI takes them (None stays NULL; a scalar is given to every plan), the call, its records"""
-    def per_plan(x, dtype):
-        if x is None:
-            return None
-        a = np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=dtype), (n,)) if np.ndim(x) == 0 else x, dtype=dtype).reshape(-1)
-        if len(a) != n:
-            raise ValueError("one entry per plan: got %d for %d plans" % (len(a), n))
-        return a
+    """the per-plan arrays of a stamp call, the call, its records"""
     out = (StampResult * max(n, 1))()
-    check(call(per_plan(values, np.int32), per_plan(from_length, np.float64), per_plan(to_length, np.float64), StampParams(float(spacing), float(margin), 0), out))
+    check(call(_per_plan(values, n, np.int32), _per_plan(from_length, n), _per_plan(to_length, n), StampParams(float(spacing), float(margin), 0), out))
     return list(out)[:n]
 
 
 def _locate(n, poses, from_length, to_length, spacing, heading_weight, call):
-    """the per-plan arrays of a locate call as the C ABI takes them (a window of None stays NULL; a scalar is given to every plan), the call, its records"""
+    """the vehicle poses and per-plan arrays of a locate call, the call, its records"""
     v = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
     if len(v) != n:
         raise ValueError("one vehicle pose per plan: got %d for %d plans" % (len(v), n))
-
-    def per_plan(x):
-        if x is None:
-            return None
-        a = np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float64), (n,)) if np.ndim(x) == 0 else x, dtype=np.float64).reshape(-1)
-        if len(a) != n:
-            raise ValueError("one entry per plan: got %d for %d plans" % (len(a), n))
-        return a
     out = (LocateResult * max(n, 1))()
-    check(call(v, per_plan(from_length), per_plan(to_length), LocateParams(float(spacing), float(heading_weight)), out))
+    check(call(v, _per_plan(from_length, n), _per_plan(to_length, n), LocateParams(float(spacing), float(heading_weight)), out))
     return list(out)[:n]
 
 
