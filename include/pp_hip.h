@@ -662,6 +662,82 @@ int pp_pipeline_locate(pp_pipeline* pipeline, int32_t n, const uint64_t* tickets
  * and for a planner that is a pipeline's buffer set (pp_pipeline_locate knows which slots are held). */
 int pp_planner_locate(pp_planner* planner, int32_t n_queries, const double* poses_host, const double* from_length, const double* to_length,
 	const pp_locate_params* params, pp_locate_result* results_host);
+/* ---- speed profiles along held plans, by ticket ----------------------------------------------------------------------------------------------
+ * A SPEED PROFILE of a plan is, for every sample of the stamp's schedule inside a window of arc length, the speed v the vehicle may drive there and
+ * the time t at which it arrives there: what a controller that has located its vehicle at s tracks, and what turns "the next 5 seconds" into the
+ * window [s, s'] of a stamp.  One wave per plan (k_speed_profile_tickets) reads the plan where the search left it.  It writes nothing but its own
+ * buffers, so the call is legal beside queries in flight.  All arithmetic below is in double, in the order written (the library is built without
+ * contraction), unless a float is named.
+ *  Samples. The stamp's schedule, exactly: edges 1 .. n_path - 1 root first; S_e the sequential root-first sum, so `length` has
+ *           pp_revalidate_result::length's bits; edge e of length L has n = L > 0 ? (int)ceil(L / spacing) : 0 steps (capped at 2^19) and the samples
+ *           (double)k / (double)n for k = 0 .. n, at arc length s = S_e + ratio * L -- both ends of every edge, so a junction is sampled twice at one s.
+ *           A one-pose plan has one sample: its pose, at s = 0.  The samples with from <= s <= to, in schedule order, are the SEQUENCE j = 0 .. N - 1
+ *           (one run of the schedule: s does not decrease along it).  N == 0: status 1.  N > max_samples: status -5, and nothing is written to the
+ *           plan's sample rows.
+ *  Per sample. The pose is the path object's interpolation at the ratio.  The direction dir_j is the path object's travel direction at the ratio; a
+ *           sample whose path object reports no motion there (a Reeds-Shepp path of length 0) takes the direction of its predecessor in the sequence,
+ *           and has none while no sample of the sequence has moved.  kappa_j >= 0 is |curvature| of a constant-steer edge; on the Reeds-Shepp edge
+ *           1 / min_turning_radius on a turning motion and 0 on a straight one, the motion being the one the direction is read from.
+ *  Cusp.    Sample j > 0 is a CUSP STOP iff dir_j and dir_{j-1} both exist and differ.  At a junction the second of the two samples is the stop.  A
+ *           direction change inside the Reeds-Shepp edge stops at the first sample behind it, up to `spacing` late: the library picks no spacing for
+ *           the caller.
+ *  Cap.     c = dir_j forward ? v_max_forward : v_max_reverse (a sample without a direction: v_max_reverse).  If kappa_j > 0: c = min(c, sqrt(a_lat /
+ *           kappa_j)).  If clearance_gain > 0: c = min(c, v_floor + clearance_gain * (double)cl_j), cl_j the float `clearance` of the footprint state
+ *           check of the sample pose ("vehicle footprint", step 3) on the TARGET map's distance grid -- with the holder's footprint its discs, without
+ *           one the disc (0, 0, the target's min_safe_radius), as re-validation takes the target's tunables; a pose that fails steps 1-2 (which
+ *           includes a negative clearance) has cl_j = 0.  w_j = c * c; then w_j = 0 at a cusp stop; then w_0 = min(w_0, v_start^2); then
+ *           w_{N-1} = min(w_{N-1}, v_end^2) (for N == 1 in this order).
+ *  Envelope. A_i = w_i - (2 a_acc) s_i, F_j = min_{i <= j} A_i, fwd_j = F_j + (2 a_acc) s_j: what accelerating at a_acc from any earlier sample allows.
+ *           B_i = w_i + (2 a_dec) s_i, G_j = min_{i >= j} B_i, bwd_j = G_j - (2 a_dec) s_j: what braking at a_dec for any later sample allows.
+ *           e_j = max(0, min(w_j, min(fwd_j, bwd_j))), v_j = sqrt(e_j).  min is exact, so the result does not depend on the order of evaluation.
+ *  Time.    t_0 = 0, t_{j+1} = t_j + (dt_j + (dwell if j + 1 is a cusp stop)).  With ds = s_{j+1} - s_j: ds == 0 gives dt_j = 0; else v_j + v_{j+1} > 0 gives
+ *           dt_j = (2 ds) / (v_j + v_{j+1}); else both ends stand: x = ds * a_dec / (a_acc + a_dec), dt_j = sqrt(2 x / a_acc) + sqrt(2 (ds - x) / a_dec).
+ *           t is the sequential sum in sample order, and the device forms it in that order: t never decreases along the sequence (a sum formed in
+ *           another order, e.g. a tree-shaped scan, would differ by a few units of 2^-53 times the number of samples and could step down by an ulp).
+ *  - samples_host (may be NULL) is [n][max_samples][3] doubles (s, v, t); rows beyond a plan's n_samples, and every row of a plan whose status is
+ *    not 0, are left untouched.  results_host (may be NULL) belongs to tickets[i].
+ *  - target == NULL: the pipeline's own map as it is now.  Otherwise a pp_map of the same context, of any geometry.  It is read only when
+ *    clearance_gain > 0, and only then must it have a distance grid.
+ *  - PP_ERR_INVALID, nothing launched, the pipeline usable as before, the message naming the first offending ticket or argument: n < 0 or
+ *    n > capacity; a ticket that is unknown, released, still in flight or given twice; NULL params with n > 0; spacing, v_max_forward, v_max_reverse,
+ *    a_acc, a_dec or a_lat not finite and > 0; dwell, clearance_gain or v_floor not finite and >= 0; max_samples < 1; a NaN in a window array; a
+ *    v_start or v_end that is not finite and >= 0; a target of another context; with clearance_gain > 0 a target without a distance grid.
+ *    n == 0 is PP_OK.
+ *  - The pipeline owns the slot list, the per-ticket arguments, the result buffer and the sample rows (4 + 32 + 72 bytes per ticket and 24 bytes per
+ *    sample of the largest n x max_samples so far), kept aside like the post-processing buffers when they have to grow beside queries in flight. */
+typedef struct pp_speed_profile_params {
+	double spacing;        /* > 0, finite, metres: the sample spacing (the stamp's and the locate call's meaning) */
+	double v_max_forward;  /* > 0, finite, m/s */
+	double v_max_reverse;  /* > 0, finite, m/s */
+	double a_acc;          /* > 0, finite, m/s^2 */
+	double a_dec;          /* > 0, finite, m/s^2 */
+	double a_lat;          /* > 0, finite, m/s^2: v^2 kappa <= a_lat */
+	double dwell;          /* >= 0, finite, s: standstill added at every cusp stop */
+	double clearance_gain; /* >= 0, finite, 1/s; 0: no clearance term, no map is read */
+	double v_floor;        /* >= 0, finite, m/s: the clearance term's cap at clearance 0 */
+} pp_speed_profile_params;
+typedef struct pp_speed_profile_result {
+	int32_t status;          /* 0 profiled; 1 no sample in the window; -1 no plan; -4 path longer than the planner's path capacity;
+	                            -5 more than max_samples samples in the window (n_samples says how many) */
+	int32_t n_samples;       /* N */
+	int32_t n_cusps;         /* cusp stops in the sequence */
+	int32_t reserved;
+	double  length;          /* pp_revalidate_result::length, bit for bit */
+	double  s_first, s_last; /* s_0, s_{N-1} */
+	double  duration;        /* t_{N-1}, seconds */
+	double  v_peak;          /* max_j v_j */
+	double  min_clearance;   /* min_j cl_j as double; +inf when clearance_gain == 0 */
+	double  s_min_clearance; /* the smallest s at which it is taken; 0 when clearance_gain == 0 */
+} pp_speed_profile_result;   /* 72 bytes; for status != 0 every field but status, n_samples and length is zero */
+int pp_pipeline_speed_profile(pp_pipeline* pipeline, pp_map* target /* NULL: the pipeline's map as it is now */, int32_t n, const uint64_t* tickets,
+	const double* from_length, const double* to_length, const double* v_start /* NULL: 0 */, const double* v_end /* NULL: 0 */,
+	const pp_speed_profile_params* params, int32_t max_samples, double* samples_host /* may be NULL */, pp_speed_profile_result* results_host /* may be NULL */);
+/* The same kernel over the first n_queries queries of the planner's last batch (identity slots), on the planner's stream, with the planner's
+ * footprint if it has one.  PP_ERR_INVALID as above, and for a planner that is a pipeline's buffer set (pp_pipeline_speed_profile knows which slots
+ * are held). */
+int pp_planner_speed_profile(pp_planner* planner, pp_map* target /* NULL: own map */, int32_t n_queries, const double* from_length, const double* to_length,
+	const double* v_start, const double* v_end, const pp_speed_profile_params* params, int32_t max_samples, double* samples_host,
+	pp_speed_profile_result* results_host);
 /* Diagnostics: waves of the search grid that are alive right now (a blocking device-to-host copy; -1 on error). */
 int pp_pipeline_alive_waves(pp_pipeline* pipeline);
 pp_planner* pp_pipeline_planner(pp_pipeline* pipeline);           /* the buffer set: set_nonholo_table, set_primitives, get_path(slot), ... */

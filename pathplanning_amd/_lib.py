@@ -104,6 +104,21 @@ class LocateParams(C.Structure):
     _fields_ = [("spacing", C.c_double), ("heading_weight", C.c_double)]
 
 
+class SpeedProfileParams(C.Structure):
+    """pp_speed_profile_params: the sample spacing (> 0, metres), the speed limits by direction (> 0, m/s), the longitudinal and lateral acceleration
+    limits (> 0, m/s^2), the dwell at a cusp stop (>= 0, s) and the clearance term cap <= v_floor + clearance_gain * clearance (both >= 0; gain 0: none)"""
+    _fields_ = [("spacing", C.c_double), ("v_max_forward", C.c_double), ("v_max_reverse", C.c_double), ("a_acc", C.c_double), ("a_dec", C.c_double),
+                ("a_lat", C.c_double), ("dwell", C.c_double), ("clearance_gain", C.c_double), ("v_floor", C.c_double)]
+
+
+class SpeedProfileResult(C.Structure):
+    """pp_speed_profile_result: status 0 profiled, 1 no sample in the window, -1 no plan, -4 path beyond the path capacity, -5 more than max_samples
+    samples; the number of samples and cusp stops, the plan's length, the first and last arc length, the arrival time at the last sample, the highest
+    speed, and the smallest clearance with the arc length where it is taken (+inf and 0 without a clearance term)"""
+    _fields_ = [("status", C.c_int32), ("n_samples", C.c_int32), ("n_cusps", C.c_int32), ("reserved", C.c_int32), ("length", C.c_double), ("s_first", C.c_double),
+                ("s_last", C.c_double), ("duration", C.c_double), ("v_peak", C.c_double), ("min_clearance", C.c_double), ("s_min_clearance", C.c_double)]
+
+
 class LocateResult(C.Structure):
     """pp_locate_result: status 0 located, 1 no sample in the window, -1 no plan, -4 path beyond the path capacity; the located point's edge
     (1 .. n_path - 1; 0 for a one-pose plan), travel direction (+1 / -1), arc length s, ratio on the edge and path pose; the vehicle's distance,
@@ -240,6 +255,8 @@ def load():
     L.pp_planner_stamp.argtypes = [vp, vp, C.c_int32, vp, vp, vp, C.POINTER(StampParams), vp]
     L.pp_pipeline_locate.argtypes = [vp, C.c_int32, vp, vp, vp, vp, C.POINTER(LocateParams), vp]
     L.pp_planner_locate.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(LocateParams), vp]
+    L.pp_pipeline_speed_profile.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(SpeedProfileParams), C.c_int32, vp, vp]
+    L.pp_planner_speed_profile.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, C.POINTER(SpeedProfileParams), C.c_int32, vp, vp]
     L.pp_pipeline_timings.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.pp_pipeline_backlog.argtypes = [vp, vp, vp]
     L.pp_pipeline_planner.argtypes = [vp]

@@ -162,6 +162,34 @@ def build_locate_rule_test(verbose=True):
     return out
 
 
+def build_pipeline_speed_profile_test(verbose=True):
+    """tests/cpp/test_pipeline_speed_profile.cpp: SpeedProfile(tickets) of HybridAStarPipeline against a sequential sweep over the plan's path objects (run on the GPU box)."""
+    build()
+    out = os.path.join(LIB_DIR, "test_pipeline_speed_profile")
+    src = os.path.join(HERE, "..", "tests", "cpp", "test_pipeline_speed_profile.cpp")
+    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", src, "-o", out, "-L" + LIB_DIR, "-lpphip", "-Wl,-rpath,$ORIGIN"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return out
+
+
+def build_speed_rule_test(verbose=True):
+    """tests/cpp/test_speed_rule.cpp: the cap, the envelopes, the step time and the cusp predicate of a speed profile (csrc/pp_speed_rule.hpp) alone, on
+    the CPU, under the address and undefined-behaviour sanitizers; without contraction, as the library is built."""
+    os.makedirs(LIB_DIR, exist_ok=True)
+    out = os.path.join(LIB_DIR, "test_speed_rule")
+    src = os.path.join(HERE, "..", "tests", "cpp", "test_speed_rule.cpp")
+    headers = [os.path.join(CSRC, "pp_speed_rule.hpp"), os.path.join(CSRC, "pp_stamp_rule.hpp")]
+    if os.path.exists(out) and os.path.getmtime(out) > max(os.path.getmtime(f) for f in [src] + headers):
+        return out
+    cmd = ["g++", "-std=c++17", "-g", "-O1", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC, src, "-o", out]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return out
+
+
 def build_ticket_table_test(verbose=True):
     """tests/cpp/test_ticket_table.cpp: the pipeline's slot and ticket bookkeeping (csrc/pp_ticket_table.hpp) alone, on the CPU, under the address and
     undefined-behaviour sanitizers."""
@@ -202,5 +230,7 @@ if __name__ == "__main__":
     print(build_stamp_rule_test())
     print(build_pipeline_locate_test())
     print(build_locate_rule_test())
+    print(build_pipeline_speed_profile_test())
+    print(build_speed_rule_test())
     print(build_ticket_table_test())
     print(build_row_test())

@@ -2,8 +2,8 @@
 // names their argument types) and in front of pp_planner and pp_pipeline, which both keep one buffer group per service.
 //
 // Finished plans (path records, Reeds-Shepp log, result record) are held by a batch planner, as queries 0 .. n-1 of its last batch, or by a pipeline, as
-// the slots of held tickets.  A service over them -- post-processing, re-validation, the stamp, the locate call -- has one core (post_process_plans,
-// revalidate_plans, stamp_plans, locate_plans in pp_planner.hip) that takes a HeldPlans and goes through held_grow and held_run; its two extern "C"
+// the slots of held tickets.  A service over them -- post-processing, re-validation, the stamp, the locate call, the speed profile -- has one core (post_process_plans,
+// revalidate_plans, stamp_plans, locate_plans, speed_profile_plans in pp_planner.hip) that takes a HeldPlans and goes through held_grow and held_run; its two extern "C"
 // entries check what is the holder's own and describe the holder (batch_plans, pipe_plans).
 #pragma once
 
@@ -69,6 +69,13 @@ struct PostGroup {
 			e = hipMemcpyAsync(smoothedHost + to * 3, smoothed + from * 3, count * 24, hipMemcpyDeviceToHost, s);
 		return e;
 	}
+};
+
+/// The speed profile's buffers: the records, and one row of max_samples (s, v, t) triples per plan, which the kernel also works in
+struct SpeedGroup {
+	HeldBuffers<SpeedArg, pp_speed_profile_result> rec;
+	pph::Dev<double> rows;
+	size_t samples = 0; // samples `rows` holds (24 bytes each)
 };
 
 /// Buffers that hold `capacity` units are made to hold `wanted` ({buffer, bytes}; 0 bytes: the holder does not use it).  A holder that may not free now

@@ -207,6 +207,7 @@ struct pp_pipeline {
 	HeldBuffers<NoPlanArg, pp_revalidate_result> reval;
 	HeldBuffers<StampArg, pp_stamp_result> stamp;
 	HeldBuffers<LocateArg, pp_locate_result> locate;
+	SpeedGroup speed;
 	std::vector<pph::DeviceMem> heldParked; // their buffers outgrown while queries were in flight: hipFree waits for the whole device (the persistent grid
 	                                        // included), so they are kept until a call finds nothing in flight (or the pipeline goes): held_grow
 	int nWf = 2;      // wavefront streams in use: consecutive submissions' launches overlap (the tail of one under the head of the next)
@@ -604,7 +605,7 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 			return PP_ERR_INVALID;
 		}
 	}
-	// an empty dispatch of the kernels pp_pipeline_postprocess, pp_pipeline_revalidate, pp_pipeline_stamp and pp_pipeline_locate launch, on the stream they use
+	// an empty dispatch of the kernels pp_pipeline_postprocess, pp_pipeline_revalidate, pp_pipeline_stamp, pp_pipeline_locate and pp_pipeline_speed_profile launch, on the stream they use
 	const char* service = "";
 	e = warm_up_held_kernels(pl, P->ctlStream, true, &service);
 	if (e != hipSuccess) {
@@ -1174,6 +1175,22 @@ int pp_pipeline_locate(pp_pipeline* P, int32_t n, const uint64_t* tickets, const
 	if (int rc = pipe_resolve(P, n, tickets, "located", true, h.slots))
 		return rc;
 	return locate_plans(h, P->locate, plans, params, results_host);
+}
+
+/// Speeds and arrival times along the plans of n completed, held queries (include/pp_hip.h; speed_profile_plans): legal beside queries in flight
+int pp_pipeline_speed_profile(pp_pipeline* P, pp_map* target, int32_t n, const uint64_t* tickets, const double* from_length, const double* to_length, const double* v_start,
+	const double* v_end, const pp_speed_profile_params* params, int32_t max_samples, double* samples_host, pp_speed_profile_result* results_host)
+{
+	HeldPlans h;
+	if (int rc = pipe_plans(P, n, tickets, h))
+		return rc;
+	pp_map* const map = target ? target : P->pl->map;
+	std::vector<SpeedArg> plans;
+	if (int rc = speed_check(h, map, from_length, to_length, v_start, v_end, params, max_samples, plans))
+		return rc;
+	if (int rc = pipe_resolve(P, n, tickets, "profiled", true, h.slots))
+		return rc;
+	return speed_profile_plans(h, P->speed, map, plans, params, max_samples, samples_host, results_host);
 }
 
 /// Launch durations seen so far (HIP events on the launching streams; harvested by pp_pipeline_poll) and reset.  Wavefront: one launch per

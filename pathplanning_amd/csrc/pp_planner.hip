@@ -19,6 +19,7 @@
 #include "pp_row_primitives.hpp"
 #include "pp_stamp_rule.hpp"
 #include "pp_locate_rule.hpp"
+#include "pp_speed_rule.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -305,6 +306,8 @@ struct PipeView {
 #include "pp_stamp.hpp"
 // vehicles located on their held plans (one wave per plan; the same PostEdge / load_edge and the stamp's sample schedule)
 #include "pp_locate.hpp"
+// speed profiles and arrival times along held plans (one wave per plan; the same PostEdge / load_edge and the stamp's sample schedule)
+#include "pp_speed_profile.hpp"
 
 } // namespace
 
@@ -369,6 +372,7 @@ struct pp_planner {
 	HeldBuffers<NoPlanArg, pp_revalidate_result> reval;
 	HeldBuffers<StampArg, pp_stamp_result> stamp;
 	HeldBuffers<LocateArg, pp_locate_result> locate;
+	SpeedGroup speed;
 };
 
 namespace {
@@ -451,6 +455,18 @@ hipError_t launch_locate(hipStream_t s, const SearchArgs& args, const pp_locate_
 	return hipGetLastError();
 }
 
+/// k_speed_profile_tickets over `count` plans of buffer set p (count = 0 on a grid of one: the warm-up, which dereferences nothing)
+hipError_t launch_speed_profile(hipStream_t s, const SearchArgs& args, const Footprint& foot, const pp_speed_profile_params* params, int maxSamples, int count,
+	const int32_t* slotsDev, const SpeedArg* argsDev, pp_planner* p, double* rowsDev, pp_speed_profile_result* outDev)
+{
+	ppv::Limits limits {};
+	if (params)
+		limits = ppv::Limits { params->v_max_forward, params->v_max_reverse, params->a_acc, params->a_dec, params->a_lat, params->dwell, params->clearance_gain, params->v_floor };
+	hipLaunchKernelGGL(k_speed_profile_tickets, dim3(count > 0 ? count : 1), dim3(kSpeedLanes), speed_lds_bytes(args.maxPath), s, args, foot, limits, params ? params->spacing : 1.0,
+		maxSamples, count, slotsDev, argsDev, p->paths.get(), p->rsLogs.get(), p->results.get(), rowsDev, outDev);
+	return hipGetLastError();
+}
+
 /// An empty dispatch of each kernel that works on held plans (post-processing in the holder's form), on stream s, which is drained behind each: the queue
 /// allocates their scratch here, where a failure is an error code (see warm_up_kernels).  *service names the service whose kernel failed.
 hipError_t warm_up_held_kernels(pp_planner* p, hipStream_t s, bool byTicket, const char** service)
@@ -472,7 +488,8 @@ hipError_t warm_up_held_kernels(pp_planner* p, hipStream_t s, bool byTicket, con
 	hipLaunchKernelGGL(k_revalidate_tickets, dim3(1), dim3(64), 0, s, p->args, Footprint {}, 0, (const int32_t*)nullptr, (const PathRec*)nullptr, (const RsLogEntry*)nullptr,
 		(const DevResult*)nullptr, (pp_revalidate_result*)nullptr);
 	if (ok("re-validation", hipGetLastError()) && ok("stamp", launch_stamp(s, p->args, Footprint {}, nullptr, 0, nullptr, nullptr, p, nullptr, nullptr)))
-		(void)ok("locate", launch_locate(s, p->args, nullptr, 0, nullptr, nullptr, p, nullptr));
+		if (ok("locate", launch_locate(s, p->args, nullptr, 0, nullptr, nullptr, p, nullptr)))
+			(void)ok("speed profile", launch_speed_profile(s, p->args, Footprint {}, nullptr, 1, 0, nullptr, nullptr, p, nullptr, nullptr));
 	return e;
 }
 
@@ -666,6 +683,63 @@ int locate_check(const HeldPlans& h, const double* poses, const double* from_len
 	return PP_OK;
 }
 
+/// The arguments of a speed-profile call that do not depend on who holds the plans (pp_planner_speed_profile, pp_pipeline_speed_profile): the target's
+/// context and -- with a clearance term -- its distance grid, the parameters, the sample limit, and the per-plan windows and end speeds, which go into
+/// `plans` (h.name(i) names plan i in a refusal)
+int speed_check(const HeldPlans& h, const pp_map* target, const double* from_length, const double* to_length, const double* v_start, const double* v_end,
+	const pp_speed_profile_params* params, int max_samples, std::vector<SpeedArg>& plans)
+{
+	const int n = h.n;
+	if (target->ctx != h.pl->map->ctx) {
+		set_error("the target map belongs to another context than the planner's map");
+		return PP_ERR_INVALID;
+	}
+	if (n > 0 && !params) {
+		set_error("invalid arguments (null params: a pp_speed_profile_params is needed)");
+		return PP_ERR_INVALID;
+	}
+	if (params) {
+		const std::pair<const char*, double> positive[] = { { "spacing", params->spacing }, { "v_max_forward", params->v_max_forward }, { "v_max_reverse", params->v_max_reverse },
+			{ "a_acc", params->a_acc }, { "a_dec", params->a_dec }, { "a_lat", params->a_lat } };
+		for (const auto& [name, value] : positive)
+			if (!std::isfinite(value) || !(value > 0.0)) {
+				set_error(std::string("invalid arguments (the speed profile's ") + name + " is finite and > 0)");
+				return PP_ERR_INVALID;
+			}
+		const std::pair<const char*, double> nonNegative[] = { { "dwell", params->dwell }, { "clearance_gain", params->clearance_gain }, { "v_floor", params->v_floor } };
+		for (const auto& [name, value] : nonNegative)
+			if (!std::isfinite(value) || !(value >= 0.0)) {
+				set_error(std::string("invalid arguments (the speed profile's ") + name + " is finite and >= 0)");
+				return PP_ERR_INVALID;
+			}
+		if (params->clearance_gain > 0.0 && !target->dist) {
+			set_error("the target map has no distance grid, which a clearance_gain > 0 reads: pp_map_upload_dist2, pp_map_upload_distance or pp_map_update_gvd first");
+			return PP_ERR_INVALID;
+		}
+	}
+	if (max_samples < 1) {
+		set_error("invalid arguments (max_samples >= 1, got " + std::to_string(max_samples) + ")");
+		return PP_ERR_INVALID;
+	}
+	plans.resize((size_t)n);
+	for (int i = 0; i < n; i++) {
+		SpeedArg& a = plans[(size_t)i];
+		a.from = from_length ? from_length[i] : -HUGE_VAL;
+		a.to = to_length ? to_length[i] : HUGE_VAL;
+		a.vStart = v_start ? v_start[i] : 0.0;
+		a.vEnd = v_end ? v_end[i] : 0.0;
+		if (a.from != a.from || a.to != a.to) {
+			set_error(h.name(i) + " has a NaN in its window");
+			return PP_ERR_INVALID;
+		}
+		if (!std::isfinite(a.vStart) || !(a.vStart >= 0.0) || !std::isfinite(a.vEnd) || !(a.vEnd >= 0.0)) {
+			set_error(h.name(i) + " has a v_start or v_end that is not finite and >= 0");
+			return PP_ERR_INVALID;
+		}
+	}
+	return PP_OK;
+}
+
 // ---- the services over held plans, one core each (pp_held_plans.hpp); both holders' extern "C" entries end here
 
 /// the plans of a batch planner's last batch: queries 0 .. n-1
@@ -775,6 +849,44 @@ int locate_plans(const HeldPlans& h, HeldBuffers<LocateArg, pp_locate_result>& b
 	const SearchArgs args = held_args(h, h.ownView);
 	return held_run(h, b, plans, results_host,
 		[&](const int32_t* slotsDev) { return launch_locate(h.stream, args, params, h.n, slotsDev, b.args.get(), pl, b.out.get()); });
+}
+
+/// Speeds and arrival times along the plans of h (`plans`: speed_check's).  With a clearance term the launch travels with the target's view of this moment and
+/// the holder's footprint, or the point validator of the TARGET seen as one disc; without one it reads no map and travels with the holder's own view.  The
+/// sample rows come back behind the kernel on the holder's stream, in the synchronisation held_run makes for the records, and the first n_samples rows of
+/// every profiled plan go on to the caller's array.
+int speed_profile_plans(const HeldPlans& h, SpeedGroup& g, pp_map* target, const std::vector<SpeedArg>& plans, const pp_speed_profile_params* params, int max_samples,
+	double* samples_host, pp_speed_profile_result* results_host)
+{
+	if (h.n == 0)
+		return PP_OK;
+	pp_planner* const pl = h.pl;
+	PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
+	PP_HIP_TRY(held_grow(h, g.samples, h.rows * (size_t)max_samples, { { &g.rows, h.rows * (size_t)max_samples * 24 } }));
+	const bool clearance = params->clearance_gain > 0.0;
+	const SearchArgs args = held_args(h, clearance ? target->view() : h.ownView);
+	Footprint discs {};
+	if (clearance) {
+		discs = h.foot();
+		if (!h.footprint) {
+			discs.n = 1;
+			discs.r[0] = target->minSafeRadius;
+		}
+	}
+	const size_t stride = (size_t)max_samples * 3;
+	std::vector<double> staged(samples_host ? (size_t)h.n * stride : 0);
+	std::vector<pp_speed_profile_result> recs;
+	if (int rc = held_run(h, g.rec, plans, results_host, [&](const int32_t* slotsDev) {
+			if (const hipError_t e = launch_speed_profile(h.stream, args, discs, params, max_samples, h.n, slotsDev, g.rec.args.get(), pl, g.rows.get(), g.rec.out.get()))
+				return e;
+			return samples_host ? hipMemcpyAsync(staged.data(), g.rows.get(), staged.size() * 8, hipMemcpyDeviceToHost, h.stream) : hipSuccess;
+		}, &recs))
+		return rc;
+	if (samples_host)
+		for (size_t i = 0; i < (size_t)h.n; i++)
+			if (recs[i].status == 0)
+				std::copy(staged.begin() + i * stride, staged.begin() + i * stride + (size_t)recs[i].n_samples * 3, samples_host + i * stride);
+	return PP_OK;
 }
 
 void free_planner(pp_planner* p)
@@ -1595,6 +1707,19 @@ int pp_planner_stamp(pp_planner* planner, pp_map* target, int32_t n_queries, con
 	if (int rc = stamp_check(h, map, values, from_length, to_length, params, plans))
 		return rc;
 	return stamp_plans(h, planner->stamp, map, plans, params, results_host);
+}
+
+int pp_planner_speed_profile(pp_planner* planner, pp_map* target, int32_t n_queries, const double* from_length, const double* to_length, const double* v_start,
+	const double* v_end, const pp_speed_profile_params* params, int32_t max_samples, double* samples_host, pp_speed_profile_result* results_host)
+{
+	if (int rc = batch_check(planner, n_queries, "pp_pipeline_speed_profile profiles its held tickets"))
+		return rc;
+	pp_map* const map = target ? target : planner->map;
+	const HeldPlans h = batch_plans(planner, n_queries);
+	std::vector<SpeedArg> plans;
+	if (int rc = speed_check(h, map, from_length, to_length, v_start, v_end, params, max_samples, plans))
+		return rc;
+	return speed_profile_plans(h, planner->speed, map, plans, params, max_samples, samples_host, results_host);
 }
 
 int pp_planner_locate(pp_planner* planner, int32_t n_queries, const double* poses_host, const double* from_length, const double* to_length, const pp_locate_params* params,

@@ -139,6 +139,8 @@ struct PostEdge {
 	rs::Path rsp;
 	__device__ __forceinline__ Pose interpolate(double ratio) const { return kind == 1 ? arc.interpolate(ratio) : rsp.interpolate(ratio); }
 	__device__ __forceinline__ int direction(double ratio) const { return kind == 1 ? (arc.backward ? rs::kBwd : rs::kFwd) : rsp.direction(ratio); }
+	/// |curvature| at `ratio`: the arc's, or 1 / rmin on a turning motion of the Reeds-Shepp path and 0 on a straight one (the motion direction(ratio) selects)
+	__device__ __forceinline__ double curvature(double ratio) const { return kind == 1 ? fabs(arc.kappa) : (rsp.steer(ratio) == rs::kStraight ? 0.0 : 1.0 / rsp.rmin); }
 	__device__ __forceinline__ double length() const { return kind == 1 ? arc.length : rsp.length; }
 };
 

@@ -485,17 +485,29 @@ namespace rs {
 		/// PathReedsShepp::GetDirection, paths/path_reeds_shepp.cpp:155-167
 		PPD_INLINE int direction(double ratio) const
 		{
+			const int i = motion_at(ratio);
+			return i < 0 ? kNoMotion : seg.dir[i];
+		}
+		/// the steering of the motion whose direction direction(ratio) returns (kStraight where that is kNoMotion)
+		PPD_INLINE int steer(double ratio) const
+		{
+			const int i = motion_at(ratio);
+			return i < 0 ? kStraight : seg.steer[i];
+		}
+		/// GetDirection's selection: the first motion whose end lies at or behind ratio * length; -1: none (a zero-length path, or a ratio behind the last end)
+		PPD_INLINE int motion_at(double ratio) const
+		{
 			if (length == 0)
-				return kNoMotion;
+				return -1;
 			double len = 0;
 			for (int i = 0; i < kNumMotion; i++) {
 				if (!motion_valid(seg, i))
 					break;
 				len += seg.len[i] * rmin;
 				if (ratio * length <= len)
-					return seg.dir[i];
+					return i;
 			}
-			return kNoMotion;
+			return -1;
 		}
 		/// PathReedsShepp::GetCuspPointRatios, paths/path_reeds_shepp.cpp:95-121: the std::set as a sorted array without
 		/// duplicates (at most 4 entries); returns the count

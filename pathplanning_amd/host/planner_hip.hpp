@@ -1020,6 +1020,7 @@ struct RRTStarParameters {
 /// Revalidate(tickets) asks whether held plans are still collision-free after the map changed (pp_pipeline_revalidate).
 /// Stamp(tickets, into, spacing) writes the cells held plans sweep into a map's occupancy grid (pp_pipeline_stamp): the reservation map of the next vehicle.
 /// Locate(tickets, poses, spacing) finds each vehicle on its held plan (pp_pipeline_locate): the arc length that windows Stamp, the errors a controller steers on.
+/// SpeedProfile(tickets, spacing, limits) gives the speed and the arrival time at every sample of a held plan (pp_pipeline_speed_profile): what a controller tracks at s.
 class HybridAStarPipeline {
 public:
 	struct Result {
@@ -1310,6 +1311,82 @@ public:
 			out[i].headingError = r[i].heading_error;
 			out[i].length = r[i].length;
 			out[i].pose = Pose2d(r[i].pose[0], r[i].pose[1], r[i].pose[2]);
+		}
+		return out;
+	}
+	/// The limits of a speed profile (pp_speed_profile_params without the spacing)
+	struct SpeedLimits {
+		double vMaxForward = 5.0, vMaxReverse = 2.0; // m/s
+		double aAcc = 1.5, aDec = 2.5, aLat = 2.0;   // m/s^2: speeding up, braking, v^2 * curvature
+		double dwell = 0.0;                          // s of standstill at every change of travel direction
+		double clearanceGain = 0.0, vFloor = 0.0;    // v <= vFloor + clearanceGain * clearance; gain 0: no clearance term, no map read
+	};
+	/// What SpeedProfile says about one held plan (pp_speed_profile_result) and its samples
+	struct SpeedProfiled {
+		enum class Status { Profiled = 0, NoSampleInWindow = 1, NoPlan = -1, PathTooLong = -4, TooManySamples = -5 };
+		Status status = Status::NoPlan;
+		int numSamples = 0, numCusps = 0;
+		double length = 0.0;                // length of the composite path
+		double sFirst = 0.0, sLast = 0.0;   // arc length of the first and the last sample
+		double duration = 0.0;              // arrival time at the last sample
+		double vPeak = 0.0;
+		double minClearance = 0.0, sMinClearance = 0.0; // +inf and 0 without a clearance term
+		std::vector<double> s, v, t;        // per sample: arc length, speed, arrival time (empty unless Profiled)
+	};
+	/// Speeds and arrival times along the graph-search plans of held queries (pp_pipeline_speed_profile; include/pp_hip.h has the definition): at every
+	/// sample of Stamp's schedule (`spacing`) inside [fromLength[i], toLength[i]] the speed under `limits`, with a stop at every change of travel
+	/// direction, vStart[i] at the first and vEnd[i] at the last sample, and the time of arrival.  `on`: the validator whose map the clearance term reads --
+	/// nullptr: the pipeline's own; read only when limits.clearanceGain > 0.  fromLength / toLength / vStart / vEnd: empty, or one entry per ticket (empty:
+	/// -inf / +inf / 0 / 0).  A plan with more than maxSamples samples in its window is TooManySamples.  Legal beside queries in flight.
+	std::vector<SpeedProfiled> SpeedProfile(const std::vector<uint64_t>& tickets, double spacing) { return SpeedProfile(tickets, spacing, SpeedLimits()); }
+	std::vector<SpeedProfiled> SpeedProfile(const std::vector<uint64_t>& tickets, double spacing, const SpeedLimits& limits, int maxSamples = 2048,
+		const std::vector<double>& fromLength = {}, const std::vector<double>& toLength = {}, const std::vector<double>& vStart = {}, const std::vector<double>& vEnd = {},
+		const Ref<StateValidatorOccupancyMap>& on = nullptr)
+	{
+		for (uint64_t t : tickets)
+			HeldOf(t); // (throws for a ticket that is not held)
+		const size_t n = tickets.size();
+		for (const std::vector<double>* a : { &fromLength, &toLength, &vStart, &vEnd })
+			if (!a->empty() && a->size() != n)
+				throw std::invalid_argument("SpeedProfile: fromLength, toLength, vStart and vEnd are empty or hold one entry per ticket");
+		std::vector<SpeedProfiled> out(n);
+		if (!m_pipe || n == 0)
+			return out;
+		pp_map* target = nullptr;
+		if (limits.clearanceGain > 0.0) {
+			const Ref<StateValidatorOccupancyMap>& v = on ? on : m_validator;
+			if (v->GetOccupancyMap()->FieldsOutdated())
+				v->GetOccupancyMap()->BuildFields(20.0f, 30.0f);
+			target = v->Device(); // pushes host-side grids and the validator's tunables
+			if (InFlight() == 0)
+				SyncFootprint();
+		}
+		const pp_speed_profile_params sp { spacing, limits.vMaxForward, limits.vMaxReverse, limits.aAcc, limits.aDec, limits.aLat, limits.dwell, limits.clearanceGain, limits.vFloor };
+		auto orNull = [](const std::vector<double>& a) { return a.empty() ? nullptr : a.data(); };
+		std::vector<pp_speed_profile_result> r(n);
+		std::vector<double> rows(maxSamples > 0 ? n * (size_t)maxSamples * 3 : 0);
+		ppCheck(pp_pipeline_speed_profile(m_pipe, target, (int32_t)n, tickets.data(), orNull(fromLength), orNull(toLength), orNull(vStart), orNull(vEnd), &sp, maxSamples, rows.data(),
+			r.data()));
+		for (size_t i = 0; i < n; i++) {
+			SpeedProfiled& o = out[i];
+			o.status = (SpeedProfiled::Status)r[i].status;
+			o.numSamples = r[i].n_samples;
+			o.numCusps = r[i].n_cusps;
+			o.length = r[i].length;
+			o.sFirst = r[i].s_first;
+			o.sLast = r[i].s_last;
+			o.duration = r[i].duration;
+			o.vPeak = r[i].v_peak;
+			o.minClearance = r[i].min_clearance;
+			o.sMinClearance = r[i].s_min_clearance;
+			if (r[i].status != 0)
+				continue;
+			const double* row = rows.data() + i * (size_t)maxSamples * 3;
+			for (int j = 0; j < r[i].n_samples; j++) {
+				o.s.push_back(row[3 * j]);
+				o.v.push_back(row[3 * j + 1]);
+				o.t.push_back(row[3 * j + 2]);
+			}
 		}
 		return out;
 	}

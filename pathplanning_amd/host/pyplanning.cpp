@@ -436,6 +436,31 @@ PYBIND11_MODULE(pyplanning, m)
 			},
 			py::arg("tickets"), py::arg("poses"), py::arg("spacing") = 0.1, py::arg("heading_weight") = 0.0, py::arg("from_length") = std::vector<double>(),
 			py::arg("to_length") = std::vector<double>())
+		// speeds and arrival times along held plans: ((status, n_samples, n_cusps, length, s_first, s_last, duration, v_peak, min_clearance, s_min_clearance), s, v, t) per
+		// ticket; validator=None: the pipeline's own validator's map, read only when clearance_gain > 0
+		.def("speed_profile",
+			[](HybridAStarPipeline& h, const std::vector<uint64_t>& tickets, double spacing, double vMaxForward, double vMaxReverse, double aAcc, double aDec, double aLat, double dwell,
+				double clearanceGain, double vFloor, int maxSamples, const std::vector<double>& fromLength, const std::vector<double>& toLength, const std::vector<double>& vStart,
+				const std::vector<double>& vEnd, const Ref<StateValidatorOccupancyMap>& validator) {
+				HybridAStarPipeline::SpeedLimits limits;
+				limits.vMaxForward = vMaxForward;
+				limits.vMaxReverse = vMaxReverse;
+				limits.aAcc = aAcc;
+				limits.aDec = aDec;
+				limits.aLat = aLat;
+				limits.dwell = dwell;
+				limits.clearanceGain = clearanceGain;
+				limits.vFloor = vFloor;
+				py::list out;
+				for (const auto& r : h.SpeedProfile(tickets, spacing, limits, maxSamples, fromLength, toLength, vStart, vEnd, validator))
+					out.append(py::make_tuple(py::make_tuple((int)r.status, r.numSamples, r.numCusps, r.length, r.sFirst, r.sLast, r.duration, r.vPeak, r.minClearance, r.sMinClearance), r.s,
+						r.v, r.t));
+				return out;
+			},
+			py::arg("tickets"), py::arg("spacing") = 0.1, py::arg("v_max_forward") = 5.0, py::arg("v_max_reverse") = 2.0, py::arg("a_acc") = 1.5, py::arg("a_dec") = 2.5,
+			py::arg("a_lat") = 2.0, py::arg("dwell") = 0.0, py::arg("clearance_gain") = 0.0, py::arg("v_floor") = 0.0, py::arg("max_samples") = 2048,
+			py::arg("from_length") = std::vector<double>(), py::arg("to_length") = std::vector<double>(), py::arg("v_start") = std::vector<double>(),
+			py::arg("v_end") = std::vector<double>(), py::arg("validator") = Ref<StateValidatorOccupancyMap>())
 		.def("get_path", &HybridAStarPipeline::GetPath, py::arg("ticket"))
 		.def("get_graph_search_path", &HybridAStarPipeline::GetGraphSearchPath, py::arg("ticket"))
 		.def("get_smoothing_status", &HybridAStarPipeline::GetSmoothingStatus, py::arg("ticket"))

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (RS_PATH_DTYPE, FootprintDisc, HybridParams, LocateParams, LocateResult, MapDesc, PostResult, QueryResult, RevalidateResult, SmootherParams,
-                   StampParams, StampResult, check, ptr)
+                   SpeedProfileParams, SpeedProfileResult, StampParams, StampResult, check, ptr)
 
 
 class Status:
@@ -700,6 +700,14 @@ class HybridAStarBatch:
         return _locate(n, poses, from_length, to_length, spacing, heading_weight,
                        lambda v, a, b, lp, out: self.lib.pp_planner_locate(self.h, n, ptr(v), ptr(a), ptr(b), C.byref(lp), out))
 
+    def speed_profile(self, n_queries=None, map_set=None, from_length=None, to_length=None, v_start=None, v_end=None, max_samples=2048, samples=True, **limits):
+        """Speeds and arrival times along the plans of the first n queries of the last batch: pp_planner_speed_profile, the batch form of
+        HybridAStarPipeline.speed_profile, with the same arguments and return value."""
+        n = len(self._results) if n_queries is None else int(n_queries)
+        return _speed_profile(n, from_length, to_length, v_start, v_end, max_samples, samples, limits,
+                              lambda a, b, vs, ve, sp, rows, out: self.lib.pp_planner_speed_profile(self.h, map_set.h if map_set is not None else None, n, ptr(a), ptr(b), ptr(vs),
+                                                                                                    ptr(ve), C.byref(sp), int(max_samples), ptr(rows), out))
+
     def certify_lattice(self, q):
         """SURVEY 7.3 H2 as a contract (pp_planner_certify_lattice): created nodes and logged lattice-line children of query q recomputed on
         the host with glibc; returns (checked, cell mismatches, unverified events, largest pose difference).  mismatches == unverified == 0
@@ -1027,6 +1035,24 @@ class HybridAStarPipeline:
         return _locate(len(t), poses, from_length, to_length, spacing, heading_weight,
                        lambda v, a, b, lp, out: self.lib.pp_pipeline_locate(self.h, len(t), ptr(t), ptr(v), ptr(a), ptr(b), C.byref(lp), out))
 
+    def speed_profile(self, tickets, map_set=None, from_length=None, to_length=None, v_start=None, v_end=None, max_samples=2048, samples=True, **limits):
+        """How fast may the vehicle of the completed, HELD query tickets[k] drive along its plan, and when is it where?  pp_pipeline_speed_profile, whose
+        definition is in include/pp_hip.h: at every sample of the stamp's schedule (`spacing`) inside [from_length[k], to_length[k]] metres from the start
+        (None: the whole plan) the speed under v_max_forward / v_max_reverse, the lateral limit v^2 kappa <= a_lat, the acceleration limits a_acc / a_dec, a
+        stop (plus `dwell` seconds) at every change of travel direction, v_start[k] at the first and v_end[k] at the last sample (None: 0) and, with
+        clearance_gain > 0, v <= v_floor + clearance_gain * clearance on map_set (None: the pipeline's own map); and the arrival time.  `limits` are the
+        fields of SpeedProfileParams (defaults: spacing 0.1, v_max_forward 5, v_max_reverse 2, a_acc 1.5, a_dec 2.5, a_lat 2, dwell 0, clearance_gain 0,
+        v_floor 0).  Nothing but the call's own buffers is written: legal while other queries are in flight.
+        Returns the SpeedProfileResult records and, with samples=True, a list of (n_samples, 3) arrays of (s, v, t), empty for a plan whose status is
+        not 0 (status -5: more than max_samples samples).  r.s of a locate result is what from_length takes.
+        Raises PPError, with nothing launched, for a ticket that is unknown, released, in flight or given twice, a limit outside its domain,
+        max_samples < 1, a NaN in a window, a v_start / v_end that is not finite and >= 0, a foreign map, or a map without a distance grid when
+        clearance_gain > 0."""
+        t = np.ascontiguousarray(tickets, dtype=np.uint64).reshape(-1)
+        return _speed_profile(len(t), from_length, to_length, v_start, v_end, max_samples, samples, limits,
+                              lambda a, b, vs, ve, sp, rows, out: self.lib.pp_pipeline_speed_profile(self.h, map_set.h if map_set is not None else None, len(t), ptr(t), ptr(a),
+                                                                                                     ptr(b), ptr(vs), ptr(ve), C.byref(sp), int(max_samples), ptr(rows), out))
+
     def get_expanded_of(self, ticket):
         """expansion sequence (log_expansions=True) of a completed query polled with release=False"""
         slot = self.lib.pp_pipeline_slot_of(self.h, C.c_uint64(int(ticket)))
@@ -1091,6 +1117,24 @@ def _stamp(n, values, from_length, to_length, spacing, margin, call):
     out = (StampResult * max(n, 1))()
     check(call(_per_plan(values, n, np.int32), _per_plan(from_length, n), _per_plan(to_length, n), StampParams(float(spacing), float(margin), 0), out))
     return list(out)[:n]
+
+
+SPEED_PROFILE_DEFAULTS = dict(spacing=0.1, v_max_forward=5.0, v_max_reverse=2.0, a_acc=1.5, a_dec=2.5, a_lat=2.0, dwell=0.0, clearance_gain=0.0, v_floor=0.0)
+
+
+def _speed_profile(n, from_length, to_length, v_start, v_end, max_samples, samples, limits, call):
+    """the parameters and per-plan arrays of a speed-profile call, the call, its records and (if wanted) each plan's (s, v, t) rows"""
+    unknown = set(limits) - set(SPEED_PROFILE_DEFAULTS)
+    if unknown:
+        raise TypeError("unknown speed-profile limits: %s" % sorted(unknown))
+    sp = SpeedProfileParams(**{k: float(v) for k, v in dict(SPEED_PROFILE_DEFAULTS, **limits).items()})
+    out = (SpeedProfileResult * max(n, 1))()
+    rows = np.zeros((n, max(int(max_samples), 0), 3)) if samples else None
+    check(call(_per_plan(from_length, n), _per_plan(to_length, n), _per_plan(v_start, n), _per_plan(v_end, n), sp, rows, out))
+    recs = list(out)[:n]
+    if not samples:
+        return recs
+    return recs, [rows[i, :r.n_samples].copy() if r.status == 0 else np.zeros((0, 3)) for i, r in enumerate(recs)]
 
 
 def _locate(n, poses, from_length, to_length, spacing, heading_weight, call):
