@@ -738,6 +738,84 @@ int pp_pipeline_speed_profile(pp_pipeline* pipeline, pp_map* target /* NULL: the
 int pp_planner_speed_profile(pp_planner* planner, pp_map* target /* NULL: own map */, int32_t n_queries, const double* from_length, const double* to_length,
 	const double* v_start, const double* v_end, const pp_speed_profile_params* params, int32_t max_samples, double* samples_host,
 	pp_speed_profile_result* results_host);
+/* ---- space-time conflicts between held plans, by ticket -----------------------------------------------------------------------------------------
+ * Do vehicle A and vehicle B, each driving its held plan on the timetable of its speed profile, ever come too close AT THE SAME TIME, and where and
+ * when first?  (A stamp reserves space for all time: two vehicles that cross one junction a minute apart block each other there.)  The call takes n
+ * plans, a start time for each and a list of pairs; it forms every plan's TRAJECTORY -- its pose at every time of a common lattice -- once
+ * (k_trajectory_tickets, one wave per plan) and then the disc separation of every pair over the lattice (k_conflict_pairs, one wave per pair).  No
+ * plan data leaves the device.  It reads no map and writes nothing but its own buffers, so the call is legal beside queries in flight.  All
+ * arithmetic below is in double, in the order written (the library is built without contraction), unless a float is named.
+ *  Profile. A holder remembers its most recent speed-profile call that returned PP_OK: per plan of that call the row, the status and n_samples, and
+ *           once its max_samples, a_acc and a_dec; the rows stay where the kernel left them.  A pipeline keys this by ticket, a batch planner by query
+ *           index.  A later speed-profile call replaces all of it (one with n == 0 leaves nothing), releasing a ticket drops that ticket's entry, a new
+ *           batch on a batch planner drops everything.  The rows of plan i are (s_j, v_j, t_j), j = 0 .. N - 1, t_0 = 0.
+ *  Lattice. k0 = (int64) ceil(t_from / dt), k1 = (int64) floor(t_to / dt), both clipped to +-2^62 in double before the conversion; T = k1 - k0 + 1;
+ *           tau_m = (double)(k0 + m) * dt for m = 0 .. T - 1.  The lattice is global, not anchored at t_from: two calls with overlapping horizons
+ *           look at the same times.
+ *  Position. u = tau - t_start[i].  u < 0: absent if hold_before == 0, else at s_0.  u > t_{N-1}: absent if hold_after == 0, else at s_{N-1}.
+ *           Otherwise j is the largest index with t_j <= u (binary search; behind equal times the last one).  j == N - 1: s = s_j.  Else, with
+ *           ds = s_{j+1} - s_j and delta = u - t_j: ds == 0 gives s = s_j (a junction or a dwell is a standstill).  Else let m be the motion time of
+ *           the step, the speed profile's dt_j (without the dwell).  delta >= m gives s = s_{j+1}: the vehicle dwells at the cusp stop.  Else, if
+ *           v_j + v_{j+1} > 0: a = (v_{j+1} - v_j) / m and s = s_j + (v_j + (0.5 * a) * delta) * delta.  Else the triangle: x = ds * a_dec / (a_acc +
+ *           a_dec), ta = sqrt(2 x / a_acc); delta <= ta gives s = s_j + (0.5 * a_acc) * delta * delta; otherwise r = m - delta and
+ *           s = s_{j+1} - (0.5 * a_dec) * r * r.  Last, s is clamped into [s_j, s_{j+1}].
+ *  Pose.    e is the largest edge with S_e <= s, ratio = L_e > 0 ? (s - S_e) / L_e : 0, capped at 1 (the locate call's lattice mapping), and the
+ *           pose is the path object's interpolation at the ratio.  A one-pose plan gives its pose.  S_e is the sequential root-first sum:
+ *           pp_revalidate_result::length's bits.
+ *  Separation. The discs are the stamp's: the holder's footprint, else the disc (0, 0, min_safe_radius of the holder's OWN map); their centres are
+ *           "vehicle footprint"'s expression on the pose.  The separation of a pair at tau is the minimum over disc a of A and disc b of B of
+ *           sqrt(dx dx + dy dy) - ((double)r_a + (double)r_b), (dx, dy) the difference of the centres, A's minus B's.  CONFLICT iff separation < margin.
+ *           min_separation is the minimum under the order (separation, tau); the first conflict is the smallest tau in conflict.  Only min and integer
+ *           counts are formed across lanes, so no result depends on the order of evaluation.
+ *  Between lattice times. A reference point moves at most v_peak * dt between two lattice times, and a disc centre at most v_peak * dt * (1 +
+ *           kappa_max * rho), rho the footprint's largest centre offset.  A margin of at least the sum of that bound over the pair's two vehicles
+ *           therefore makes "no conflict" hold between the lattice times too.  The library picks neither dt nor margin for the caller.
+ *  - pairs (may be NULL) is [n_pairs][2] indices into tickets.  NULL: every pair i < j in row-major order, n_pairs == n (n - 1) / 2; the device
+ *    derives the pair from its index and no list is uploaded.
+ *  - poses_host (may be NULL) is [n][T][3] doubles (x, y, theta), a NaN in all three where the vehicle is absent; it comes down only when asked for.
+ *    plans_host (may be NULL) belongs to tickets[i], results_host (may be NULL) to pairs[p].
+ *  - PP_ERR_INVALID, nothing launched, the holder usable as before, the message naming the first offending ticket or argument: n < 0 or
+ *    n > capacity; a ticket that is unknown, released, still in flight or given twice; a ticket without a remembered profile ("run speed_profile
+ *    first"); NULL t_start or params with n > 0; a t_start that is not finite; t_from, t_to not finite or t_from > t_to; dt not finite and > 0;
+ *    margin not finite and >= 0; T < 1 or T > 2^20; a hold flag other than 0 / 1; n_pairs < 0; a pair index outside 0 .. n - 1; a pair (i, i);
+ *    pairs == NULL with n_pairs != n (n - 1) / 2.  n == 0 is PP_OK.
+ *  - The holder owns the slot list, the per-plan arguments and records (4 + 16 + 32 bytes per plan), the trajectory (48 bytes per plan and lattice
+ *    time of the largest n x T so far), the pair list and the pair records (8 + 80 bytes per pair), kept aside like the post-processing buffers when
+ *    they have to grow beside queries in flight. */
+typedef struct pp_conflict_params {
+	double  t_from, t_to;  /* finite, t_from <= t_to: the horizon in absolute seconds */
+	double  dt;            /* finite, > 0: the time lattice tau_k = (double)k * dt */
+	double  margin;        /* finite, >= 0: conflict iff separation < margin */
+	int32_t hold_before;   /* 0: a vehicle is absent before its start; 1: it stands at its first sample */
+	int32_t hold_after;    /* 0: absent after its last sample's time; 1: it stands at its last sample */
+} pp_conflict_params;      /* 40 bytes */
+typedef struct pp_trajectory_result {
+	int32_t status;        /* 0; 1 never present on the lattice; -1 the ticket's profile has status != 0 */
+	int32_t n_present;
+	int32_t first, last;   /* indices 0 .. T-1 of the first / last lattice time it is present; -1, -1 if none */
+	double  s_enter, s_leave; /* its arc length at those two times */
+} pp_trajectory_result;    /* 32 bytes; for status != 0 n_present, s_enter and s_leave are zero */
+typedef struct pp_conflict_result {
+	int32_t status;        /* 0 no conflict; 1 conflict; 2 never both present; -1 a plan of the pair has status -1 */
+	int32_t n_times;       /* lattice times at which both are present */
+	int32_t n_conflict;    /* of them, in conflict */
+	int32_t reserved;
+	double  t_first;       /* the first lattice time in conflict */
+	double  s_first[2];    /* arc lengths of the pair's two plans there */
+	double  min_separation;/* over the n_times times; +inf when n_times == 0 */
+	double  t_min;         /* the smallest lattice time at which it is taken */
+	double  s_min[2];
+	double  reserved1;     /* zero: the record is 80 bytes */
+} pp_conflict_result;      /* 80 bytes; for status 2 and -1 every field but status is zero, except min_separation = +inf for status 2; for status 0
+                              t_first and s_first are zero */
+int pp_pipeline_conflicts(pp_pipeline* pipeline, int32_t n, const uint64_t* tickets, const double* t_start /* [n], finite */, int32_t n_pairs,
+	const int32_t* pairs /* may be NULL */, const pp_conflict_params* params, double* poses_host /* may be NULL */,
+	pp_trajectory_result* plans_host /* may be NULL */, pp_conflict_result* results_host /* may be NULL */);
+/* The same kernels over the first n_queries queries of the planner's last batch (identity slots; the profiles of the planner's last
+ * pp_planner_speed_profile call), on the planner's stream, with the planner's footprint if it has one.  PP_ERR_INVALID as above, and for a planner that
+ * is a pipeline's buffer set (pp_pipeline_conflicts knows which slots are held). */
+int pp_planner_conflicts(pp_planner* planner, int32_t n_queries, const double* t_start, int32_t n_pairs, const int32_t* pairs,
+	const pp_conflict_params* params, double* poses_host, pp_trajectory_result* plans_host, pp_conflict_result* results_host);
 /* Diagnostics: waves of the search grid that are alive right now (a blocking device-to-host copy; -1 on error). */
 int pp_pipeline_alive_waves(pp_pipeline* pipeline);
 pp_planner* pp_pipeline_planner(pp_pipeline* pipeline);           /* the buffer set: set_nonholo_table, set_primitives, get_path(slot), ... */

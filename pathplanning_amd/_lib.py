@@ -119,6 +119,26 @@ class SpeedProfileResult(C.Structure):
                 ("s_last", C.c_double), ("duration", C.c_double), ("v_peak", C.c_double), ("min_clearance", C.c_double), ("s_min_clearance", C.c_double)]
 
 
+class ConflictParams(C.Structure):
+    """pp_conflict_params: the horizon [t_from, t_to] in absolute seconds, the step dt of the global time lattice k * dt (> 0), the margin (>= 0,
+    metres: conflict iff separation < margin) and whether a vehicle stands at its first / last sample before its start / behind its end (0 / 1)"""
+    _fields_ = [("t_from", C.c_double), ("t_to", C.c_double), ("dt", C.c_double), ("margin", C.c_double), ("hold_before", C.c_int32), ("hold_after", C.c_int32)]
+
+
+class TrajectoryResult(C.Structure):
+    """pp_trajectory_result: status 0, 1 never present on the lattice, -1 the plan's speed profile has a status other than 0; the number of lattice
+    times it is present at, the indices of the first and last of them (-1, -1: none) and its arc length at those two"""
+    _fields_ = [("status", C.c_int32), ("n_present", C.c_int32), ("first", C.c_int32), ("last", C.c_int32), ("s_enter", C.c_double), ("s_leave", C.c_double)]
+
+
+class ConflictResult(C.Structure):
+    """pp_conflict_result: status 0 no conflict, 1 conflict, 2 never both present, -1 a plan of the pair has status -1; the lattice times both are
+    present at and those in conflict; the first time in conflict with the two arc lengths there; the smallest separation (+inf: never both present),
+    the smallest time it is taken at and the two arc lengths there"""
+    _fields_ = [("status", C.c_int32), ("n_times", C.c_int32), ("n_conflict", C.c_int32), ("reserved", C.c_int32), ("t_first", C.c_double),
+                ("s_first", C.c_double * 2), ("min_separation", C.c_double), ("t_min", C.c_double), ("s_min", C.c_double * 2), ("reserved1", C.c_double)]
+
+
 class LocateResult(C.Structure):
     """pp_locate_result: status 0 located, 1 no sample in the window, -1 no plan, -4 path beyond the path capacity; the located point's edge
     (1 .. n_path - 1; 0 for a one-pose plan), travel direction (+1 / -1), arc length s, ratio on the edge and path pose; the vehicle's distance,
@@ -257,6 +277,8 @@ def load():
     L.pp_planner_locate.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(LocateParams), vp]
     L.pp_pipeline_speed_profile.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(SpeedProfileParams), C.c_int32, vp, vp]
     L.pp_planner_speed_profile.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, C.POINTER(SpeedProfileParams), C.c_int32, vp, vp]
+    L.pp_pipeline_conflicts.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, C.POINTER(ConflictParams), vp, vp, vp]
+    L.pp_planner_conflicts.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.POINTER(ConflictParams), vp, vp, vp]
     L.pp_pipeline_timings.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.pp_pipeline_backlog.argtypes = [vp, vp, vp]
     L.pp_pipeline_planner.argtypes = [vp]

@@ -190,6 +190,35 @@ def build_speed_rule_test(verbose=True):
     return out
 
 
+def build_pipeline_conflicts_test(verbose=True):
+    """tests/cpp/test_pipeline_conflicts.cpp: Conflicts(tickets, starts) of HybridAStarPipeline against a plain sequential loop over the profile rows and the plan's
+    path objects (run on the GPU box)."""
+    build()
+    out = os.path.join(LIB_DIR, "test_pipeline_conflicts")
+    src = os.path.join(HERE, "..", "tests", "cpp", "test_pipeline_conflicts.cpp")
+    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", src, "-o", out, "-L" + LIB_DIR, "-lpphip", "-Wl,-rpath,$ORIGIN"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return out
+
+
+def build_conflict_rule_test(verbose=True):
+    """tests/cpp/test_conflict_rule.cpp: the lattice, the row search, the position within a step, the separation and the two orders of a conflict call
+    (csrc/pp_conflict_rule.hpp) alone, on the CPU, under the address and undefined-behaviour sanitizers; without contraction, as the library is built."""
+    os.makedirs(LIB_DIR, exist_ok=True)
+    out = os.path.join(LIB_DIR, "test_conflict_rule")
+    src = os.path.join(HERE, "..", "tests", "cpp", "test_conflict_rule.cpp")
+    headers = [os.path.join(CSRC, "pp_conflict_rule.hpp"), os.path.join(CSRC, "pp_speed_rule.hpp"), os.path.join(CSRC, "pp_stamp_rule.hpp")]
+    if os.path.exists(out) and os.path.getmtime(out) > max(os.path.getmtime(f) for f in [src] + headers):
+        return out
+    cmd = ["g++", "-std=c++17", "-g", "-O1", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC, src, "-o", out]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return out
+
+
 def build_ticket_table_test(verbose=True):
     """tests/cpp/test_ticket_table.cpp: the pipeline's slot and ticket bookkeeping (csrc/pp_ticket_table.hpp) alone, on the CPU, under the address and
     undefined-behaviour sanitizers."""
@@ -232,5 +261,7 @@ if __name__ == "__main__":
     print(build_locate_rule_test())
     print(build_pipeline_speed_profile_test())
     print(build_speed_rule_test())
+    print(build_pipeline_conflicts_test())
+    print(build_conflict_rule_test())
     print(build_ticket_table_test())
     print(build_row_test())

@@ -2,8 +2,8 @@
 // names their argument types) and in front of pp_planner and pp_pipeline, which both keep one buffer group per service.
 //
 // Finished plans (path records, Reeds-Shepp log, result record) are held by a batch planner, as queries 0 .. n-1 of its last batch, or by a pipeline, as
-// the slots of held tickets.  A service over them -- post-processing, re-validation, the stamp, the locate call, the speed profile -- has one core (post_process_plans,
-// revalidate_plans, stamp_plans, locate_plans, speed_profile_plans in pp_planner.hip) that takes a HeldPlans and goes through held_grow and held_run; its two extern "C"
+// the slots of held tickets.  A service over them -- post-processing, re-validation, the stamp, the locate call, the speed profile, the conflict call -- has one core (post_process_plans,
+// revalidate_plans, stamp_plans, locate_plans, speed_profile_plans, conflict_plans in pp_planner.hip) that takes a HeldPlans and goes through held_grow and held_run; its two extern "C"
 // entries check what is the holder's own and describe the holder (batch_plans, pipe_plans).
 #pragma once
 
@@ -76,6 +76,27 @@ struct SpeedGroup {
 	HeldBuffers<SpeedArg, pp_speed_profile_result> rec;
 	pph::Dev<double> rows;
 	size_t samples = 0; // samples `rows` holds (24 bytes each)
+	/// What the holder remembers of its most recent speed-profile call that returned PP_OK, for the services that read `rows` where the kernel left
+	/// them (the conflict call): per plan its row and what the record said, once the call's stride and acceleration limits.  A batch planner keys the
+	/// plans by query index, a pipeline by ticket, as PostGroup::indexOfTicket does; a later call replaces all of it, a released ticket loses its entry.
+	struct Profile {
+		int32_t row, status, nSamples;
+	};
+	std::unordered_map<uint64_t, Profile> profileOf;
+	int maxSamples = 0;
+	double aAcc = 0.0, aDec = 0.0;
+};
+
+/// The conflict call's buffers: per plan the slot list, the start time and profile row, and the trajectory record; the trajectory itself, one array per
+/// component and plan-major (pp_conflicts.hpp); the pair list (absent when the call pairs every i < j) and the pair records
+struct ConflictGroup {
+	HeldBuffers<ConflictArg, pp_trajectory_result> rec;
+	pph::Dev<double> traj;
+	size_t doubles = 0; // doubles `traj` holds
+	pph::Dev<int32_t> pairs;
+	size_t listed = 0; // pairs `pairs` holds (8 bytes each)
+	pph::Dev<pp_conflict_result> out;
+	size_t pairRows = 0; // pair records `out` holds
 };
 
 /// Buffers that hold `capacity` units are made to hold `wanted` ({buffer, bytes}; 0 bytes: the holder does not use it).  A holder that may not free now

@@ -208,6 +208,7 @@ struct pp_pipeline {
 	HeldBuffers<StampArg, pp_stamp_result> stamp;
 	HeldBuffers<LocateArg, pp_locate_result> locate;
 	SpeedGroup speed;
+	ConflictGroup conflict;
 	std::vector<pph::DeviceMem> heldParked; // their buffers outgrown while queries were in flight: hipFree waits for the whole device (the persistent grid
 	                                        // included), so they are kept until a call finds nothing in flight (or the pipeline goes): held_grow
 	int nWf = 2;      // wavefront streams in use: consecutive submissions' launches overlap (the tail of one under the head of the next)
@@ -405,6 +406,7 @@ int pipe_refuse(const pp_pipeline* P, uint64_t ticket, const char* verb)
 bool pipe_release(pp_pipeline* P, uint64_t ticket)
 {
 	P->post.indexOfTicket.erase(ticket);
+	P->speed.profileOf.erase(ticket);
 	return P->tickets.release(ticket);
 }
 
@@ -605,7 +607,7 @@ int pp_pipeline_create(pp_map* map, const pp_hybrid_params* params, int32_t capa
 			return PP_ERR_INVALID;
 		}
 	}
-	// an empty dispatch of the kernels pp_pipeline_postprocess, pp_pipeline_revalidate, pp_pipeline_stamp, pp_pipeline_locate and pp_pipeline_speed_profile launch, on the stream they use
+	// an empty dispatch of the kernels pp_pipeline_postprocess, pp_pipeline_revalidate, pp_pipeline_stamp, pp_pipeline_locate, pp_pipeline_speed_profile and pp_pipeline_conflicts launch, on the stream they use
 	const char* service = "";
 	e = warm_up_held_kernels(pl, P->ctlStream, true, &service);
 	if (e != hipSuccess) {
@@ -1191,6 +1193,25 @@ int pp_pipeline_speed_profile(pp_pipeline* P, pp_map* target, int32_t n, const u
 	if (int rc = pipe_resolve(P, n, tickets, "profiled", true, h.slots))
 		return rc;
 	return speed_profile_plans(h, P->speed, map, plans, params, max_samples, samples_host, results_host);
+}
+
+/// Trajectories of n completed, held queries on the timetables of their speed profiles, and the separation of pairs of them (include/pp_hip.h;
+/// conflict_plans): legal beside queries in flight
+int pp_pipeline_conflicts(pp_pipeline* P, int32_t n, const uint64_t* tickets, const double* t_start, int32_t n_pairs, const int32_t* pairs, const pp_conflict_params* params,
+	double* poses_host, pp_trajectory_result* plans_host, pp_conflict_result* results_host)
+{
+	HeldPlans h;
+	if (int rc = pipe_plans(P, n, tickets, h))
+		return rc;
+	ConflictLattice lattice;
+	if (int rc = conflict_check(h, t_start, n_pairs, pairs, params, lattice))
+		return rc;
+	if (int rc = pipe_resolve(P, n, tickets, "looked at for conflicts", true, h.slots))
+		return rc;
+	std::vector<ConflictArg> plans;
+	if (int rc = conflict_profiles(h, P->speed, t_start, lattice, plans))
+		return rc;
+	return conflict_plans(h, P->conflict, P->speed, plans, lattice, n_pairs, pairs, poses_host, plans_host, results_host);
 }
 
 /// Launch durations seen so far (HIP events on the launching streams; harvested by pp_pipeline_poll) and reset.  Wavefront: one launch per

@@ -20,6 +20,7 @@
 #include "pp_stamp_rule.hpp"
 #include "pp_locate_rule.hpp"
 #include "pp_speed_rule.hpp"
+#include "pp_conflict_rule.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -308,6 +309,8 @@ struct PipeView {
 #include "pp_locate.hpp"
 // speed profiles and arrival times along held plans (one wave per plan; the same PostEdge / load_edge and the stamp's sample schedule)
 #include "pp_speed_profile.hpp"
+// space-time conflicts between held plans on the timetables of their speed profiles (one wave per plan, then one per pair; the same PostEdge / load_edge)
+#include "pp_conflicts.hpp"
 
 } // namespace
 
@@ -373,6 +376,7 @@ struct pp_planner {
 	HeldBuffers<StampArg, pp_stamp_result> stamp;
 	HeldBuffers<LocateArg, pp_locate_result> locate;
 	SpeedGroup speed;
+	ConflictGroup conflict;
 };
 
 namespace {
@@ -467,6 +471,23 @@ hipError_t launch_speed_profile(hipStream_t s, const SearchArgs& args, const Foo
 	return hipGetLastError();
 }
 
+/// k_trajectory_tickets over `count` plans of buffer set p (count = 0 on a grid of one: the warm-up, which dereferences nothing)
+hipError_t launch_trajectory(hipStream_t s, const SearchArgs& args, const ConflictLattice& lattice, bool withHeading, int count, const int32_t* slotsDev,
+	const ConflictArg* argsDev, pp_planner* p, const double* rowsDev, double* trajDev, pp_trajectory_result* outDev)
+{
+	hipLaunchKernelGGL(k_trajectory_tickets, dim3(count > 0 ? count : 1), dim3(kConflictLanes), trajectory_lds_bytes(args.maxPath), s, args, lattice, withHeading ? 1 : 0, count,
+		slotsDev, argsDev, p->paths.get(), p->rsLogs.get(), p->results.get(), rowsDev, trajDev, outDev);
+	return hipGetLastError();
+}
+
+/// k_conflict_pairs over `count` pairs of `plans` trajectories (count = 0 on a grid of one: the warm-up, which dereferences nothing)
+hipError_t launch_conflict_pairs(hipStream_t s, const Footprint& discs, const ConflictLattice& lattice, int plans, long long count, const int32_t* pairsDev,
+	const double* trajDev, const pp_trajectory_result* plansDev, pp_conflict_result* outDev)
+{
+	hipLaunchKernelGGL(k_conflict_pairs, dim3((unsigned)(count > 0 ? count : 1)), dim3(kConflictLanes), 0, s, discs, lattice, plans, count, pairsDev, trajDev, plansDev, outDev);
+	return hipGetLastError();
+}
+
 /// An empty dispatch of each kernel that works on held plans (post-processing in the holder's form), on stream s, which is drained behind each: the queue
 /// allocates their scratch here, where a failure is an error code (see warm_up_kernels).  *service names the service whose kernel failed.
 hipError_t warm_up_held_kernels(pp_planner* p, hipStream_t s, bool byTicket, const char** service)
@@ -489,7 +510,9 @@ hipError_t warm_up_held_kernels(pp_planner* p, hipStream_t s, bool byTicket, con
 		(const DevResult*)nullptr, (pp_revalidate_result*)nullptr);
 	if (ok("re-validation", hipGetLastError()) && ok("stamp", launch_stamp(s, p->args, Footprint {}, nullptr, 0, nullptr, nullptr, p, nullptr, nullptr)))
 		if (ok("locate", launch_locate(s, p->args, nullptr, 0, nullptr, nullptr, p, nullptr)))
-			(void)ok("speed profile", launch_speed_profile(s, p->args, Footprint {}, nullptr, 1, 0, nullptr, nullptr, p, nullptr, nullptr));
+			if (ok("speed profile", launch_speed_profile(s, p->args, Footprint {}, nullptr, 1, 0, nullptr, nullptr, p, nullptr, nullptr)))
+				if (ok("conflict trajectories", launch_trajectory(s, p->args, ConflictLattice {}, false, 0, nullptr, nullptr, p, nullptr, nullptr, nullptr)))
+					(void)ok("conflict pairs", launch_conflict_pairs(s, Footprint {}, ConflictLattice {}, 0, 0, nullptr, nullptr, nullptr, nullptr));
 	return e;
 }
 
@@ -740,6 +763,101 @@ int speed_check(const HeldPlans& h, const pp_map* target, const double* from_len
 	return PP_OK;
 }
 
+/// The arguments of a conflict call that do not depend on who holds the plans (pp_planner_conflicts, pp_pipeline_conflicts): the parameters and the
+/// lattice they span, the start times and the pair list (h.name(i) names plan i in a refusal)
+int conflict_check(const HeldPlans& h, const double* t_start, int n_pairs, const int32_t* pairs, const pp_conflict_params* params, ConflictLattice& lattice)
+{
+	const int n = h.n;
+	if (n > 0 && !t_start) {
+		set_error("invalid arguments (null t_start: one start time per plan is needed)");
+		return PP_ERR_INVALID;
+	}
+	if (n > 0 && !params) {
+		set_error("invalid arguments (null params: a pp_conflict_params is needed)");
+		return PP_ERR_INVALID;
+	}
+	lattice = ConflictLattice {};
+	if (params) {
+		if (!std::isfinite(params->t_from) || !std::isfinite(params->t_to) || !(params->t_from <= params->t_to)) {
+			set_error("invalid arguments (the conflict call's t_from and t_to are finite and t_from <= t_to)");
+			return PP_ERR_INVALID;
+		}
+		if (!std::isfinite(params->dt) || !(params->dt > 0.0)) {
+			set_error("invalid arguments (the conflict call's dt is finite and > 0 seconds)");
+			return PP_ERR_INVALID;
+		}
+		if (!std::isfinite(params->margin) || !(params->margin >= 0.0)) {
+			set_error("invalid arguments (the conflict call's margin is finite and >= 0 metres)");
+			return PP_ERR_INVALID;
+		}
+		const int64_t k0 = ppc::lattice_begin(params->t_from, params->dt), T = ppc::lattice_count(k0, ppc::lattice_end(params->t_to, params->dt));
+		if (T < 1 || T > ppc::kMaxTimes) {
+			set_error("invalid arguments (the horizon holds " + (T < 1 ? std::string("no") : "more than " + std::to_string(ppc::kMaxTimes)) +
+				" lattice times k * dt: 1 <= T <= " + std::to_string(ppc::kMaxTimes) + ")");
+			return PP_ERR_INVALID;
+		}
+		if ((params->hold_before != 0 && params->hold_before != 1) || (params->hold_after != 0 && params->hold_after != 1)) {
+			set_error("invalid arguments (the conflict call's hold_before and hold_after are 0 or 1)");
+			return PP_ERR_INVALID;
+		}
+		lattice.k0 = k0;
+		lattice.T = (int)T;
+		lattice.holdBefore = params->hold_before;
+		lattice.holdAfter = params->hold_after;
+		lattice.dt = params->dt;
+		lattice.margin = params->margin;
+	}
+	for (int i = 0; i < n; i++)
+		if (!std::isfinite(t_start[i])) {
+			set_error(h.name(i) + " has a t_start that is not finite");
+			return PP_ERR_INVALID;
+		}
+	if (n_pairs < 0) {
+		set_error("invalid arguments (n_pairs >= 0, got " + std::to_string(n_pairs) + ")");
+		return PP_ERR_INVALID;
+	}
+	if (!pairs) {
+		const int64_t all = (int64_t)n * (n - 1) / 2;
+		if (n_pairs != all) {
+			set_error("invalid arguments (null pairs means every pair i < j: n_pairs == n (n - 1) / 2 = " + std::to_string(all) + ", got " + std::to_string(n_pairs) + ")");
+			return PP_ERR_INVALID;
+		}
+		return PP_OK;
+	}
+	for (int p = 0; p < n_pairs; p++) {
+		const int32_t a = pairs[2 * (size_t)p], b = pairs[2 * (size_t)p + 1];
+		if (a < 0 || a >= n || b < 0 || b >= n) {
+			set_error("pair " + std::to_string(p) + " = (" + std::to_string(a) + ", " + std::to_string(b) + ") has an index outside 0 .. n - 1 = " + std::to_string(n - 1));
+			return PP_ERR_INVALID;
+		}
+		if (a == b) {
+			set_error("pair " + std::to_string(p) + " = (" + std::to_string(a) + ", " + std::to_string(b) + ") pairs a plan with itself");
+			return PP_ERR_INVALID;
+		}
+	}
+	return PP_OK;
+}
+
+/// ... and what the holder remembers of its last speed-profile call for the plans of h: their rows, into `plans`, and the call's stride and limits, into `lattice`
+int conflict_profiles(const HeldPlans& h, const SpeedGroup& g, const double* t_start, ConflictLattice& lattice, std::vector<ConflictArg>& plans)
+{
+	plans.resize((size_t)h.n);
+	for (int i = 0; i < h.n; i++) {
+		const auto it = g.profileOf.find(h.byTicket ? h.tickets[i] : (uint64_t)i);
+		if (it == g.profileOf.end()) {
+			set_error(h.name(i) + " has no speed profile: run speed_profile first (it was not in the holder's last speed-profile call, or has been released since)");
+			return PP_ERR_INVALID;
+		}
+		const SpeedGroup::Profile& f = it->second;
+		const bool profiled = f.status == 0 && f.nSamples >= 1;
+		plans[(size_t)i] = ConflictArg { t_start[i], profiled ? f.row : 0, profiled ? f.nSamples : 0 };
+	}
+	lattice.maxSamples = g.maxSamples;
+	lattice.aAcc = g.aAcc;
+	lattice.aDec = g.aDec;
+	return PP_OK;
+}
+
 // ---- the services over held plans, one core each (pp_held_plans.hpp); both holders' extern "C" entries end here
 
 /// the plans of a batch planner's last batch: queries 0 .. n-1
@@ -858,6 +976,7 @@ int locate_plans(const HeldPlans& h, HeldBuffers<LocateArg, pp_locate_result>& b
 int speed_profile_plans(const HeldPlans& h, SpeedGroup& g, pp_map* target, const std::vector<SpeedArg>& plans, const pp_speed_profile_params* params, int max_samples,
 	double* samples_host, pp_speed_profile_result* results_host)
 {
+	g.profileOf.clear(); // (what the holder remembers of its last call ends here, whatever happens below: the rows are about to be rewritten)
 	if (h.n == 0)
 		return PP_OK;
 	pp_planner* const pl = h.pl;
@@ -886,6 +1005,53 @@ int speed_profile_plans(const HeldPlans& h, SpeedGroup& g, pp_map* target, const
 		for (size_t i = 0; i < (size_t)h.n; i++)
 			if (recs[i].status == 0)
 				std::copy(staged.begin() + i * stride, staged.begin() + i * stride + (size_t)recs[i].n_samples * 3, samples_host + i * stride);
+	for (int i = 0; i < h.n; i++)
+		g.profileOf[h.byTicket ? h.tickets[i] : (uint64_t)i] = SpeedGroup::Profile { i, recs[(size_t)i].status, recs[(size_t)i].n_samples };
+	g.maxSamples = max_samples;
+	g.aAcc = params->a_acc;
+	g.aDec = params->a_dec;
+	return PP_OK;
+}
+
+/// Trajectories of the plans of h on the lattice and the separation of `n_pairs` pairs of them (`plans`, `lattice`: conflict_check's and conflict_profiles').  Both
+/// kernels, the pair list before them and every copy behind them run on the holder's stream, which held_run synchronises once.  The trajectory comes down only for a
+/// caller that wants poses, and is interleaved here.
+int conflict_plans(const HeldPlans& h, ConflictGroup& g, const SpeedGroup& speed, const std::vector<ConflictArg>& plans, const ConflictLattice& lattice, int n_pairs,
+	const int32_t* pairs, double* poses_host, pp_trajectory_result* plans_host, pp_conflict_result* results_host)
+{
+	if (h.n == 0)
+		return PP_OK;
+	pp_planner* const pl = h.pl;
+	PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
+	const size_t n = (size_t)h.n, T = (size_t)lattice.T, nPairs = (size_t)n_pairs, component = n * T;
+	PP_HIP_TRY(held_grow(h, g.doubles, component * kTrajectoryComponents, { { &g.traj, component * kTrajectoryComponents * 8 } }));
+	if (pairs)
+		PP_HIP_TRY(held_grow(h, g.listed, nPairs, { { &g.pairs, nPairs * 8 } }));
+	PP_HIP_TRY(held_grow(h, g.pairRows, nPairs, { { &g.out, nPairs * sizeof(pp_conflict_result) } }));
+	const SearchArgs args = held_args(h, h.ownView);
+	const Footprint discs = stamp_discs(h.footprint, pl->map);
+	std::vector<double> staged(poses_host ? component * 3 : 0);
+	std::vector<pp_conflict_result> recs(results_host ? nPairs : 0);
+	if (int rc = held_run(h, g.rec, plans, plans_host, [&](const int32_t* slotsDev) {
+			hipError_t e = hipSuccess;
+			if (pairs && nPairs)
+				e = hipMemcpyAsync(g.pairs, pairs, nPairs * 8, hipMemcpyHostToDevice, h.stream);
+			if (e == hipSuccess)
+				e = launch_trajectory(h.stream, args, lattice, discs.anyOffset != 0, h.n, slotsDev, g.rec.args.get(), pl, speed.rows.get(), g.traj.get(), g.rec.out.get());
+			if (e == hipSuccess && nPairs)
+				e = launch_conflict_pairs(h.stream, discs, lattice, h.n, (long long)nPairs, pairs ? g.pairs.get() : nullptr, g.traj.get(), g.rec.out.get(), g.out.get());
+			if (e == hipSuccess && !recs.empty())
+				e = hipMemcpyAsync(recs.data(), g.out, nPairs * sizeof(pp_conflict_result), hipMemcpyDeviceToHost, h.stream);
+			if (e == hipSuccess && !staged.empty())
+				e = hipMemcpyAsync(staged.data(), g.traj, staged.size() * 8, hipMemcpyDeviceToHost, h.stream);
+			return e;
+		}))
+		return rc;
+	std::copy(recs.begin(), recs.end(), results_host);
+	if (poses_host)
+		for (size_t i = 0; i < component; i++) // (plan-major in both: plan i, time m is i * T + m)
+			for (size_t c = 0; c < 3; c++)
+				poses_host[i * 3 + c] = staged[c * component + i];
 	return PP_OK;
 }
 
@@ -1324,6 +1490,7 @@ int pp_planner_search_batch_dev(pp_planner* planner, int32_t n_queries, const do
 	}
 	if (n_queries == 0)
 		return PP_OK;
+	planner->speed.profileOf.clear(); // the speed profiles the planner remembers are the last batch's plans'
 	PP_HIP_TRY(hipSetDevice(planner->map->ctx->device));
 	if (!planner->tableReady)
 		if (int rc = pp_planner_set_nonholo_table(planner, nullptr))
@@ -1720,6 +1887,21 @@ int pp_planner_speed_profile(pp_planner* planner, pp_map* target, int32_t n_quer
 	if (int rc = speed_check(h, map, from_length, to_length, v_start, v_end, params, max_samples, plans))
 		return rc;
 	return speed_profile_plans(h, planner->speed, map, plans, params, max_samples, samples_host, results_host);
+}
+
+int pp_planner_conflicts(pp_planner* planner, int32_t n_queries, const double* t_start, int32_t n_pairs, const int32_t* pairs, const pp_conflict_params* params,
+	double* poses_host, pp_trajectory_result* plans_host, pp_conflict_result* results_host)
+{
+	if (int rc = batch_check(planner, n_queries, "pp_pipeline_conflicts looks at its held tickets"))
+		return rc;
+	const HeldPlans h = batch_plans(planner, n_queries);
+	ConflictLattice lattice;
+	if (int rc = conflict_check(h, t_start, n_pairs, pairs, params, lattice))
+		return rc;
+	std::vector<ConflictArg> plans;
+	if (int rc = conflict_profiles(h, planner->speed, t_start, lattice, plans))
+		return rc;
+	return conflict_plans(h, planner->conflict, planner->speed, plans, lattice, n_pairs, pairs, poses_host, plans_host, results_host);
 }
 
 int pp_planner_locate(pp_planner* planner, int32_t n_queries, const double* poses_host, const double* from_length, const double* to_length, const pp_locate_params* params,

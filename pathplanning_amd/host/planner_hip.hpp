@@ -1390,6 +1390,99 @@ public:
 		}
 		return out;
 	}
+	/// The horizon, the time lattice k * dt, the margin and the hold flags of a Conflicts call (pp_conflict_params)
+	struct ConflictHorizon {
+		double tFrom = 0.0, tTo = 60.0; // absolute seconds
+		double dt = 0.1;                // the lattice step
+		double margin = 0.0;            // conflict iff separation < margin, metres
+		bool holdBefore = false, holdAfter = false; // a vehicle stands at its first / last sample before its start / behind its end instead of being absent
+	};
+	/// What Conflicts says about one held plan on the lattice (pp_trajectory_result) and, if asked, its pose at every lattice time (NaN where absent)
+	struct Trajectory {
+		enum class Status { Present = 0, NeverPresent = 1, NoProfile = -1 };
+		Status status = Status::NoProfile;
+		int numPresent = 0, first = -1, last = -1;
+		double sEnter = 0.0, sLeave = 0.0;
+		std::vector<Pose2d> poses;
+	};
+	/// ... and about one pair of them (pp_conflict_result)
+	struct Conflict {
+		enum class Status { Free = 0, Conflict = 1, NeverBothPresent = 2, NoProfile = -1 };
+		Status status = Status::NoProfile;
+		int numTimes = 0, numConflict = 0;
+		double tFirst = 0.0, sFirst[2] = { 0.0, 0.0 };
+		double minSeparation = 0.0, tMin = 0.0, sMin[2] = { 0.0, 0.0 };
+	};
+	struct Conflicted {
+		std::vector<Trajectory> plans;
+		std::vector<Conflict> pairs;
+	};
+	/// Space-time conflicts between held queries that drive their plans on the timetables of the LAST SpeedProfile call, ticket i from tStart[i] on
+	/// (pp_pipeline_conflicts; include/pp_hip.h has the definition): every plan's pose at the lattice times inside the horizon, and for every pair of
+	/// `pairs` (indices into tickets; allPairs: every i < j, row-major) the separation of the vehicles' discs at the times both are present.  Legal beside
+	/// queries in flight; no plan data leaves the device unless withPoses asks for the poses.
+	Conflicted Conflicts(const std::vector<uint64_t>& tickets, const std::vector<double>& tStart) { return Conflicts(tickets, tStart, {}, true, ConflictHorizon(), false); }
+	Conflicted Conflicts(const std::vector<uint64_t>& tickets, const std::vector<double>& tStart, const ConflictHorizon& horizon, bool withPoses = false)
+	{
+		return Conflicts(tickets, tStart, {}, true, horizon, withPoses);
+	}
+	Conflicted Conflicts(const std::vector<uint64_t>& tickets, const std::vector<double>& tStart, const std::vector<std::pair<int, int>>& pairs, bool allPairs,
+		const ConflictHorizon& horizon, bool withPoses = false)
+	{
+		for (uint64_t t : tickets)
+			HeldOf(t); // (throws for a ticket that is not held)
+		const size_t n = tickets.size();
+		if (tStart.size() != n)
+			throw std::invalid_argument("Conflicts: tStart holds one entry per ticket");
+		Conflicted out;
+		if (!m_pipe || n == 0)
+			return out;
+		const pp_conflict_params cp { horizon.tFrom, horizon.tTo, horizon.dt, horizon.margin, horizon.holdBefore ? 1 : 0, horizon.holdAfter ? 1 : 0 };
+		std::vector<int32_t> list;
+		for (const auto& p : pairs) {
+			list.push_back(p.first);
+			list.push_back(p.second);
+		}
+		const size_t nPairs = allPairs ? n * (n - 1) / 2 : pairs.size();
+		size_t T = 0;
+		if (withPoses && horizon.dt > 0.0) { // (the library's lattice; a horizon it refuses gets no pose array)
+			const double k0 = std::ceil(horizon.tFrom / horizon.dt), k1 = std::floor(horizon.tTo / horizon.dt);
+			if (k1 >= k0 && k1 - k0 < 1048576.0)
+				T = (size_t)(k1 - k0) + 1;
+		}
+		std::vector<double> xyt(n * T * 3);
+		std::vector<pp_trajectory_result> r(n);
+		std::vector<pp_conflict_result> c(nPairs);
+		ppCheck(pp_pipeline_conflicts(m_pipe, (int32_t)n, tickets.data(), tStart.data(), (int32_t)nPairs, allPairs ? nullptr : list.data(), &cp, T ? xyt.data() : nullptr, r.data(),
+			c.data()));
+		out.plans.resize(n);
+		for (size_t i = 0; i < n; i++) {
+			Trajectory& o = out.plans[i];
+			o.status = (Trajectory::Status)r[i].status;
+			o.numPresent = r[i].n_present;
+			o.first = r[i].first;
+			o.last = r[i].last;
+			o.sEnter = r[i].s_enter;
+			o.sLeave = r[i].s_leave;
+			for (size_t m = 0; m < T; m++)
+				o.poses.emplace_back(xyt[(i * T + m) * 3], xyt[(i * T + m) * 3 + 1], xyt[(i * T + m) * 3 + 2]);
+		}
+		out.pairs.resize(nPairs);
+		for (size_t p = 0; p < nPairs; p++) {
+			Conflict& o = out.pairs[p];
+			o.status = (Conflict::Status)c[p].status;
+			o.numTimes = c[p].n_times;
+			o.numConflict = c[p].n_conflict;
+			o.tFirst = c[p].t_first;
+			o.minSeparation = c[p].min_separation;
+			o.tMin = c[p].t_min;
+			for (int k = 0; k < 2; k++) {
+				o.sFirst[k] = c[p].s_first[k];
+				o.sMin[k] = c[p].s_min[k];
+			}
+		}
+		return out;
+	}
 	/// HybridAStar::GetPath() of a held query: after PostProcess the sampled and, when the smoother succeeded, smoothed path; before it the
 	/// graph-search nodes
 	std::vector<Pose2d> GetPath(uint64_t ticket) const

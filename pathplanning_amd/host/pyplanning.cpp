@@ -461,6 +461,41 @@ PYBIND11_MODULE(pyplanning, m)
 			py::arg("a_lat") = 2.0, py::arg("dwell") = 0.0, py::arg("clearance_gain") = 0.0, py::arg("v_floor") = 0.0, py::arg("max_samples") = 2048,
 			py::arg("from_length") = std::vector<double>(), py::arg("to_length") = std::vector<double>(), py::arg("v_start") = std::vector<double>(),
 			py::arg("v_end") = std::vector<double>(), py::arg("validator") = Ref<StateValidatorOccupancyMap>())
+		.def("conflicts",
+			[](HybridAStarPipeline& h, const std::vector<uint64_t>& tickets, const std::vector<double>& tStart, const py::object& pairs, double tFrom, double tTo, double dt,
+				double margin, bool holdBefore, bool holdAfter, bool poses) {
+				HybridAStarPipeline::ConflictHorizon horizon;
+				horizon.tFrom = tFrom;
+				horizon.tTo = tTo;
+				horizon.dt = dt;
+				horizon.margin = margin;
+				horizon.holdBefore = holdBefore;
+				horizon.holdAfter = holdAfter;
+				const bool all = pairs.is_none();
+				const auto r = h.Conflicts(tickets, tStart, all ? std::vector<std::pair<int, int>>() : pairs.cast<std::vector<std::pair<int, int>>>(), all, horizon, poses);
+				py::list plans, found, xyt;
+				for (const auto& p : r.plans) {
+					plans.append(py::make_tuple((int)p.status, p.numPresent, p.first, p.last, p.sEnter, p.sLeave));
+					if (poses) {
+						py::list one;
+						for (const Pose2d& q : p.poses)
+							one.append(py::make_tuple(q.x(), q.y(), q.theta));
+						xyt.append(one);
+					}
+				}
+				for (const auto& c : r.pairs)
+					found.append(py::make_tuple((int)c.status, c.numTimes, c.numConflict, c.tFirst, py::make_tuple(c.sFirst[0], c.sFirst[1]), c.minSeparation, c.tMin,
+						py::make_tuple(c.sMin[0], c.sMin[1])));
+				return poses ? py::object(py::make_tuple(plans, found, xyt)) : py::object(py::make_tuple(plans, found));
+			},
+			"Space-time conflicts between held queries on the timetables of the last speed_profile call.  tickets: the held queries; t_start: the absolute time each starts "
+			"to drive, one per ticket; pairs: (i, j) indices into tickets, None: every i < j in row-major order; t_from, t_to: the horizon in absolute seconds; dt: the step of "
+			"the global time lattice k * dt; margin: conflict iff the separation of the vehicles' discs is below it; hold_before / hold_after: a vehicle stands at its first / "
+			"last sample before its start / behind its end instead of being absent; poses: also return every plan's (x, y, theta) per lattice time (NaN where absent).  Returns "
+			"(plans, pairs[, poses]): per plan (status, n_present, first, last, s_enter, s_leave), per pair (status, n_times, n_conflict, t_first, s_first, min_separation, "
+			"t_min, s_min).",
+			py::arg("tickets"), py::arg("t_start"), py::arg("pairs") = py::none(), py::arg("t_from") = 0.0, py::arg("t_to") = 60.0, py::arg("dt") = 0.1, py::arg("margin") = 0.0,
+			py::arg("hold_before") = false, py::arg("hold_after") = false, py::arg("poses") = false)
 		.def("get_path", &HybridAStarPipeline::GetPath, py::arg("ticket"))
 		.def("get_graph_search_path", &HybridAStarPipeline::GetGraphSearchPath, py::arg("ticket"))
 		.def("get_smoothing_status", &HybridAStarPipeline::GetSmoothingStatus, py::arg("ticket"))

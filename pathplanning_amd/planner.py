@@ -12,8 +12,8 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import (RS_PATH_DTYPE, FootprintDisc, HybridParams, LocateParams, LocateResult, MapDesc, PostResult, QueryResult, RevalidateResult, SmootherParams,
-                   SpeedProfileParams, SpeedProfileResult, StampParams, StampResult, check, ptr)
+from ._lib import (RS_PATH_DTYPE, ConflictParams, ConflictResult, FootprintDisc, HybridParams, LocateParams, LocateResult, MapDesc, PostResult, QueryResult, RevalidateResult,
+                   SmootherParams, SpeedProfileParams, SpeedProfileResult, StampParams, StampResult, TrajectoryResult, check, ptr)
 
 
 class Status:
@@ -708,6 +708,13 @@ class HybridAStarBatch:
                               lambda a, b, vs, ve, sp, rows, out: self.lib.pp_planner_speed_profile(self.h, map_set.h if map_set is not None else None, n, ptr(a), ptr(b), ptr(vs),
                                                                                                     ptr(ve), C.byref(sp), int(max_samples), ptr(rows), out))
 
+    def conflicts(self, t_start, n_queries=None, pairs=None, t_from=0.0, t_to=60.0, dt=0.1, margin=0.0, hold_before=False, hold_after=False, poses=False):
+        """Space-time conflicts between the plans of the first n queries of the last batch on the timetables of the planner's last speed_profile call:
+        pp_planner_conflicts, the batch form of HybridAStarPipeline.conflicts, with the same arguments (pair indices are query indices) and return value."""
+        n = len(self._results) if n_queries is None else int(n_queries)
+        return _conflicts(n, t_start, pairs, t_from, t_to, dt, margin, hold_before, hold_after, poses,
+                          lambda ts, npairs, pr, cp, xyt, plans, out: self.lib.pp_planner_conflicts(self.h, n, ptr(ts), npairs, ptr(pr), C.byref(cp), ptr(xyt), plans, out))
+
     def certify_lattice(self, q):
         """SURVEY 7.3 H2 as a contract (pp_planner_certify_lattice): created nodes and logged lattice-line children of query q recomputed on
         the host with glibc; returns (checked, cell mismatches, unverified events, largest pose difference).  mismatches == unverified == 0
@@ -1053,6 +1060,23 @@ class HybridAStarPipeline:
                               lambda a, b, vs, ve, sp, rows, out: self.lib.pp_pipeline_speed_profile(self.h, map_set.h if map_set is not None else None, len(t), ptr(t), ptr(a),
                                                                                                      ptr(b), ptr(vs), ptr(ve), C.byref(sp), int(max_samples), ptr(rows), out))
 
+    def conflicts(self, tickets, t_start, pairs=None, t_from=0.0, t_to=60.0, dt=0.1, margin=0.0, hold_before=False, hold_after=False, poses=False):
+        """Do the vehicles of the completed, HELD queries `tickets`, each driving its plan on the timetable of the pipeline's last speed_profile call
+        from t_start[k] (absolute seconds) on, ever come too close at the same time?  pp_pipeline_conflicts, whose definition is in include/pp_hip.h:
+        every plan's pose at the times k * dt inside [t_from, t_to], then for every pair in `pairs` ([n_pairs, 2] indices into `tickets`; None: every
+        pair i < j, row-major) the separation of the vehicles' discs (the pipeline's footprint, else the map's min_safe_radius) at the times both are
+        present; conflict iff separation < margin.  hold_before / hold_after: a vehicle stands at its first / last sample before its start / behind
+        its end instead of being absent.  Nothing but the call's own buffers is written: legal while other queries are in flight.
+        Returns (TrajectoryResult per ticket, ConflictResult per pair) and, with poses=True, a list of (T, 3) arrays of (x, y, theta), NaN where the
+        vehicle is absent.
+        Raises PPError, with nothing launched, for a ticket that is unknown, released, in flight, given twice or without a speed profile (run
+        speed_profile first), a t_start that is not finite, a horizon, dt, margin or hold flag outside its domain, fewer than 1 or more than 2^20
+        lattice times, a pair index outside the tickets or a pair of a plan with itself."""
+        t = np.ascontiguousarray(tickets, dtype=np.uint64).reshape(-1)
+        return _conflicts(len(t), t_start, pairs, t_from, t_to, dt, margin, hold_before, hold_after, poses,
+                          lambda ts, npairs, pr, cp, xyt, plans, out: self.lib.pp_pipeline_conflicts(self.h, len(t), ptr(t), ptr(ts), npairs, ptr(pr), C.byref(cp), ptr(xyt),
+                                                                                                     plans, out))
+
     def get_expanded_of(self, ticket):
         """expansion sequence (log_expansions=True) of a completed query polled with release=False"""
         slot = self.lib.pp_pipeline_slot_of(self.h, C.c_uint64(int(ticket)))
@@ -1135,6 +1159,31 @@ def _speed_profile(n, from_length, to_length, v_start, v_end, max_samples, sampl
     if not samples:
         return recs
     return recs, [rows[i, :r.n_samples].copy() if r.status == 0 else np.zeros((0, 3)) for i, r in enumerate(recs)]
+
+
+def conflict_lattice(t_from, t_to, dt):
+    """(k0, T) of the time lattice k * dt inside [t_from, t_to], as the library forms them: tau_m = (k0 + m) * dt for m = 0 .. T - 1"""
+    k0, k1 = np.ceil(np.float64(t_from) / np.float64(dt)), np.floor(np.float64(t_to) / np.float64(dt))
+    k0, k1 = (int(np.clip(k, -2.0 ** 62, 2.0 ** 62)) if k == k else 2 ** 62 for k in (k0, k1))
+    return k0, max(k1 - k0 + 1, 0)
+
+
+def _conflicts(n, t_start, pairs, t_from, t_to, dt, margin, hold_before, hold_after, poses, call):
+    """the parameters, start times and pair list of a conflict call, the call, its plan and pair records and (if wanted) each plan's (x, y, theta) per lattice time"""
+    cp = ConflictParams(float(t_from), float(t_to), float(dt), float(margin), int(hold_before), int(hold_after))
+    ts = _per_plan(t_start, n)
+    if ts is None and n:
+        raise ValueError("one start time per plan")
+    pr = None if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    n_pairs = n * (n - 1) // 2 if pr is None else len(pr)
+    xyt = None
+    if poses:
+        T = conflict_lattice(t_from, t_to, dt)[1] if float(dt) > 0.0 and np.isfinite([t_from, t_to, dt]).all() else 0
+        xyt = np.full((n, T if T <= 1 << 20 else 0, 3), np.nan)
+    plans, out = (TrajectoryResult * max(n, 1))(), (ConflictResult * max(n_pairs, 1))()
+    check(call(ts, n_pairs, pr, cp, xyt, plans, out))
+    recs = (list(plans)[:n], list(out)[:n_pairs])
+    return recs + ([xyt[i] for i in range(n)],) if poses else recs
 
 
 def _locate(n, poses, from_length, to_length, spacing, heading_weight, call):
