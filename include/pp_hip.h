@@ -816,6 +816,58 @@ int pp_pipeline_conflicts(pp_pipeline* pipeline, int32_t n, const uint64_t* tick
  * is a pipeline's buffer set (pp_pipeline_conflicts knows which slots are held). */
 int pp_planner_conflicts(pp_planner* planner, int32_t n_queries, const double* t_start, int32_t n_pairs, const int32_t* pairs,
 	const pp_conflict_params* params, double* poses_host, pp_trajectory_result* plans_host, pp_conflict_result* results_host);
+/* ---- start delays that clear conflicts, by priority and ticket ------------------------------------------------------------------------------------
+ * How long must a lower-priority vehicle wait at its start so that it stays clear of the vehicles above it?  The call takes what a conflict call
+ * takes -- n plans, a start time for each, a list of pairs, the lattice -- and a largest delay, and gives every vehicle the smallest whole number
+ * of lattice steps to wait so that, on the lattice, it is never closer than the margin to a pair partner of higher priority.  No plan data leaves
+ * the device.  It reads no map and writes nothing but its own buffers, so the call is legal beside queries in flight.
+ *  Priority. The position in `tickets`: index 0 never yields, and of a pair (a, b) the larger index yields.  The caller sorts: vehicles already
+ *           under way go first, with no pairs among themselves.
+ *  Lattice. k0, k1, T, tau_m, the profiles, position, pose, discs and separation are exactly "space-time conflicts between held plans"' for
+ *           params->lattice.  With D = max_delay_steps (0 <= D, T + D <= 2^20) the call forms the EXTENDED trajectory of every plan: its pose at
+ *           the lattice indices k0 - D .. k1, T + D columns, with the undelayed t_start[i] (k_trajectory_tickets, unchanged, on that lattice).
+ *  Delay.   A delay is a whole number of lattice steps, and delaying by d steps is an index shift: at lattice time tau_m = (k0 + m) * dt, m = 0 ..
+ *           T - 1, vehicle i with delay d_i is where its extended trajectory has column m + D - d_i, and absent exactly where that column is (a NaN).
+ *           No time is recomputed, so the result does not depend on the order of evaluation and is reproducible bit for bit from the trajectory.
+ *           The effective start reported is t_start[i] + (double)d_i * dt.  A later conflict call with that start forms u = tau - t_start' afresh,
+ *           so it agrees with what was decided here to rounding, not bit for bit.
+ *  Rule.    Vehicles are decided in index order.  Vehicle i takes the smallest d in 0 .. D such that at every m in 0 .. T - 1 and against every
+ *           pair partner j < i that is scheduled (status 0, delay d_j) the two are not both present with separation < margin.  If no d <= D is
+ *           clear, its status is 1 and delay_steps = -1, and the vehicles below it are scheduled AS IF IT WERE ABSENT: the caller replans it or calls
+ *           again with a larger D.  A plan whose profile or status is bad (pp_trajectory_result::status -1) gets status -1 and is ignored likewise.
+ *  Blocker. blocker, t_block and s_block describe the LAST REJECTED candidate: d - 1 for a vehicle that waited d steps, D for status 1.  Of that
+ *           candidate's conflicts it is the one with the least key (m, j), compared as integers (m * n + j): blocker = j, an index into tickets,
+ *           t_block = tau_m, s_block the arc lengths of i and of j there.  With no rejected candidate blocker is -1 and t_block, s_block are zero.
+ *           n_tried is the number of candidates evaluated: delay_steps + 1, or D + 1 for status 1.
+ *  Schedule. The order between vehicles is known without device data: level(i) = 0 with no partner j < i, else 1 + max level(j).  The host builds
+ *           the levels and each vehicle's list of lower-index partners, and launches k_delay_level once per level, one wave per vehicle of the
+ *           level, on the holder's stream; the order of that stream is the only synchronisation.  pairs == NULL lists every pair, so level(i) = i:
+ *           n launches of one wave each and n (n - 1) / 2 list entries.  A fleet passes the pairs that can meet.
+ *  - PP_ERR_INVALID, nothing launched, the holder usable as before: every refusal of the conflict call (a ticket without a remembered profile: "run
+ *    speed_profile first"), and max_delay_steps < 0, T + D > 2^20, reserved != 0.  n == 0 is PP_OK.  results_host may be NULL.
+ *  - The holder owns, beside the conflict call's buffers (the trajectory of the largest n x (T + D) so far), 12 + 48 bytes per plan, 4 per listed
+ *    pair, kept aside like the post-processing buffers when they have to grow beside queries in flight. */
+typedef struct pp_delay_params {
+	pp_conflict_params lattice; /* the conflict call's: horizon, dt, margin, hold flags */
+	int32_t max_delay_steps;    /* D >= 0, T + D <= 2^20: the delays tried are 0 .. D lattice steps */
+	int32_t reserved;           /* zero */
+} pp_delay_params;             /* 48 bytes */
+typedef struct pp_delay_result {
+	int32_t status;        /* 0 scheduled; 1 no delay of 0 .. D steps is clear; -1 the ticket's profile has status != 0 */
+	int32_t delay_steps;   /* d; -1 for status 1 and -1 */
+	int32_t n_tried;       /* candidates evaluated */
+	int32_t blocker;       /* index into tickets of the partner that rejected the last rejected candidate; -1: none was rejected */
+	double  t_start;       /* the effective start t_start[i] + (double)d * dt; t_start[i] for status 1; zero for status -1 */
+	double  t_block;       /* the lattice time of that candidate's first conflict */
+	double  s_block[2];    /* arc lengths of this vehicle and of the blocker there */
+} pp_delay_result;        /* 48 bytes; for status -1 every field but status, delay_steps and blocker is zero */
+int pp_pipeline_deconflict(pp_pipeline* pipeline, int32_t n, const uint64_t* tickets, const double* t_start /* [n], finite */, int32_t n_pairs,
+	const int32_t* pairs /* may be NULL */, const pp_delay_params* params, pp_delay_result* results_host /* may be NULL */);
+/* The same kernels over the first n_queries queries of the planner's last batch (identity slots; the profiles of the planner's last
+ * pp_planner_speed_profile call), on the planner's stream, with the planner's footprint if it has one.  PP_ERR_INVALID as above, and for a planner that
+ * is a pipeline's buffer set (pp_pipeline_deconflict knows which slots are held). */
+int pp_planner_deconflict(pp_planner* planner, int32_t n_queries, const double* t_start, int32_t n_pairs, const int32_t* pairs,
+	const pp_delay_params* params, pp_delay_result* results_host);
 /* Diagnostics: waves of the search grid that are alive right now (a blocking device-to-host copy; -1 on error). */
 int pp_pipeline_alive_waves(pp_pipeline* pipeline);
 pp_planner* pp_pipeline_planner(pp_pipeline* pipeline);           /* the buffer set: set_nonholo_table, set_primitives, get_path(slot), ... */

@@ -139,6 +139,20 @@ class ConflictResult(C.Structure):
                 ("s_first", C.c_double * 2), ("min_separation", C.c_double), ("t_min", C.c_double), ("s_min", C.c_double * 2), ("reserved1", C.c_double)]
 
 
+class DelayParams(C.Structure):
+    """pp_delay_params: the conflict call's parameters (horizon, dt, margin, hold flags) and max_delay_steps, the largest delay tried in lattice steps
+    (>= 0, T + max_delay_steps <= 2^20); reserved is zero"""
+    _fields_ = [("lattice", ConflictParams), ("max_delay_steps", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DelayResult(C.Structure):
+    """pp_delay_result: status 0 scheduled, 1 no delay of 0 .. max_delay_steps is clear, -1 the plan's speed profile has a status other than 0; the
+    delay in lattice steps (-1: none), the candidates evaluated, the partner (an index into the call's plans; -1: none) that rejected the last rejected
+    candidate, the effective start, and the lattice time and the two arc lengths of that candidate's first conflict"""
+    _fields_ = [("status", C.c_int32), ("delay_steps", C.c_int32), ("n_tried", C.c_int32), ("blocker", C.c_int32), ("t_start", C.c_double), ("t_block", C.c_double),
+                ("s_block", C.c_double * 2)]
+
+
 class LocateResult(C.Structure):
     """pp_locate_result: status 0 located, 1 no sample in the window, -1 no plan, -4 path beyond the path capacity; the located point's edge
     (1 .. n_path - 1; 0 for a one-pose plan), travel direction (+1 / -1), arc length s, ratio on the edge and path pose; the vehicle's distance,
@@ -279,6 +293,8 @@ def load():
     L.pp_planner_speed_profile.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, C.POINTER(SpeedProfileParams), C.c_int32, vp, vp]
     L.pp_pipeline_conflicts.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, C.POINTER(ConflictParams), vp, vp, vp]
     L.pp_planner_conflicts.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.POINTER(ConflictParams), vp, vp, vp]
+    L.pp_pipeline_deconflict.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, C.POINTER(DelayParams), vp]
+    L.pp_planner_deconflict.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.POINTER(DelayParams), vp]
     L.pp_pipeline_timings.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.pp_pipeline_backlog.argtypes = [vp, vp, vp]
     L.pp_pipeline_planner.argtypes = [vp]

@@ -2,8 +2,8 @@
 // names their argument types) and in front of pp_planner and pp_pipeline, which both keep one buffer group per service.
 //
 // Finished plans (path records, Reeds-Shepp log, result record) are held by a batch planner, as queries 0 .. n-1 of its last batch, or by a pipeline, as
-// the slots of held tickets.  A service over them -- post-processing, re-validation, the stamp, the locate call, the speed profile, the conflict call -- has one core (post_process_plans,
-// revalidate_plans, stamp_plans, locate_plans, speed_profile_plans, conflict_plans in pp_planner.hip) that takes a HeldPlans and goes through held_grow and held_run; its two extern "C"
+// the slots of held tickets.  A service over them -- post-processing, re-validation, the stamp, the locate call, the speed profile, the conflict call, the delay call -- has one core (post_process_plans,
+// revalidate_plans, stamp_plans, locate_plans, speed_profile_plans, conflict_plans, deconflict_plans in pp_planner.hip) that takes a HeldPlans and goes through held_grow and held_run; its two extern "C"
 // entries check what is the holder's own and describe the holder (batch_plans, pipe_plans).
 #pragma once
 
@@ -97,6 +97,17 @@ struct ConflictGroup {
 	size_t listed = 0; // pairs `pairs` holds (8 bytes each)
 	pph::Dev<pp_conflict_result> out;
 	size_t pairRows = 0; // pair records `out` holds
+};
+
+/// What the delay call adds to the conflict call's buffers (it forms its extended trajectory in ConflictGroup's `rec` and `traj`, grown for n x (T + D)
+/// columns): per plan its place in the level order, the start of its partner list and its decided delay; the lists of lower-index partners; the records
+struct DelayGroup {
+	pph::Dev<int32_t> members, offsets, delays;
+	size_t vehicles = 0; // plans they hold (`offsets` one more)
+	pph::Dev<int32_t> partners;
+	size_t listed = 0; // partners `partners` holds (4 bytes each)
+	pph::Dev<pp_delay_result> out;
+	size_t rows = 0; // records `out` holds
 };
 
 /// Buffers that hold `capacity` units are made to hold `wanted` ({buffer, bytes}; 0 bytes: the holder does not use it).  A holder that may not free now

@@ -209,6 +209,7 @@ struct pp_pipeline {
 	HeldBuffers<LocateArg, pp_locate_result> locate;
 	SpeedGroup speed;
 	ConflictGroup conflict;
+	DelayGroup delay;
 	std::vector<pph::DeviceMem> heldParked; // their buffers outgrown while queries were in flight: hipFree waits for the whole device (the persistent grid
 	                                        // included), so they are kept until a call finds nothing in flight (or the pipeline goes): held_grow
 	int nWf = 2;      // wavefront streams in use: consecutive submissions' launches overlap (the tail of one under the head of the next)
@@ -1212,6 +1213,25 @@ int pp_pipeline_conflicts(pp_pipeline* P, int32_t n, const uint64_t* tickets, co
 	if (int rc = conflict_profiles(h, P->speed, t_start, lattice, plans))
 		return rc;
 	return conflict_plans(h, P->conflict, P->speed, plans, lattice, n_pairs, pairs, poses_host, plans_host, results_host);
+}
+
+/// Start delays that clear the conflicts of n completed, held queries with their pair partners of higher priority (include/pp_hip.h; deconflict_plans):
+/// legal beside queries in flight
+int pp_pipeline_deconflict(pp_pipeline* P, int32_t n, const uint64_t* tickets, const double* t_start, int32_t n_pairs, const int32_t* pairs, const pp_delay_params* params,
+	pp_delay_result* results_host)
+{
+	HeldPlans h;
+	if (int rc = pipe_plans(P, n, tickets, h))
+		return rc;
+	ConflictLattice lattice;
+	if (int rc = delay_check(h, t_start, n_pairs, pairs, params, lattice))
+		return rc;
+	if (int rc = pipe_resolve(P, n, tickets, "scheduled", true, h.slots))
+		return rc;
+	std::vector<ConflictArg> plans;
+	if (int rc = conflict_profiles(h, P->speed, t_start, lattice, plans))
+		return rc;
+	return deconflict_plans(h, P->conflict, P->delay, P->speed, plans, lattice, params ? params->max_delay_steps : 0, n_pairs, pairs, results_host);
 }
 
 /// Launch durations seen so far (HIP events on the launching streams; harvested by pp_pipeline_poll) and reset.  Wavefront: one launch per

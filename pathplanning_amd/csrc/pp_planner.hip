@@ -21,6 +21,7 @@
 #include "pp_locate_rule.hpp"
 #include "pp_speed_rule.hpp"
 #include "pp_conflict_rule.hpp"
+#include "pp_delay_rule.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -311,6 +312,8 @@ struct PipeView {
 #include "pp_speed_profile.hpp"
 // space-time conflicts between held plans on the timetables of their speed profiles (one wave per plan, then one per pair; the same PostEdge / load_edge)
 #include "pp_conflicts.hpp"
+// start delays that clear those conflicts, by priority (one wave per vehicle of a level, one launch per level; reads the trajectory layout of the file above)
+#include "pp_deconflict.hpp"
 
 } // namespace
 
@@ -377,6 +380,7 @@ struct pp_planner {
 	HeldBuffers<LocateArg, pp_locate_result> locate;
 	SpeedGroup speed;
 	ConflictGroup conflict;
+	DelayGroup delay;
 };
 
 namespace {
@@ -488,6 +492,16 @@ hipError_t launch_conflict_pairs(hipStream_t s, const Footprint& discs, const Co
 	return hipGetLastError();
 }
 
+/// k_delay_level over the `count` vehicles `membersDev` of one level (count = 0 on a grid of one: the warm-up, which dereferences nothing)
+hipError_t launch_delay_level(hipStream_t s, const Footprint& discs, const ConflictLattice& lattice, int maxDelay, int plans, int count, const int32_t* membersDev,
+	const int32_t* offsetsDev, const int32_t* partnersDev, const ConflictArg* argsDev, const double* trajDev, const pp_trajectory_result* plansDev, int32_t* delaysDev,
+	pp_delay_result* outDev)
+{
+	hipLaunchKernelGGL(k_delay_level, dim3((unsigned)(count > 0 ? count : 1)), dim3(kDelayLanes), 0, s, discs, lattice, maxDelay, plans, count, membersDev, offsetsDev, partnersDev,
+		argsDev, trajDev, plansDev, delaysDev, outDev);
+	return hipGetLastError();
+}
+
 /// An empty dispatch of each kernel that works on held plans (post-processing in the holder's form), on stream s, which is drained behind each: the queue
 /// allocates their scratch here, where a failure is an error code (see warm_up_kernels).  *service names the service whose kernel failed.
 hipError_t warm_up_held_kernels(pp_planner* p, hipStream_t s, bool byTicket, const char** service)
@@ -513,6 +527,8 @@ hipError_t warm_up_held_kernels(pp_planner* p, hipStream_t s, bool byTicket, con
 			if (ok("speed profile", launch_speed_profile(s, p->args, Footprint {}, nullptr, 1, 0, nullptr, nullptr, p, nullptr, nullptr)))
 				if (ok("conflict trajectories", launch_trajectory(s, p->args, ConflictLattice {}, false, 0, nullptr, nullptr, p, nullptr, nullptr, nullptr)))
 					(void)ok("conflict pairs", launch_conflict_pairs(s, Footprint {}, ConflictLattice {}, 0, 0, nullptr, nullptr, nullptr, nullptr));
+	if (e == hipSuccess)
+		(void)ok("delay levels", launch_delay_level(s, Footprint {}, ConflictLattice {}, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
 	return e;
 }
 
@@ -838,6 +854,30 @@ int conflict_check(const HeldPlans& h, const double* t_start, int n_pairs, const
 	return PP_OK;
 }
 
+/// The arguments of a delay call (pp_planner_deconflict, pp_pipeline_deconflict): the conflict call's, and the largest delay.  `lattice` is the conflict call's,
+/// of T columns from k0 on; the extended one is formed where the trajectory is launched.
+int delay_check(const HeldPlans& h, const double* t_start, int n_pairs, const int32_t* pairs, const pp_delay_params* params, ConflictLattice& lattice)
+{
+	if (int rc = conflict_check(h, t_start, n_pairs, pairs, params ? &params->lattice : nullptr, lattice))
+		return rc;
+	if (!params)
+		return PP_OK; // (n == 0)
+	if (params->max_delay_steps < 0) {
+		set_error("invalid arguments (max_delay_steps >= 0, got " + std::to_string(params->max_delay_steps) + ")");
+		return PP_ERR_INVALID;
+	}
+	if ((int64_t)lattice.T + params->max_delay_steps > ppc::kMaxTimes) {
+		set_error("invalid arguments (the extended trajectory holds T + max_delay_steps = " + std::to_string((int64_t)lattice.T + params->max_delay_steps) +
+			" lattice times: at most " + std::to_string(ppc::kMaxTimes) + ")");
+		return PP_ERR_INVALID;
+	}
+	if (params->reserved != 0) {
+		set_error("invalid arguments (the delay call's reserved field is zero)");
+		return PP_ERR_INVALID;
+	}
+	return PP_OK;
+}
+
 /// ... and what the holder remembers of its last speed-profile call for the plans of h: their rows, into `plans`, and the call's stride and limits, into `lattice`
 int conflict_profiles(const HeldPlans& h, const SpeedGroup& g, const double* t_start, ConflictLattice& lattice, std::vector<ConflictArg>& plans)
 {
@@ -1052,6 +1092,55 @@ int conflict_plans(const HeldPlans& h, ConflictGroup& g, const SpeedGroup& speed
 		for (size_t i = 0; i < component; i++) // (plan-major in both: plan i, time m is i * T + m)
 			for (size_t c = 0; c < 3; c++)
 				poses_host[i * 3 + c] = staged[c * component + i];
+	return PP_OK;
+}
+
+/// Start delays of the plans of h (`plans`, `lattice`: delay_check's and conflict_profiles'; D: the largest delay in lattice steps).  The host orders the vehicles
+/// by level and lists each one's lower-index partners (pp_delay_rule.hpp); the extended trajectory is k_trajectory_tickets on the lattice k0 - D .. k1, in the
+/// conflict call's buffers; then one k_delay_level per level.  Uploads, launches and the copy of the records run on the holder's stream, which held_run
+/// synchronises once.
+int deconflict_plans(const HeldPlans& h, ConflictGroup& c, DelayGroup& g, const SpeedGroup& speed, const std::vector<ConflictArg>& plans, const ConflictLattice& lattice, int D,
+	int n_pairs, const int32_t* pairs, pp_delay_result* results_host)
+{
+	if (h.n == 0)
+		return PP_OK;
+	pp_planner* const pl = h.pl;
+	PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
+	const size_t n = (size_t)h.n, columns = (size_t)lattice.T + (size_t)D, nListed = (size_t)n_pairs, component = n * columns;
+	std::vector<int32_t> offsets(n + 1), cursor(n), list(nListed), level(n), members(n);
+	ppy::partner_offsets(h.n, n_pairs, pairs, offsets.data());
+	ppy::partner_list(h.n, n_pairs, pairs, offsets.data(), cursor.data(), list.data());
+	const int nLevels = ppy::levels(h.n, offsets.data(), list.data(), level.data());
+	std::vector<int32_t> first((size_t)nLevels + 1);
+	ppy::members_by_level(h.n, nLevels, level.data(), first.data(), members.data());
+	PP_HIP_TRY(held_grow(h, c.doubles, component * kTrajectoryComponents, { { &c.traj, component * kTrajectoryComponents * 8 } }));
+	PP_HIP_TRY(held_grow(h, g.vehicles, n, { { &g.members, n * 4 }, { &g.offsets, (n + 1) * 4 }, { &g.delays, n * 4 } }));
+	if (nListed)
+		PP_HIP_TRY(held_grow(h, g.listed, nListed, { { &g.partners, nListed * 4 } }));
+	PP_HIP_TRY(held_grow(h, g.rows, n, { { &g.out, n * sizeof(pp_delay_result) } }));
+	const SearchArgs args = held_args(h, h.ownView);
+	const Footprint discs = stamp_discs(h.footprint, pl->map);
+	ConflictLattice extended = lattice;
+	extended.k0 = lattice.k0 - D;
+	extended.T = lattice.T + D;
+	std::vector<pp_delay_result> recs(results_host ? n : 0);
+	if (int rc = held_run(h, c.rec, plans, (pp_trajectory_result*)nullptr, [&](const int32_t* slotsDev) {
+			hipError_t e = hipMemcpyAsync(g.members, members.data(), n * 4, hipMemcpyHostToDevice, h.stream);
+			if (e == hipSuccess)
+				e = hipMemcpyAsync(g.offsets, offsets.data(), (n + 1) * 4, hipMemcpyHostToDevice, h.stream);
+			if (e == hipSuccess && nListed)
+				e = hipMemcpyAsync(g.partners, list.data(), nListed * 4, hipMemcpyHostToDevice, h.stream);
+			if (e == hipSuccess)
+				e = launch_trajectory(h.stream, args, extended, discs.anyOffset != 0, h.n, slotsDev, c.rec.args.get(), pl, speed.rows.get(), c.traj.get(), c.rec.out.get());
+			for (int l = 0; l < nLevels && e == hipSuccess; l++)
+				e = launch_delay_level(h.stream, discs, lattice, D, h.n, first[(size_t)l + 1] - first[(size_t)l], g.members.get() + first[(size_t)l], g.offsets.get(),
+					g.partners.get(), c.rec.args.get(), c.traj.get(), c.rec.out.get(), g.delays.get(), g.out.get());
+			if (e == hipSuccess && !recs.empty())
+				e = hipMemcpyAsync(recs.data(), g.out, n * sizeof(pp_delay_result), hipMemcpyDeviceToHost, h.stream);
+			return e;
+		}))
+		return rc;
+	std::copy(recs.begin(), recs.end(), results_host);
 	return PP_OK;
 }
 
@@ -1902,6 +1991,21 @@ int pp_planner_conflicts(pp_planner* planner, int32_t n_queries, const double* t
 	if (int rc = conflict_profiles(h, planner->speed, t_start, lattice, plans))
 		return rc;
 	return conflict_plans(h, planner->conflict, planner->speed, plans, lattice, n_pairs, pairs, poses_host, plans_host, results_host);
+}
+
+int pp_planner_deconflict(pp_planner* planner, int32_t n_queries, const double* t_start, int32_t n_pairs, const int32_t* pairs, const pp_delay_params* params,
+	pp_delay_result* results_host)
+{
+	if (int rc = batch_check(planner, n_queries, "pp_pipeline_deconflict schedules its held tickets"))
+		return rc;
+	const HeldPlans h = batch_plans(planner, n_queries);
+	ConflictLattice lattice;
+	if (int rc = delay_check(h, t_start, n_pairs, pairs, params, lattice))
+		return rc;
+	std::vector<ConflictArg> plans;
+	if (int rc = conflict_profiles(h, planner->speed, t_start, lattice, plans))
+		return rc;
+	return deconflict_plans(h, planner->conflict, planner->delay, planner->speed, plans, lattice, params ? params->max_delay_steps : 0, n_pairs, pairs, results_host);
 }
 
 int pp_planner_locate(pp_planner* planner, int32_t n_queries, const double* poses_host, const double* from_length, const double* to_length, const pp_locate_params* params,

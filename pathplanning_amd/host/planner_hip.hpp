@@ -1483,6 +1483,53 @@ public:
 		}
 		return out;
 	}
+	/// What Deconflict says about one held plan (pp_delay_result)
+	struct Delay {
+		enum class Status { Scheduled = 0, NoClearDelay = 1, NoProfile = -1 };
+		Status status = Status::NoProfile;
+		int delaySteps = -1, numTried = 0;
+		int blocker = -1;      // index into tickets of the partner that rejected the last rejected candidate; -1: none was rejected
+		double tStart = 0.0;   // the effective start: tStart[i] + delaySteps * dt
+		double tBlock = 0.0, sBlock[2] = { 0.0, 0.0 }; // the lattice time of that candidate's first conflict, and the two arc lengths there
+	};
+	/// Start delays that clear conflicts, by priority (pp_pipeline_deconflict; include/pp_hip.h has the definition): the position in `tickets` is the
+	/// priority, of a pair of `pairs` (indices into tickets; allPairs: every pair) the larger index yields, and every vehicle takes the smallest delay of
+	/// 0 .. maxDelaySteps lattice steps at which it stays clear of its scheduled partners of smaller index on the lattice of `horizon`.  Needs the LAST
+	/// SpeedProfile call's timetables, as Conflicts does.  Legal beside queries in flight; no plan data leaves the device.
+	std::vector<Delay> Deconflict(const std::vector<uint64_t>& tickets, const std::vector<double>& tStart, const std::vector<std::pair<int, int>>& pairs, bool allPairs,
+		const ConflictHorizon& horizon, int maxDelaySteps)
+	{
+		for (uint64_t t : tickets)
+			HeldOf(t); // (throws for a ticket that is not held)
+		const size_t n = tickets.size();
+		if (tStart.size() != n)
+			throw std::invalid_argument("Deconflict: tStart holds one entry per ticket");
+		std::vector<Delay> out;
+		if (!m_pipe || n == 0)
+			return out;
+		const pp_delay_params dp { { horizon.tFrom, horizon.tTo, horizon.dt, horizon.margin, horizon.holdBefore ? 1 : 0, horizon.holdAfter ? 1 : 0 }, maxDelaySteps, 0 };
+		std::vector<int32_t> list;
+		for (const auto& p : pairs) {
+			list.push_back(p.first);
+			list.push_back(p.second);
+		}
+		const size_t nPairs = allPairs ? n * (n - 1) / 2 : pairs.size();
+		std::vector<pp_delay_result> r(n);
+		ppCheck(pp_pipeline_deconflict(m_pipe, (int32_t)n, tickets.data(), tStart.data(), (int32_t)nPairs, allPairs ? nullptr : list.data(), &dp, r.data()));
+		out.resize(n);
+		for (size_t i = 0; i < n; i++) {
+			Delay& o = out[i];
+			o.status = (Delay::Status)r[i].status;
+			o.delaySteps = r[i].delay_steps;
+			o.numTried = r[i].n_tried;
+			o.blocker = r[i].blocker;
+			o.tStart = r[i].t_start;
+			o.tBlock = r[i].t_block;
+			o.sBlock[0] = r[i].s_block[0];
+			o.sBlock[1] = r[i].s_block[1];
+		}
+		return out;
+	}
 	/// HybridAStar::GetPath() of a held query: after PostProcess the sampled and, when the smoother succeeded, smoothed path; before it the
 	/// graph-search nodes
 	std::vector<Pose2d> GetPath(uint64_t ticket) const

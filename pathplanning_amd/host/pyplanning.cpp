@@ -496,6 +496,30 @@ PYBIND11_MODULE(pyplanning, m)
 			"t_min, s_min).",
 			py::arg("tickets"), py::arg("t_start"), py::arg("pairs") = py::none(), py::arg("t_from") = 0.0, py::arg("t_to") = 60.0, py::arg("dt") = 0.1, py::arg("margin") = 0.0,
 			py::arg("hold_before") = false, py::arg("hold_after") = false, py::arg("poses") = false)
+		.def("deconflict",
+			[](HybridAStarPipeline& h, const std::vector<uint64_t>& tickets, const std::vector<double>& tStart, const py::object& pairs, double tFrom, double tTo, double dt,
+				double margin, bool holdBefore, bool holdAfter, int maxDelaySteps) {
+				HybridAStarPipeline::ConflictHorizon horizon;
+				horizon.tFrom = tFrom;
+				horizon.tTo = tTo;
+				horizon.dt = dt;
+				horizon.margin = margin;
+				horizon.holdBefore = holdBefore;
+				horizon.holdAfter = holdAfter;
+				const bool all = pairs.is_none();
+				py::list out;
+				for (const auto& d : h.Deconflict(tickets, tStart, all ? std::vector<std::pair<int, int>>() : pairs.cast<std::vector<std::pair<int, int>>>(), all, horizon, maxDelaySteps))
+					out.append(py::make_tuple((int)d.status, d.delaySteps, d.numTried, d.blocker, d.tStart, d.tBlock, py::make_tuple(d.sBlock[0], d.sBlock[1])));
+				return out;
+			},
+			"Start delays that clear conflicts between held queries, by priority, on the timetables of the last speed_profile call.  tickets: the held queries, highest "
+			"priority first; t_start: the absolute time each would start to drive, one per ticket; pairs: (i, j) indices into tickets, of which the larger index yields, None: "
+			"every pair; t_from, t_to: the horizon in absolute seconds; dt: the step of the global time lattice k * dt, and of the delays; margin: conflict iff the separation "
+			"of the vehicles' discs is below it; hold_before / hold_after: a vehicle stands at its first / last sample before its start / behind its end instead of being "
+			"absent; max_delay_steps: the largest delay tried, in lattice steps.  Returns per ticket (status, delay_steps, n_tried, blocker, t_start, t_block, s_block): "
+			"status 0 scheduled with the effective start t_start, 1 no delay is clear (those below ignore it), -1 no speed profile.",
+			py::arg("tickets"), py::arg("t_start"), py::arg("pairs") = py::none(), py::arg("t_from") = 0.0, py::arg("t_to") = 60.0, py::arg("dt") = 0.1, py::arg("margin") = 0.0,
+			py::arg("hold_before") = false, py::arg("hold_after") = false, py::arg("max_delay_steps") = 0)
 		.def("get_path", &HybridAStarPipeline::GetPath, py::arg("ticket"))
 		.def("get_graph_search_path", &HybridAStarPipeline::GetGraphSearchPath, py::arg("ticket"))
 		.def("get_smoothing_status", &HybridAStarPipeline::GetSmoothingStatus, py::arg("ticket"))

@@ -12,7 +12,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import (RS_PATH_DTYPE, ConflictParams, ConflictResult, FootprintDisc, HybridParams, LocateParams, LocateResult, MapDesc, PostResult, QueryResult, RevalidateResult,
+from ._lib import (RS_PATH_DTYPE, ConflictParams, ConflictResult, DelayParams, DelayResult, FootprintDisc, HybridParams, LocateParams, LocateResult, MapDesc, PostResult, QueryResult, RevalidateResult,
                    SmootherParams, SpeedProfileParams, SpeedProfileResult, StampParams, StampResult, TrajectoryResult, check, ptr)
 
 
@@ -715,6 +715,13 @@ class HybridAStarBatch:
         return _conflicts(n, t_start, pairs, t_from, t_to, dt, margin, hold_before, hold_after, poses,
                           lambda ts, npairs, pr, cp, xyt, plans, out: self.lib.pp_planner_conflicts(self.h, n, ptr(ts), npairs, ptr(pr), C.byref(cp), ptr(xyt), plans, out))
 
+    def deconflict(self, t_start, n_queries=None, pairs=None, t_from=0.0, t_to=60.0, dt=0.1, margin=0.0, hold_before=False, hold_after=False, max_delay_steps=0):
+        """Start delays that clear the conflicts between the plans of the first n queries of the last batch, by priority (the query index):
+        pp_planner_deconflict, the batch form of HybridAStarPipeline.deconflict, with the same arguments (pair indices are query indices) and return value."""
+        n = len(self._results) if n_queries is None else int(n_queries)
+        return _deconflict(n, t_start, pairs, t_from, t_to, dt, margin, hold_before, hold_after, max_delay_steps,
+                           lambda ts, npairs, pr, dp, out: self.lib.pp_planner_deconflict(self.h, n, ptr(ts), npairs, ptr(pr), C.byref(dp), ptr(out)))
+
     def certify_lattice(self, q):
         """SURVEY 7.3 H2 as a contract (pp_planner_certify_lattice): created nodes and logged lattice-line children of query q recomputed on
         the host with glibc; returns (checked, cell mismatches, unverified events, largest pose difference).  mismatches == unverified == 0
@@ -1077,6 +1084,21 @@ class HybridAStarPipeline:
                           lambda ts, npairs, pr, cp, xyt, plans, out: self.lib.pp_pipeline_conflicts(self.h, len(t), ptr(t), ptr(ts), npairs, ptr(pr), C.byref(cp), ptr(xyt),
                                                                                                      plans, out))
 
+    def deconflict(self, tickets, t_start, pairs=None, t_from=0.0, t_to=60.0, dt=0.1, margin=0.0, hold_before=False, hold_after=False, max_delay_steps=0):
+        """How long must each vehicle of the completed, HELD queries `tickets` wait at its start so that it stays clear of the vehicles above it?
+        pp_pipeline_deconflict, whose definition is in include/pp_hip.h.  Priority is the position in `tickets`: of a pair of `pairs` ([n_pairs, 2]
+        indices into `tickets`; None: every pair) the larger index yields.  The lattice (t_from, t_to, dt), the margin and the hold flags are those of
+        conflicts(); a delay is a whole number of lattice steps, at most max_delay_steps.  In index order every vehicle takes the smallest delay at
+        which it is never closer than the margin to a scheduled partner of smaller index; one that finds none gets status 1 and those below it are
+        scheduled as if it were absent.  Nothing but the call's own buffers is written: legal while other queries are in flight.
+        Returns a numpy record array of DELAY_DTYPE, one record per ticket: status, delay_steps, n_tried, blocker, t_start (the effective start),
+        t_block, s_block.
+        Raises PPError, with nothing launched, for everything conflicts() refuses (a ticket without a speed profile: run speed_profile first), a
+        negative max_delay_steps, or more than 2^20 lattice times and delay steps together."""
+        t = np.ascontiguousarray(tickets, dtype=np.uint64).reshape(-1)
+        return _deconflict(len(t), t_start, pairs, t_from, t_to, dt, margin, hold_before, hold_after, max_delay_steps,
+                           lambda ts, npairs, pr, dp, out: self.lib.pp_pipeline_deconflict(self.h, len(t), ptr(t), ptr(ts), npairs, ptr(pr), C.byref(dp), ptr(out)))
+
     def get_expanded_of(self, ticket):
         """expansion sequence (log_expansions=True) of a completed query polled with release=False"""
         slot = self.lib.pp_pipeline_slot_of(self.h, C.c_uint64(int(ticket)))
@@ -1184,6 +1206,40 @@ def _conflicts(n, t_start, pairs, t_from, t_to, dt, margin, hold_before, hold_af
     check(call(ts, n_pairs, pr, cp, xyt, plans, out))
     recs = (list(plans)[:n], list(out)[:n_pairs])
     return recs + ([xyt[i] for i in range(n)],) if poses else recs
+
+
+# pp_delay_result as a numpy record: a deconflict call returns one array of these, not one object per record
+DELAY_DTYPE = np.dtype([("status", np.int32), ("delay_steps", np.int32), ("n_tried", np.int32), ("blocker", np.int32), ("t_start", np.float64), ("t_block", np.float64),
+                        ("s_block", np.float64, (2,))])
+assert DELAY_DTYPE.itemsize == C.sizeof(DelayResult)
+
+
+def delay_levels(n, pairs):
+    """the level each of n vehicles is decided on by a deconflict call with the pair list `pairs` ([n_pairs, 2]; None: every pair): 0 without a pair
+    partner of smaller index, else one more than the highest level among those partners.  The call makes one kernel launch per level."""
+    if pairs is None:
+        return np.arange(n, dtype=np.int32)
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    below = [[] for _ in range(n)]
+    for lo, hi in zip(pr.min(axis=1).tolist(), pr.max(axis=1).tolist()):
+        below[hi].append(lo)
+    level = np.zeros(n, dtype=np.int32)
+    for i in range(n):
+        level[i] = max((level[j] + 1 for j in below[i]), default=0)
+    return level
+
+
+def _deconflict(n, t_start, pairs, t_from, t_to, dt, margin, hold_before, hold_after, max_delay_steps, call):
+    """the parameters, start times and pair list of a delay call, the call, its records as one numpy record array"""
+    dp = DelayParams(ConflictParams(float(t_from), float(t_to), float(dt), float(margin), int(hold_before), int(hold_after)), int(max_delay_steps), 0)
+    ts = _per_plan(t_start, n)
+    if ts is None and n:
+        raise ValueError("one start time per plan")
+    pr = None if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    n_pairs = n * (n - 1) // 2 if pr is None else len(pr)
+    out = np.zeros(max(n, 1), dtype=DELAY_DTYPE)
+    check(call(ts, n_pairs, pr, dp, out))
+    return out[:n].view(np.recarray)
 
 
 def _locate(n, poses, from_length, to_length, spacing, heading_weight, call):
