@@ -868,6 +868,64 @@ int pp_pipeline_deconflict(pp_pipeline* pipeline, int32_t n, const uint64_t* tic
  * is a pipeline's buffer set (pp_pipeline_deconflict knows which slots are held). */
 int pp_planner_deconflict(pp_planner* planner, int32_t n_queries, const double* t_start, int32_t n_pairs, const int32_t* pairs,
 	const pp_delay_params* params, pp_delay_result* results_host);
+/* ---- start delays that clear conflicts and tracked movers, by priority and ticket ----------------------------------------------------------------
+ * A person, a manually driven truck, a vehicle held by another pipeline: whatever moves without a plan of this holder is invisible to the delay
+ * call above, and a stamp reserves its space for all time.  This call is the delay call with fixed, unprioritised partners added: TRACKS, discs
+ * that move along timed waypoints.  Every vehicle gets the smallest start delay at which it is clear of the scheduled vehicles above it AND of
+ * every track.  With max_delay_steps == 0 and n_pairs == 0 it is the plain check: does this plan, on its timetable, hit a tracked mover, and when
+ * and where first?  With no tracks (tracks == NULL or n_tracks == 0) the delay records are the delay call's, byte for byte.  The definition is
+ * that of "start delays that clear conflicts" with the additions below; every expression is in double, in the order written.
+ *  Track position. At the lattice time tau = tau_m = (double)(k0 + m) * dt -- the bits the vehicles use -- track k with waypoints (t_j, x_j, y_j),
+ *           j = 0 .. W - 1, is absent for tau < t_0 or tau > t_{W-1}; the hold flags are the vehicles' only (a mover that stands is two
+ *           waypoints at one place).  Otherwise j is the largest index with t_j <= tau (binary search).  j == W - 1 gives (x_j, y_j).  Else
+ *           lam = (tau - t_j) / (t_{j+1} - t_j), x = x_j + lam * (x_{j+1} - x_j), and y likewise.  Tracks are never delayed: they are sampled
+ *           on the T columns of k0 .. k1 only (k_track_samples, one wave per track; one array per component, track-major, a NaN where absent).
+ *  Separation. Of vehicle i and track k at tau: the minimum over the vehicle's discs a (the conflict call's discs) of sqrt(dx dx + dy dy) -
+ *           ((double)r_a + R_k), (dx, dy) the disc's centre minus the track's position, R_k = radii[k].  CONFLICT iff separation < margin.
+ *  Rule.    A candidate d of vehicle i is rejected by a scheduled partner j < i as in the delay call, and by track k if at some m the vehicle
+ *           (its column m + D - d) and the track are both present in conflict.  In the key order a track is partner n + k: key = m * (n + M) +
+ *           partner, so blocker >= n names track blocker - n, and s_block[1] is then 0.0.  With M == 0 this is the delay call's key.  Levels,
+ *           n_tried, t_start and the statuses 1 and -1 are unchanged; tracks sit above every vehicle and need no level.  The kernel is
+ *           k_delay_level_tracks, launched once per level as k_delay_level is; n_pairs == 0 is one launch.
+ *  Records. track_results_host[i * M + k] describes vehicle i against track k at the vehicle's REPORTED candidate: d_i for status 0, D for status
+ *           1 (k_track_pairs, one wave per (vehicle, track), launched once behind the last level).  Counts, first conflict and min_separation
+ *           are the pair record's, with its two orders; s_first and s_min are the vehicle's arc lengths.  They are computed and copied only when
+ *           track_results_host is given and M > 0.
+ *  Cost.    O(n (D + 1) T M) separations at worst: every vehicle tries every candidate against every track at every lattice time.  The call has
+ *           no list of (vehicle, track) pairs and no broad phase; a caller with many tracks passes the ones that can matter.
+ *  - PP_ERR_INVALID, nothing launched, the holder usable as before, the message naming the first offender: everything the delay call refuses;
+ *    tracks->reserved != 0; n_tracks < 0 or > 2^16; NULL offsets, waypoints or radii with n_tracks > 0; offsets[0] != 0 or offsets not strictly
+ *    increasing; offsets[M] > 2^24; M * T > 2^26; a waypoint value that is not finite; times not strictly increasing within a track; a radius
+ *    that is not finite and >= 0.  n == 0 is PP_OK whatever the tracks.
+ *  - The holder owns, beside the delay call's buffers, the waypoints, offsets and radii as uploaded (24 bytes per waypoint row, 4 + 8 per
+ *    track), 16 bytes per track and lattice time, and 64 bytes per (vehicle, track), kept aside like the others when they have to grow beside
+ *    queries in flight. */
+typedef struct pp_track_set {
+	int32_t n_tracks;          /* M >= 0 */
+	int32_t reserved;          /* zero */
+	const int32_t* offsets;    /* host, [M + 1]: offsets[0] == 0, strictly increasing; track k owns waypoint rows offsets[k] .. offsets[k+1] - 1 (W_k >= 1) */
+	const double*  waypoints;  /* host, [offsets[M]][3]: (t, x, y), all finite, t strictly increasing within a track */
+	const double*  radii;      /* host, [M]: finite, >= 0 */
+} pp_track_set;              /* 32 bytes */
+typedef struct pp_track_result {   /* vehicle i against track k at the vehicle's REPORTED candidate */
+	int32_t status;        /* 0 no conflict; 1 conflict; 2 never both present; -1 the vehicle's delay status is -1 */
+	int32_t n_times;       /* lattice times at which both are present */
+	int32_t n_conflict;    /* of them, in conflict */
+	int32_t reserved;
+	double  t_first;       /* the first lattice time in conflict */
+	double  s_first;       /* the vehicle's arc length there */
+	double  min_separation;/* over the n_times times; +inf when n_times == 0 */
+	double  t_min;         /* the smallest lattice time at which it is taken */
+	double  s_min;         /* the vehicle's arc length there */
+	double  reserved1;     /* zero: the record is 64 bytes */
+} pp_track_result;        /* 64 bytes; for status 2 and -1 every field but status is zero, except min_separation = +inf for status 2; for status 0
+                             t_first and s_first are zero */
+int pp_pipeline_deconflict_tracks(pp_pipeline* pipeline, int32_t n, const uint64_t* tickets, const double* t_start /* [n], finite */, int32_t n_pairs,
+	const int32_t* pairs /* may be NULL */, const pp_delay_params* params, const pp_track_set* tracks /* NULL: M = 0 */,
+	pp_delay_result* results_host /* may be NULL */, pp_track_result* track_results_host /* may be NULL; [n][M] */);
+/* The same kernels over the first n_queries queries of the planner's last batch, as pp_planner_deconflict is to pp_pipeline_deconflict. */
+int pp_planner_deconflict_tracks(pp_planner* planner, int32_t n_queries, const double* t_start, int32_t n_pairs, const int32_t* pairs,
+	const pp_delay_params* params, const pp_track_set* tracks, pp_delay_result* results_host, pp_track_result* track_results_host);
 /* Diagnostics: waves of the search grid that are alive right now (a blocking device-to-host copy; -1 on error). */
 int pp_pipeline_alive_waves(pp_pipeline* pipeline);
 pp_planner* pp_pipeline_planner(pp_pipeline* pipeline);           /* the buffer set: set_nonholo_table, set_primitives, get_path(slot), ... */

@@ -153,6 +153,20 @@ class DelayResult(C.Structure):
                 ("s_block", C.c_double * 2)]
 
 
+class TrackSet(C.Structure):
+    """pp_track_set: M tracked movers for a deconflict_tracks call -- host pointers to offsets [M + 1] (int32, offsets[0] == 0, strictly increasing),
+    waypoints [offsets[M]][3] (t, x, y; t strictly increasing within a track) and radii [M] (>= 0); reserved is zero"""
+    _fields_ = [("n_tracks", C.c_int32), ("reserved", C.c_int32), ("offsets", C.c_void_p), ("waypoints", C.c_void_p), ("radii", C.c_void_p)]
+
+
+class TrackResult(C.Structure):
+    """pp_track_result: a vehicle against a track at the vehicle's reported candidate -- status 0 no conflict, 1 conflict, 2 never both present, -1 the
+    vehicle's delay status is -1; the lattice times both are present at and those in conflict; the first time in conflict with the vehicle's arc
+    length there; the smallest separation (+inf: never both present), the smallest time it is taken at and the vehicle's arc length there"""
+    _fields_ = [("status", C.c_int32), ("n_times", C.c_int32), ("n_conflict", C.c_int32), ("reserved", C.c_int32), ("t_first", C.c_double), ("s_first", C.c_double),
+                ("min_separation", C.c_double), ("t_min", C.c_double), ("s_min", C.c_double), ("reserved1", C.c_double)]
+
+
 class LocateResult(C.Structure):
     """pp_locate_result: status 0 located, 1 no sample in the window, -1 no plan, -4 path beyond the path capacity; the located point's edge
     (1 .. n_path - 1; 0 for a one-pose plan), travel direction (+1 / -1), arc length s, ratio on the edge and path pose; the vehicle's distance,
@@ -295,6 +309,8 @@ def load():
     L.pp_planner_conflicts.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.POINTER(ConflictParams), vp, vp, vp]
     L.pp_pipeline_deconflict.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, C.POINTER(DelayParams), vp]
     L.pp_planner_deconflict.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.POINTER(DelayParams), vp]
+    L.pp_pipeline_deconflict_tracks.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, C.POINTER(DelayParams), C.POINTER(TrackSet), vp, vp]
+    L.pp_planner_deconflict_tracks.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.POINTER(DelayParams), C.POINTER(TrackSet), vp, vp]
     L.pp_pipeline_timings.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.pp_pipeline_backlog.argtypes = [vp, vp, vp]
     L.pp_pipeline_planner.argtypes = [vp]

@@ -248,6 +248,35 @@ def build_delay_rule_test(verbose=True):
     return out
 
 
+def build_pipeline_deconflict_tracks_test(verbose=True):
+    """tests/cpp/test_pipeline_deconflict_tracks.cpp: DeconflictTracks(tickets, starts, tracks) of HybridAStarPipeline against a plain sequential loop over the poses
+    Conflicts returns and the tracks' waypoints (run on the GPU box)."""
+    build()
+    out = os.path.join(LIB_DIR, "test_pipeline_deconflict_tracks")
+    src = os.path.join(HERE, "..", "tests", "cpp", "test_pipeline_deconflict_tracks.cpp")
+    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", src, "-o", out, "-L" + LIB_DIR, "-lpphip", "-Wl,-rpath,$ORIGIN"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return out
+
+
+def build_track_rule_test(verbose=True):
+    """tests/cpp/test_track_rule.cpp: the waypoint search, the position of a track, the partner index of a track and the validation of a track set
+    (csrc/pp_track_rule.hpp) alone, on the CPU, under the address and undefined-behaviour sanitizers; without contraction, as the library is built."""
+    os.makedirs(LIB_DIR, exist_ok=True)
+    out = os.path.join(LIB_DIR, "test_track_rule")
+    src = os.path.join(HERE, "..", "tests", "cpp", "test_track_rule.cpp")
+    headers = [os.path.join(CSRC, f) for f in ("pp_track_rule.hpp", "pp_delay_rule.hpp", "pp_conflict_rule.hpp", "pp_speed_rule.hpp", "pp_stamp_rule.hpp")]
+    if os.path.exists(out) and os.path.getmtime(out) > max(os.path.getmtime(f) for f in [src] + headers):
+        return out
+    cmd = ["g++", "-std=c++17", "-g", "-O1", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC, src, "-o", out]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return out
+
+
 def build_ticket_table_test(verbose=True):
     """tests/cpp/test_ticket_table.cpp: the pipeline's slot and ticket bookkeeping (csrc/pp_ticket_table.hpp) alone, on the CPU, under the address and
     undefined-behaviour sanitizers."""
@@ -294,5 +323,7 @@ if __name__ == "__main__":
     print(build_conflict_rule_test())
     print(build_pipeline_deconflict_test())
     print(build_delay_rule_test())
+    print(build_pipeline_deconflict_tracks_test())
+    print(build_track_rule_test())
     print(build_ticket_table_test())
     print(build_row_test())

@@ -2,8 +2,8 @@
 // names their argument types) and in front of pp_planner and pp_pipeline, which both keep one buffer group per service.
 //
 // Finished plans (path records, Reeds-Shepp log, result record) are held by a batch planner, as queries 0 .. n-1 of its last batch, or by a pipeline, as
-// the slots of held tickets.  A service over them -- post-processing, re-validation, the stamp, the locate call, the speed profile, the conflict call, the delay call -- has one core (post_process_plans,
-// revalidate_plans, stamp_plans, locate_plans, speed_profile_plans, conflict_plans, deconflict_plans in pp_planner.hip) that takes a HeldPlans and goes through held_grow and held_run; its two extern "C"
+// the slots of held tickets.  A service over them -- post-processing, re-validation, the stamp, the locate call, the speed profile, the conflict call, the delay call without and with tracked movers -- has one core (post_process_plans,
+// revalidate_plans, stamp_plans, locate_plans, speed_profile_plans, conflict_plans, deconflict_plans, deconflict_tracks_plans in pp_planner.hip) that takes a HeldPlans and goes through held_grow and held_run; its two extern "C"
 // entries check what is the holder's own and describe the holder (batch_plans, pipe_plans).
 #pragma once
 
@@ -108,6 +108,20 @@ struct DelayGroup {
 	size_t listed = 0; // partners `partners` holds (4 bytes each)
 	pph::Dev<pp_delay_result> out;
 	size_t rows = 0; // records `out` holds
+};
+
+/// What the delay call with tracked movers adds to the delay call's buffers: the track set as uploaded (offsets, radii, waypoint rows), the tracks' positions on
+/// the lattice, one array per component and track-major (pp_tracks.hpp), and the (vehicle, track) records
+struct TrackGroup {
+	pph::Dev<int32_t> offsets;
+	pph::Dev<double> radii;
+	size_t tracks = 0; // tracks they hold (`offsets` one more)
+	pph::Dev<double> waypoints;
+	size_t rows = 0; // waypoint rows `waypoints` holds (24 bytes each)
+	pph::Dev<double> samples;
+	size_t doubles = 0; // doubles `samples` holds (16 bytes per track and lattice time)
+	pph::Dev<pp_track_result> out;
+	size_t records = 0; // records `out` holds
 };
 
 /// Buffers that hold `capacity` units are made to hold `wanted` ({buffer, bytes}; 0 bytes: the holder does not use it).  A holder that may not free now

@@ -210,6 +210,7 @@ struct pp_pipeline {
 	SpeedGroup speed;
 	ConflictGroup conflict;
 	DelayGroup delay;
+	TrackGroup track;
 	std::vector<pph::DeviceMem> heldParked; // their buffers outgrown while queries were in flight: hipFree waits for the whole device (the persistent grid
 	                                        // included), so they are kept until a call finds nothing in flight (or the pipeline goes): held_grow
 	int nWf = 2;      // wavefront streams in use: consecutive submissions' launches overlap (the tail of one under the head of the next)
@@ -1232,6 +1233,28 @@ int pp_pipeline_deconflict(pp_pipeline* P, int32_t n, const uint64_t* tickets, c
 	if (int rc = conflict_profiles(h, P->speed, t_start, lattice, plans))
 		return rc;
 	return deconflict_plans(h, P->conflict, P->delay, P->speed, plans, lattice, params ? params->max_delay_steps : 0, n_pairs, pairs, results_host);
+}
+
+/// ... that also clear tracked movers (include/pp_hip.h; deconflict_tracks_plans): legal beside queries in flight
+int pp_pipeline_deconflict_tracks(pp_pipeline* P, int32_t n, const uint64_t* tickets, const double* t_start, int32_t n_pairs, const int32_t* pairs, const pp_delay_params* params,
+	const pp_track_set* tracks, pp_delay_result* results_host, pp_track_result* track_results_host)
+{
+	HeldPlans h;
+	if (int rc = pipe_plans(P, n, tickets, h))
+		return rc;
+	ConflictLattice lattice;
+	if (int rc = delay_check(h, t_start, n_pairs, pairs, params, lattice))
+		return rc;
+	if (h.n == 0)
+		return PP_OK; // (whatever the tracks)
+	if (int rc = tracks_check(tracks, lattice.T))
+		return rc;
+	if (int rc = pipe_resolve(P, n, tickets, "scheduled", true, h.slots))
+		return rc;
+	std::vector<ConflictArg> plans;
+	if (int rc = conflict_profiles(h, P->speed, t_start, lattice, plans))
+		return rc;
+	return deconflict_tracks_plans(h, P->conflict, P->delay, P->track, P->speed, plans, lattice, params->max_delay_steps, n_pairs, pairs, tracks, results_host, track_results_host);
 }
 
 /// Launch durations seen so far (HIP events on the launching streams; harvested by pp_pipeline_poll) and reset.  Wavefront: one launch per

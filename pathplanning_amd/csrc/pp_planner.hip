@@ -22,6 +22,7 @@
 #include "pp_speed_rule.hpp"
 #include "pp_conflict_rule.hpp"
 #include "pp_delay_rule.hpp"
+#include "pp_track_rule.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -314,6 +315,8 @@ struct PipeView {
 #include "pp_conflicts.hpp"
 // start delays that clear those conflicts, by priority (one wave per vehicle of a level, one launch per level; reads the trajectory layout of the file above)
 #include "pp_deconflict.hpp"
+// ... and tracked movers beside them (one wave per track, per vehicle of a level, per (vehicle, track); the same trajectory layout)
+#include "pp_tracks.hpp"
 
 } // namespace
 
@@ -381,6 +384,7 @@ struct pp_planner {
 	SpeedGroup speed;
 	ConflictGroup conflict;
 	DelayGroup delay;
+	TrackGroup track;
 };
 
 namespace {
@@ -499,6 +503,32 @@ hipError_t launch_delay_level(hipStream_t s, const Footprint& discs, const Confl
 {
 	hipLaunchKernelGGL(k_delay_level, dim3((unsigned)(count > 0 ? count : 1)), dim3(kDelayLanes), 0, s, discs, lattice, maxDelay, plans, count, membersDev, offsetsDev, partnersDev,
 		argsDev, trajDev, plansDev, delaysDev, outDev);
+	return hipGetLastError();
+}
+
+/// k_track_samples over the tracks of `view`
+hipError_t launch_track_samples(hipStream_t s, const ConflictLattice& lattice, const TrackView& view)
+{
+	hipLaunchKernelGGL(k_track_samples, dim3((unsigned)(view.M > 0 ? view.M : 1)), dim3(kTrackLanes), 0, s, lattice, view);
+	return hipGetLastError();
+}
+
+/// k_delay_level_tracks over the `count` vehicles `membersDev` of one level: launch_delay_level's arguments, and the tracks' samples and radii
+hipError_t launch_delay_level_tracks(hipStream_t s, const Footprint& discs, const ConflictLattice& lattice, int maxDelay, int plans, int count, const int32_t* membersDev,
+	const int32_t* offsetsDev, const int32_t* partnersDev, const ConflictArg* argsDev, const double* trajDev, const pp_trajectory_result* plansDev, const TrackView& view,
+	int32_t* delaysDev, pp_delay_result* outDev)
+{
+	hipLaunchKernelGGL(k_delay_level_tracks, dim3((unsigned)(count > 0 ? count : 1)), dim3(kDelayLanes), 0, s, discs, lattice, maxDelay, plans, count, membersDev, offsetsDev,
+		partnersDev, argsDev, trajDev, plansDev, view.M, (const double*)view.samples, view.radii, delaysDev, outDev);
+	return hipGetLastError();
+}
+
+/// k_track_pairs over every (vehicle, track) of `plans` vehicles and the tracks of `view`, behind the last level
+hipError_t launch_track_pairs(hipStream_t s, const Footprint& discs, const ConflictLattice& lattice, int maxDelay, int plans, const double* trajDev,
+	const pp_delay_result* decidedDev, const TrackView& view, pp_track_result* outDev)
+{
+	hipLaunchKernelGGL(k_track_pairs, dim3((unsigned)((size_t)plans * (size_t)view.M)), dim3(kTrackLanes), 0, s, discs, lattice, maxDelay, plans, view.M, trajDev, decidedDev,
+		(const double*)view.samples, view.radii, outDev);
 	return hipGetLastError();
 }
 
@@ -878,6 +908,36 @@ int delay_check(const HeldPlans& h, const double* t_start, int n_pairs, const in
 	return PP_OK;
 }
 
+/// The track set of a delay call over T lattice times (pp_planner_deconflict_tracks, pp_pipeline_deconflict_tracks): ppk::validate's verdict as a refusal
+/// that names the first offender.  NULL is no track.
+int tracks_check(const pp_track_set* tracks, int64_t T)
+{
+	if (!tracks)
+		return PP_OK;
+	const ppk::Verdict v = ppk::validate(tracks->n_tracks, tracks->reserved, tracks->offsets, tracks->waypoints, tracks->radii, T);
+	if (v.fault == ppk::kValid)
+		return PP_OK;
+	const std::string M = std::to_string(tracks->n_tracks), at = std::to_string(v.index), of = " of track " + std::to_string(v.track);
+	switch (v.fault) {
+	case ppk::kReserved: set_error("invalid arguments (the track set's reserved field is zero)"); break;
+	case ppk::kCount: set_error("invalid arguments (0 <= n_tracks <= " + std::to_string(ppk::kMaxTracks) + ", got " + M + ")"); break;
+	case ppk::kNullOffsets: set_error("invalid arguments (null offsets with n_tracks = " + M + ")"); break;
+	case ppk::kNullWaypoints: set_error("invalid arguments (null waypoints with n_tracks = " + M + ")"); break;
+	case ppk::kNullRadii: set_error("invalid arguments (null radii with n_tracks = " + M + ")"); break;
+	case ppk::kFirstOffset: set_error("invalid arguments (the track set's offsets[0] is 0, got " + std::to_string(tracks->offsets[0]) + ")"); break;
+	case ppk::kOffsetOrder: set_error("track " + at + " owns no waypoint: offsets are strictly increasing, got offsets[" + at + "] = " + std::to_string(tracks->offsets[v.index]) +
+			" and offsets[" + std::to_string(v.index + 1) + "] = " + std::to_string(tracks->offsets[v.index + 1])); break;
+	case ppk::kWaypointCount: set_error("invalid arguments (the track set holds offsets[n_tracks] = " + std::to_string(tracks->offsets[tracks->n_tracks]) +
+			" waypoints: at most " + std::to_string(ppk::kMaxWaypoints) + ")"); break;
+	case ppk::kSampleCount: set_error("invalid arguments (n_tracks * T = " + std::to_string((int64_t)tracks->n_tracks * T) + " track samples: at most " +
+			std::to_string(ppk::kMaxSamples) + ")"); break;
+	case ppk::kWaypointValue: set_error("waypoint " + at + of + " holds a value that is not finite"); break;
+	case ppk::kWaypointOrder: set_error("waypoint " + at + of + " has a time that is not above the one before it: times are strictly increasing within a track"); break;
+	default: set_error("track " + at + " has a radius that is not finite and >= 0"); break;
+	}
+	return PP_ERR_INVALID;
+}
+
 /// ... and what the holder remembers of its last speed-profile call for the plans of h: their rows, into `plans`, and the call's stride and limits, into `lattice`
 int conflict_profiles(const HeldPlans& h, const SpeedGroup& g, const double* t_start, ConflictLattice& lattice, std::vector<ConflictArg>& plans)
 {
@@ -1141,6 +1201,79 @@ int deconflict_plans(const HeldPlans& h, ConflictGroup& c, DelayGroup& g, const 
 		}))
 		return rc;
 	std::copy(recs.begin(), recs.end(), results_host);
+	return PP_OK;
+}
+
+/// Start delays of the plans of h that also clear the movers of `tracks` (tracks_check's; NULL or n_tracks == 0: none).  deconflict_plans with three additions on the
+/// holder's stream: the track set goes up and k_track_samples samples it on the lattice's T times in front of the levels; every level is k_delay_level_tracks; and
+/// for a caller that wants the (vehicle, track) records k_track_pairs runs once behind the last level.  held_run synchronises the stream once.
+int deconflict_tracks_plans(const HeldPlans& h, ConflictGroup& c, DelayGroup& g, TrackGroup& t, const SpeedGroup& speed, const std::vector<ConflictArg>& plans,
+	const ConflictLattice& lattice, int D, int n_pairs, const int32_t* pairs, const pp_track_set* tracks, pp_delay_result* results_host, pp_track_result* track_results_host)
+{
+	if (h.n == 0)
+		return PP_OK;
+	pp_planner* const pl = h.pl;
+	PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
+	const size_t n = (size_t)h.n, columns = (size_t)lattice.T + (size_t)D, nListed = (size_t)n_pairs, component = n * columns;
+	const size_t M = tracks ? (size_t)tracks->n_tracks : 0, nRows = M ? (size_t)tracks->offsets[M] : 0, nSamples = M * (size_t)lattice.T;
+	const size_t nRecords = track_results_host ? n * M : 0;
+	if (nRecords > 0x7FFFFFFFull) {
+		set_error("invalid arguments (n * n_tracks = " + std::to_string(nRecords) + " track records: at most 2^31 - 1)");
+		return PP_ERR_INVALID;
+	}
+	std::vector<int32_t> offsets(n + 1), cursor(n), list(nListed), level(n), members(n);
+	ppy::partner_offsets(h.n, n_pairs, pairs, offsets.data());
+	ppy::partner_list(h.n, n_pairs, pairs, offsets.data(), cursor.data(), list.data());
+	const int nLevels = ppy::levels(h.n, offsets.data(), list.data(), level.data());
+	std::vector<int32_t> first((size_t)nLevels + 1);
+	ppy::members_by_level(h.n, nLevels, level.data(), first.data(), members.data());
+	PP_HIP_TRY(held_grow(h, c.doubles, component * kTrajectoryComponents, { { &c.traj, component * kTrajectoryComponents * 8 } }));
+	PP_HIP_TRY(held_grow(h, g.vehicles, n, { { &g.members, n * 4 }, { &g.offsets, (n + 1) * 4 }, { &g.delays, n * 4 } }));
+	if (nListed)
+		PP_HIP_TRY(held_grow(h, g.listed, nListed, { { &g.partners, nListed * 4 } }));
+	PP_HIP_TRY(held_grow(h, g.rows, n, { { &g.out, n * sizeof(pp_delay_result) } }));
+	PP_HIP_TRY(held_grow(h, t.tracks, M, { { &t.offsets, (M + 1) * 4 }, { &t.radii, M * 8 } }));
+	PP_HIP_TRY(held_grow(h, t.rows, nRows, { { &t.waypoints, nRows * 24 } }));
+	PP_HIP_TRY(held_grow(h, t.doubles, nSamples * 2, { { &t.samples, nSamples * 16 } }));
+	PP_HIP_TRY(held_grow(h, t.records, nRecords, { { &t.out, nRecords * sizeof(pp_track_result) } }));
+	const SearchArgs args = held_args(h, h.ownView);
+	const Footprint discs = stamp_discs(h.footprint, pl->map);
+	ConflictLattice extended = lattice;
+	extended.k0 = lattice.k0 - D;
+	extended.T = lattice.T + D;
+	const TrackView view { (int)M, t.offsets.get(), t.waypoints.get(), t.radii.get(), t.samples.get() };
+	std::vector<pp_delay_result> recs(results_host ? n : 0);
+	std::vector<pp_track_result> trackRecs(nRecords);
+	if (int rc = held_run(h, c.rec, plans, (pp_trajectory_result*)nullptr, [&](const int32_t* slotsDev) {
+			hipError_t e = hipMemcpyAsync(g.members, members.data(), n * 4, hipMemcpyHostToDevice, h.stream);
+			if (e == hipSuccess)
+				e = hipMemcpyAsync(g.offsets, offsets.data(), (n + 1) * 4, hipMemcpyHostToDevice, h.stream);
+			if (e == hipSuccess && nListed)
+				e = hipMemcpyAsync(g.partners, list.data(), nListed * 4, hipMemcpyHostToDevice, h.stream);
+			if (e == hipSuccess && M)
+				e = hipMemcpyAsync(t.offsets, tracks->offsets, (M + 1) * 4, hipMemcpyHostToDevice, h.stream);
+			if (e == hipSuccess && M)
+				e = hipMemcpyAsync(t.radii, tracks->radii, M * 8, hipMemcpyHostToDevice, h.stream);
+			if (e == hipSuccess && M)
+				e = hipMemcpyAsync(t.waypoints, tracks->waypoints, nRows * 24, hipMemcpyHostToDevice, h.stream);
+			if (e == hipSuccess && M)
+				e = launch_track_samples(h.stream, lattice, view);
+			if (e == hipSuccess)
+				e = launch_trajectory(h.stream, args, extended, discs.anyOffset != 0, h.n, slotsDev, c.rec.args.get(), pl, speed.rows.get(), c.traj.get(), c.rec.out.get());
+			for (int l = 0; l < nLevels && e == hipSuccess; l++)
+				e = launch_delay_level_tracks(h.stream, discs, lattice, D, h.n, first[(size_t)l + 1] - first[(size_t)l], g.members.get() + first[(size_t)l], g.offsets.get(),
+					g.partners.get(), c.rec.args.get(), c.traj.get(), c.rec.out.get(), view, g.delays.get(), g.out.get());
+			if (e == hipSuccess && nRecords)
+				e = launch_track_pairs(h.stream, discs, lattice, D, h.n, c.traj.get(), g.out.get(), view, t.out.get());
+			if (e == hipSuccess && !recs.empty())
+				e = hipMemcpyAsync(recs.data(), g.out, n * sizeof(pp_delay_result), hipMemcpyDeviceToHost, h.stream);
+			if (e == hipSuccess && nRecords)
+				e = hipMemcpyAsync(trackRecs.data(), t.out, nRecords * sizeof(pp_track_result), hipMemcpyDeviceToHost, h.stream);
+			return e;
+		}))
+		return rc;
+	std::copy(recs.begin(), recs.end(), results_host);
+	std::copy(trackRecs.begin(), trackRecs.end(), track_results_host);
 	return PP_OK;
 }
 
@@ -2006,6 +2139,26 @@ int pp_planner_deconflict(pp_planner* planner, int32_t n_queries, const double* 
 	if (int rc = conflict_profiles(h, planner->speed, t_start, lattice, plans))
 		return rc;
 	return deconflict_plans(h, planner->conflict, planner->delay, planner->speed, plans, lattice, params ? params->max_delay_steps : 0, n_pairs, pairs, results_host);
+}
+
+int pp_planner_deconflict_tracks(pp_planner* planner, int32_t n_queries, const double* t_start, int32_t n_pairs, const int32_t* pairs, const pp_delay_params* params,
+	const pp_track_set* tracks, pp_delay_result* results_host, pp_track_result* track_results_host)
+{
+	if (int rc = batch_check(planner, n_queries, "pp_pipeline_deconflict_tracks schedules its held tickets"))
+		return rc;
+	const HeldPlans h = batch_plans(planner, n_queries);
+	ConflictLattice lattice;
+	if (int rc = delay_check(h, t_start, n_pairs, pairs, params, lattice))
+		return rc;
+	if (h.n == 0)
+		return PP_OK; // (whatever the tracks)
+	if (int rc = tracks_check(tracks, lattice.T))
+		return rc;
+	std::vector<ConflictArg> plans;
+	if (int rc = conflict_profiles(h, planner->speed, t_start, lattice, plans))
+		return rc;
+	return deconflict_tracks_plans(h, planner->conflict, planner->delay, planner->track, planner->speed, plans, lattice, params->max_delay_steps, n_pairs, pairs, tracks,
+		results_host, track_results_host);
 }
 
 int pp_planner_locate(pp_planner* planner, int32_t n_queries, const double* poses_host, const double* from_length, const double* to_length, const pp_locate_params* params,

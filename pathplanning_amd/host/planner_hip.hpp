@@ -1530,6 +1530,91 @@ public:
 		}
 		return out;
 	}
+	/// A tracked mover for DeconflictTracks: a disc of `radius` that moves along the timed waypoints (t, x, y), t strictly increasing, on straight lines
+	/// between them; absent before the first time and behind the last
+	struct Track {
+		struct Waypoint {
+			double t, x, y;
+		};
+		double radius = 0.0;
+		std::vector<Waypoint> waypoints;
+	};
+	/// What DeconflictTracks says about one held plan against one track at the plan's reported candidate (pp_track_result)
+	struct TrackConflict {
+		enum class Status { Free = 0, Conflict = 1, NeverBothPresent = 2, NoProfile = -1 };
+		Status status = Status::NoProfile;
+		int numTimes = 0, numConflict = 0;
+		double tFirst = 0.0, sFirst = 0.0;
+		double minSeparation = 0.0, tMin = 0.0, sMin = 0.0;
+	};
+	struct DelayedWithTracks {
+		std::vector<Delay> plans;                       // a blocker >= tickets.size() names track blocker - tickets.size(); sBlock[1] is then 0
+		std::vector<std::vector<TrackConflict>> tracks; // [ticket][track]; empty without details
+	};
+	/// Deconflict with tracked movers (pp_pipeline_deconflict_tracks; include/pp_hip.h has the definition): every vehicle takes the smallest delay at which
+	/// it stays clear of its scheduled partners of smaller index AND of every track; tracks are never delayed.  With maxDelaySteps == 0 and no pairs it is
+	/// the plain check of each plan against the movers.  Without tracks the plans' records are Deconflict's.
+	DelayedWithTracks DeconflictTracks(const std::vector<uint64_t>& tickets, const std::vector<double>& tStart, const std::vector<Track>& tracks,
+		const std::vector<std::pair<int, int>>& pairs, bool allPairs, const ConflictHorizon& horizon, int maxDelaySteps, bool details = true)
+	{
+		for (uint64_t t : tickets)
+			HeldOf(t); // (throws for a ticket that is not held)
+		const size_t n = tickets.size(), M = tracks.size();
+		if (tStart.size() != n)
+			throw std::invalid_argument("DeconflictTracks: tStart holds one entry per ticket");
+		DelayedWithTracks out;
+		if (!m_pipe || n == 0)
+			return out;
+		const pp_delay_params dp { { horizon.tFrom, horizon.tTo, horizon.dt, horizon.margin, horizon.holdBefore ? 1 : 0, horizon.holdAfter ? 1 : 0 }, maxDelaySteps, 0 };
+		std::vector<int32_t> list;
+		for (const auto& p : pairs) {
+			list.push_back(p.first);
+			list.push_back(p.second);
+		}
+		const size_t nPairs = allPairs ? n * (n - 1) / 2 : pairs.size();
+		if (!allPairs && list.empty())
+			list.resize(2); // (an empty list that exists: a null one would mean every pair)
+		std::vector<int32_t> offsets { 0 };
+		std::vector<double> waypoints, radii;
+		for (const Track& k : tracks) {
+			for (const Track::Waypoint& w : k.waypoints)
+				waypoints.insert(waypoints.end(), { w.t, w.x, w.y });
+			offsets.push_back((int32_t)(waypoints.size() / 3));
+			radii.push_back(k.radius);
+		}
+		const pp_track_set set { (int32_t)M, 0, offsets.data(), waypoints.data(), radii.data() };
+		std::vector<pp_delay_result> r(n);
+		std::vector<pp_track_result> c(details ? n * M : 0);
+		ppCheck(pp_pipeline_deconflict_tracks(m_pipe, (int32_t)n, tickets.data(), tStart.data(), (int32_t)nPairs, allPairs ? nullptr : list.data(), &dp, M ? &set : nullptr, r.data(),
+			c.empty() ? nullptr : c.data()));
+		out.plans.resize(n);
+		for (size_t i = 0; i < n; i++) {
+			Delay& o = out.plans[i];
+			o.status = (Delay::Status)r[i].status;
+			o.delaySteps = r[i].delay_steps;
+			o.numTried = r[i].n_tried;
+			o.blocker = r[i].blocker;
+			o.tStart = r[i].t_start;
+			o.tBlock = r[i].t_block;
+			o.sBlock[0] = r[i].s_block[0];
+			o.sBlock[1] = r[i].s_block[1];
+		}
+		if (details) {
+			out.tracks.assign(n, std::vector<TrackConflict>(M));
+			for (size_t p = 0; p < n * M; p++) {
+				TrackConflict& o = out.tracks[p / M][p % M];
+				o.status = (TrackConflict::Status)c[p].status;
+				o.numTimes = c[p].n_times;
+				o.numConflict = c[p].n_conflict;
+				o.tFirst = c[p].t_first;
+				o.sFirst = c[p].s_first;
+				o.minSeparation = c[p].min_separation;
+				o.tMin = c[p].t_min;
+				o.sMin = c[p].s_min;
+			}
+		}
+		return out;
+	}
 	/// HybridAStar::GetPath() of a held query: after PostProcess the sampled and, when the smoother succeeded, smoothed path; before it the
 	/// graph-search nodes
 	std::vector<Pose2d> GetPath(uint64_t ticket) const

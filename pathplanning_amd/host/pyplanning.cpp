@@ -520,6 +520,46 @@ PYBIND11_MODULE(pyplanning, m)
 			"status 0 scheduled with the effective start t_start, 1 no delay is clear (those below ignore it), -1 no speed profile.",
 			py::arg("tickets"), py::arg("t_start"), py::arg("pairs") = py::none(), py::arg("t_from") = 0.0, py::arg("t_to") = 60.0, py::arg("dt") = 0.1, py::arg("margin") = 0.0,
 			py::arg("hold_before") = false, py::arg("hold_after") = false, py::arg("max_delay_steps") = 0)
+		.def("deconflict_tracks",
+			[](HybridAStarPipeline& h, const std::vector<uint64_t>& tickets, const std::vector<double>& tStart,
+				const std::vector<std::pair<double, std::vector<std::tuple<double, double, double>>>>& tracks, const py::object& pairs, double tFrom, double tTo, double dt, double margin,
+				bool holdBefore, bool holdAfter, int maxDelaySteps, bool details) {
+				HybridAStarPipeline::ConflictHorizon horizon;
+				horizon.tFrom = tFrom;
+				horizon.tTo = tTo;
+				horizon.dt = dt;
+				horizon.margin = margin;
+				horizon.holdBefore = holdBefore;
+				horizon.holdAfter = holdAfter;
+				std::vector<HybridAStarPipeline::Track> movers;
+				for (const auto& k : tracks) {
+					HybridAStarPipeline::Track t;
+					t.radius = k.first;
+					for (const auto& w : k.second)
+						t.waypoints.push_back({ std::get<0>(w), std::get<1>(w), std::get<2>(w) });
+					movers.push_back(std::move(t));
+				}
+				const bool all = pairs.is_none();
+				const auto r = h.DeconflictTracks(tickets, tStart, movers, all ? std::vector<std::pair<int, int>>() : pairs.cast<std::vector<std::pair<int, int>>>(), all, horizon,
+					maxDelaySteps, details);
+				py::list out, found;
+				for (const auto& d : r.plans)
+					out.append(py::make_tuple((int)d.status, d.delaySteps, d.numTried, d.blocker, d.tStart, d.tBlock, py::make_tuple(d.sBlock[0], d.sBlock[1])));
+				for (const auto& row : r.tracks) {
+					py::list one;
+					for (const auto& c : row)
+						one.append(py::make_tuple((int)c.status, c.numTimes, c.numConflict, c.tFirst, c.sFirst, c.minSeparation, c.tMin, c.sMin));
+					found.append(one);
+				}
+				return details ? py::object(py::make_tuple(out, found)) : py::object(out);
+			},
+			"deconflict with tracked movers: every vehicle takes the smallest start delay at which it is clear of the scheduled vehicles above it and of every track.  "
+			"tracks: a list of (radius, [(t, x, y), ...]), discs that move along timed waypoints on straight lines, absent before the first and behind the last time, never "
+			"delayed; the other arguments are deconflict's (pairs=[] and max_delay_steps=0: the plain check of each plan against the movers).  Returns per ticket deconflict's "
+			"tuple -- a blocker >= len(tickets) names track blocker - len(tickets) -- and, with details, per ticket and track (status, n_times, n_conflict, t_first, s_first, "
+			"min_separation, t_min, s_min) at the vehicle's reported candidate.",
+			py::arg("tickets"), py::arg("t_start"), py::arg("tracks"), py::arg("pairs") = py::none(), py::arg("t_from") = 0.0, py::arg("t_to") = 60.0, py::arg("dt") = 0.1,
+			py::arg("margin") = 0.0, py::arg("hold_before") = false, py::arg("hold_after") = false, py::arg("max_delay_steps") = 0, py::arg("details") = true)
 		.def("get_path", &HybridAStarPipeline::GetPath, py::arg("ticket"))
 		.def("get_graph_search_path", &HybridAStarPipeline::GetGraphSearchPath, py::arg("ticket"))
 		.def("get_smoothing_status", &HybridAStarPipeline::GetSmoothingStatus, py::arg("ticket"))

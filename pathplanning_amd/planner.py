@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (RS_PATH_DTYPE, ConflictParams, ConflictResult, DelayParams, DelayResult, FootprintDisc, HybridParams, LocateParams, LocateResult, MapDesc, PostResult, QueryResult, RevalidateResult,
-                   SmootherParams, SpeedProfileParams, SpeedProfileResult, StampParams, StampResult, TrajectoryResult, check, ptr)
+                   SmootherParams, SpeedProfileParams, SpeedProfileResult, StampParams, StampResult, TrackResult, TrackSet, TrajectoryResult, check, ptr)
 
 
 class Status:
@@ -722,6 +722,16 @@ class HybridAStarBatch:
         return _deconflict(n, t_start, pairs, t_from, t_to, dt, margin, hold_before, hold_after, max_delay_steps,
                            lambda ts, npairs, pr, dp, out: self.lib.pp_planner_deconflict(self.h, n, ptr(ts), npairs, ptr(pr), C.byref(dp), ptr(out)))
 
+    def deconflict_tracks(self, t_start, tracks, n_queries=None, pairs=None, t_from=0.0, t_to=60.0, dt=0.1, margin=0.0, hold_before=False, hold_after=False, max_delay_steps=0,
+                          details=True):
+        """Start delays that clear the conflicts between the plans of the first n queries of the last batch and with the tracked movers `tracks`:
+        pp_planner_deconflict_tracks, the batch form of HybridAStarPipeline.deconflict_tracks, with the same arguments (pair indices are query indices) and
+        return value."""
+        n = len(self._results) if n_queries is None else int(n_queries)
+        return _deconflict_tracks(n, t_start, tracks, pairs, t_from, t_to, dt, margin, hold_before, hold_after, max_delay_steps, details,
+                                  lambda ts, npairs, pr, dp, tk, out, rec: self.lib.pp_planner_deconflict_tracks(self.h, n, ptr(ts), npairs, ptr(pr), C.byref(dp), tk, ptr(out),
+                                                                                                                 ptr(rec)))
+
     def certify_lattice(self, q):
         """SURVEY 7.3 H2 as a contract (pp_planner_certify_lattice): created nodes and logged lattice-line children of query q recomputed on
         the host with glibc; returns (checked, cell mismatches, unverified events, largest pose difference).  mismatches == unverified == 0
@@ -1099,6 +1109,24 @@ class HybridAStarPipeline:
         return _deconflict(len(t), t_start, pairs, t_from, t_to, dt, margin, hold_before, hold_after, max_delay_steps,
                            lambda ts, npairs, pr, dp, out: self.lib.pp_pipeline_deconflict(self.h, len(t), ptr(t), ptr(ts), npairs, ptr(pr), C.byref(dp), ptr(out)))
 
+    def deconflict_tracks(self, tickets, t_start, tracks, pairs=None, t_from=0.0, t_to=60.0, dt=0.1, margin=0.0, hold_before=False, hold_after=False, max_delay_steps=0,
+                          details=True):
+        """deconflict() with tracked movers: every vehicle of the completed, HELD queries `tickets` gets the smallest start delay at which it is clear of
+        the scheduled vehicles above it AND of every track.  pp_pipeline_deconflict_tracks, whose definition is in include/pp_hip.h.  `tracks` is a
+        sequence of (radius, waypoints [W, 3]) -- a disc of that radius moving along the rows (t, x, y), t strictly increasing, on straight lines
+        between them, absent before its first and behind its last time -- or None for none.  Tracks are never delayed and outrank every vehicle.  With
+        max_delay_steps=0 and pairs=[] the call is the plain check of each plan against the movers.  The remaining arguments are deconflict()'s.
+        Returns the numpy record array of DELAY_DTYPE -- a blocker >= len(tickets) names track blocker - len(tickets), and s_block[1] is then 0 -- and, with
+        details, an [n, M] record array of TRACK_DTYPE: every vehicle against every track at the vehicle's reported candidate (its delay; for status 1
+        the largest delay tried).  Without tracks the delay records are deconflict()'s bytes.
+        Raises PPError, with nothing launched, for everything deconflict() refuses and for a track set outside its domain (more than 2^16 tracks, 2^24
+        waypoints or 2^26 track samples, a value that is not finite, times that do not increase, a negative radius); ValueError for a track whose
+        waypoints are not [W, 3] with W >= 1."""
+        t = np.ascontiguousarray(tickets, dtype=np.uint64).reshape(-1)
+        return _deconflict_tracks(len(t), t_start, tracks, pairs, t_from, t_to, dt, margin, hold_before, hold_after, max_delay_steps, details,
+                                  lambda ts, npairs, pr, dp, tk, out, rec: self.lib.pp_pipeline_deconflict_tracks(self.h, len(t), ptr(t), ptr(ts), npairs, ptr(pr), C.byref(dp), tk,
+                                                                                                                  ptr(out), ptr(rec)))
+
     def get_expanded_of(self, ticket):
         """expansion sequence (log_expansions=True) of a completed query polled with release=False"""
         slot = self.lib.pp_pipeline_slot_of(self.h, C.c_uint64(int(ticket)))
@@ -1240,6 +1268,45 @@ def _deconflict(n, t_start, pairs, t_from, t_to, dt, margin, hold_before, hold_a
     out = np.zeros(max(n, 1), dtype=DELAY_DTYPE)
     check(call(ts, n_pairs, pr, dp, out))
     return out[:n].view(np.recarray)
+
+
+# pp_track_result as a numpy record: a deconflict_tracks call returns an [n, M] array of these
+TRACK_DTYPE = np.dtype([("status", np.int32), ("n_times", np.int32), ("n_conflict", np.int32), ("reserved", np.int32), ("t_first", np.float64), ("s_first", np.float64),
+                        ("min_separation", np.float64), ("t_min", np.float64), ("s_min", np.float64), ("reserved1", np.float64)])
+assert TRACK_DTYPE.itemsize == C.sizeof(TrackResult)
+
+
+def track_set(tracks):
+    """(TrackSet, the arrays it points into) of a sequence of (radius, waypoints [W, 3]); None: no track.  The arrays must outlive the call."""
+    tracks = [] if tracks is None else list(tracks)
+    offsets, rows, radii = [0], [], []
+    for k, (radius, waypoints) in enumerate(tracks):
+        w = np.asarray(waypoints, dtype=np.float64)
+        if w.ndim != 2 or w.shape[1] != 3 or len(w) < 1:
+            raise ValueError("track %d: waypoints are [W, 3] rows (t, x, y) with W >= 1, got shape %s" % (k, w.shape))
+        rows.append(w)
+        offsets.append(offsets[-1] + len(w))
+        radii.append(float(radius))
+    keep = (np.array(offsets, dtype=np.int32), np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 3))), np.array(radii, dtype=np.float64))
+    return TrackSet(len(tracks), 0, *(a.ctypes.data for a in keep)), keep
+
+
+def _deconflict_tracks(n, t_start, tracks, pairs, t_from, t_to, dt, margin, hold_before, hold_after, max_delay_steps, details, call):
+    """the parameters, start times, pair list and track set of a delay call with tracked movers, the call, its records as numpy record arrays"""
+    dp = DelayParams(ConflictParams(float(t_from), float(t_to), float(dt), float(margin), int(hold_before), int(hold_after)), int(max_delay_steps), 0)
+    ts = _per_plan(t_start, n)
+    if ts is None and n:
+        raise ValueError("one start time per plan")
+    pr = None if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    n_pairs = n * (n - 1) // 2 if pr is None else len(pr)
+    tk, keep = (None, None) if tracks is None else track_set(tracks)
+    M = 0 if tk is None else tk.n_tracks
+    out = np.zeros(max(n, 1), dtype=DELAY_DTYPE)
+    rec = np.zeros((n, M), dtype=TRACK_DTYPE) if details else None
+    check(call(ts, n_pairs, pr, dp, None if tk is None else C.byref(tk), out, rec if rec is not None and rec.size else None))
+    del keep
+    out = out[:n].view(np.recarray)
+    return (out, rec.view(np.recarray)) if details else out
 
 
 def _locate(n, poses, from_length, to_length, spacing, heading_weight, call):
