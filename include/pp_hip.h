@@ -926,6 +926,54 @@ int pp_pipeline_deconflict_tracks(pp_pipeline* pipeline, int32_t n, const uint64
 /* The same kernels over the first n_queries queries of the planner's last batch, as pp_planner_deconflict is to pp_pipeline_deconflict. */
 int pp_planner_deconflict_tracks(pp_planner* planner, int32_t n_queries, const double* t_start, int32_t n_pairs, const int32_t* pairs,
 	const pp_delay_params* params, const pp_track_set* tracks, pp_delay_result* results_host, pp_track_result* track_results_host);
+/* ---- the pairs that can meet, by a space-time broad phase -----------------------------------------------------------------------------------------
+ * The conflict call and the two delay calls take a pair list.  NULL lists every pair -- n (n - 1) / 2 waves for the conflict call, and level(i) = i,
+ * n launches one behind the other, for a delay call -- and a list by some heuristic (the nearest by start pose) misses vehicles that start far apart
+ * and cross mid-route without anybody saying so.  This call returns a CONSERVATIVE, SORTED, REPRODUCIBLE list from per-plan bounding boxes over blocks
+ * of lattice times.  No plan data leaves the device; only the pairs come back.  Every expression is in double, in the order written.
+ *  Trajectory. The lattice, profiles, position, pose, hold flags and D = max_delay_steps are those of "start delays that clear conflicts", for
+ *           params->delay.  The call forms the extended trajectory exactly as the delay call does: k_trajectory_tickets, unchanged, on k0 - D .. k1,
+ *           T + D columns with the undelayed t_start, in the conflict call's buffers.  D = 0 gives a list for pp_*_conflicts.
+ *  Boxes.   B = times_per_box, NB = ceil(T / B).  Box b of plan i is the bounding box (xmin, ymin, xmax, ymax) of the reference point (x, y) over the
+ *           columns b B .. min(b B + B, T) - 1 + D at which the plan is present (x is not a NaN): the columns a lattice time of block b can read
+ *           under any delay 0 .. D (a time m delayed by d reads column m + D - d).  A plan that is present in none of them -- a plan with trajectory
+ *           status -1 always -- has a box of four NaNs.  Only min and max are formed, so the boxes do not depend on the order of evaluation.
+ *  Reach.   R = max over the holder's discs a (the stamp's: the footprint, or the point validator's one disc) of sqrt(ox_a ox_a + oy_a oy_a) +
+ *           (double)r_a, formed on the host; reach = (margin + (R + R)) + 1e-6.  The micrometre covers the rounding of the narrow phase -- disc
+ *           centres, differences, the square root, a few ulp of the coordinates -- for coordinates below 10^6 m, where an ulp is about 1e-10 m.
+ *  Rule.    Pair (i, j), i < j, is LISTED iff for some b both boxes exist and !(gx > reach) && !(gy > reach), gx = max(xmin_i - xmax_j, xmin_j -
+ *           xmax_i) and gy likewise; first_box is the smallest such b.
+ *  Guarantee. For any delays d_i, d_j in 0 .. D and any lattice time m: if the discs of i and j are closer than the margin there, (i, j) is listed.
+ *           In one line: both columns m + D - d lie in box b = m / B of their plan, two discs closer than the margin have reference points closer
+ *           than margin + 2 R, and a box gap on an axis is at most the distance of any two points of the boxes.  Hence pp_*_conflicts (with D = 0),
+ *           pp_*_deconflict and pp_*_deconflict_tracks give the same records over the list as over every pair (for the pairs of the list).
+ *  Order.   The list is ascending in (i, j), the row-major order of pairs == NULL, and the same bytes on every run: a pair's place is a prefix sum, no
+ *           atomic (k_plan_boxes, one wave per plan; k_box_pairs, one wave per row i, once to count and once to fill; k_pair_offsets between them).
+ *  - A list longer than max_pairs is PP_OK: the first max_pairs pairs are written, nothing behind them, and the summary says n_found > n_written.
+ *  - PP_ERR_INVALID, nothing launched, the holder usable as before: everything the delay call refuses about the tickets, the starts, the lattice and
+ *    D (reserved fields included); times_per_box outside 1 .. 2^20; max_pairs < 0; NULL pairs_host with max_pairs > 0; n * NB > 2^26.
+ *  - n == 0 and n == 1 are PP_OK with an empty list (n == 0: a summary of zeros, nothing else is looked at but what the delay call refuses).
+ *  - Legal beside queries in flight: it writes only its own buffers (32 bytes per plan and box, 8 + 4 + 8 per plan, 12 per pair it writes), kept aside
+ *    like the others when they have to grow then.  It synchronises the holder's stream twice: once to learn n_found, once behind the copy. */
+typedef struct pp_pair_params {
+	pp_delay_params delay;   /* lattice, margin, hold flags, D (0 for a list meant for pp_*_conflicts) */
+	int32_t times_per_box;   /* B, 1 .. 2^20 */
+	int32_t max_pairs;       /* rows of pairs_host / first_box_host, >= 0 */
+} pp_pair_params;            /* 56 bytes */
+typedef struct pp_pair_summary {
+	int64_t n_found;         /* pairs the rule lists */
+	int32_t n_written;       /* min(n_found, max_pairs): the FIRST n_written pairs in order */
+	int32_t n_boxes;         /* NB */
+	double  reach;
+	int32_t n_boxed;         /* plans with at least one box */
+	int32_t reserved;        /* zero */
+} pp_pair_summary;           /* 32 bytes */
+int pp_pipeline_candidate_pairs(pp_pipeline* pipeline, int32_t n, const uint64_t* tickets, const double* t_start /* [n], finite */,
+	const pp_pair_params* params, int32_t* pairs_host /* [max_pairs][2]; NULL only with max_pairs == 0 */, int32_t* first_box_host /* may be NULL; [max_pairs] */,
+	double* boxes_host /* may be NULL; [n][NB][4] */, pp_pair_summary* summary /* may be NULL */);
+/* The same kernels over the first n_queries queries of the planner's last batch, as pp_planner_deconflict is to pp_pipeline_deconflict. */
+int pp_planner_candidate_pairs(pp_planner* planner, int32_t n_queries, const double* t_start, const pp_pair_params* params, int32_t* pairs_host,
+	int32_t* first_box_host, double* boxes_host, pp_pair_summary* summary);
 /* Diagnostics: waves of the search grid that are alive right now (a blocking device-to-host copy; -1 on error). */
 int pp_pipeline_alive_waves(pp_pipeline* pipeline);
 pp_planner* pp_pipeline_planner(pp_pipeline* pipeline);           /* the buffer set: set_nonholo_table, set_primitives, get_path(slot), ... */

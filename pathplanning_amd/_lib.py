@@ -153,6 +153,18 @@ class DelayResult(C.Structure):
                 ("s_block", C.c_double * 2)]
 
 
+class PairParams(C.Structure):
+    """pp_pair_params: the delay call's parameters (max_delay_steps = 0 for a list meant for a conflict call), times_per_box (B, 1 .. 2^20 lattice times
+    per bounding box) and max_pairs, the rows of the caller's pair array"""
+    _fields_ = [("delay", DelayParams), ("times_per_box", C.c_int32), ("max_pairs", C.c_int32)]
+
+
+class PairSummary(C.Structure):
+    """pp_pair_summary: the pairs the rule lists, how many of them were written (the first ones in order), the boxes per plan, the reach, the plans with
+    at least one box; reserved is zero"""
+    _fields_ = [("n_found", C.c_int64), ("n_written", C.c_int32), ("n_boxes", C.c_int32), ("reach", C.c_double), ("n_boxed", C.c_int32), ("reserved", C.c_int32)]
+
+
 class TrackSet(C.Structure):
     """pp_track_set: M tracked movers for a deconflict_tracks call -- host pointers to offsets [M + 1] (int32, offsets[0] == 0, strictly increasing),
     waypoints [offsets[M]][3] (t, x, y; t strictly increasing within a track) and radii [M] (>= 0); reserved is zero"""
@@ -311,6 +323,8 @@ def load():
     L.pp_planner_deconflict.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.POINTER(DelayParams), vp]
     L.pp_pipeline_deconflict_tracks.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, C.POINTER(DelayParams), C.POINTER(TrackSet), vp, vp]
     L.pp_planner_deconflict_tracks.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.POINTER(DelayParams), C.POINTER(TrackSet), vp, vp]
+    L.pp_pipeline_candidate_pairs.argtypes = [vp, C.c_int32, vp, vp, C.POINTER(PairParams), vp, vp, vp, C.POINTER(PairSummary)]
+    L.pp_planner_candidate_pairs.argtypes = [vp, C.c_int32, vp, C.POINTER(PairParams), vp, vp, vp, C.POINTER(PairSummary)]
     L.pp_pipeline_timings.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.pp_pipeline_backlog.argtypes = [vp, vp, vp]
     L.pp_pipeline_planner.argtypes = [vp]

@@ -2,8 +2,8 @@
 // names their argument types) and in front of pp_planner and pp_pipeline, which both keep one buffer group per service.
 //
 // Finished plans (path records, Reeds-Shepp log, result record) are held by a batch planner, as queries 0 .. n-1 of its last batch, or by a pipeline, as
-// the slots of held tickets.  A service over them -- post-processing, re-validation, the stamp, the locate call, the speed profile, the conflict call, the delay call without and with tracked movers -- has one core (post_process_plans,
-// revalidate_plans, stamp_plans, locate_plans, speed_profile_plans, conflict_plans, deconflict_plans, deconflict_tracks_plans in pp_planner.hip) that takes a HeldPlans and goes through held_grow and held_run; its two extern "C"
+// the slots of held tickets.  A service over them -- post-processing, re-validation, the stamp, the locate call, the speed profile, the conflict call, the delay call without and with tracked movers, the broad phase -- has one core (post_process_plans,
+// revalidate_plans, stamp_plans, locate_plans, speed_profile_plans, conflict_plans, deconflict_plans, deconflict_tracks_plans, candidate_pairs_plans in pp_planner.hip) that takes a HeldPlans and goes through held_grow and held_run; its two extern "C"
 // entries check what is the holder's own and describe the holder (batch_plans, pipe_plans).
 #pragma once
 
@@ -122,6 +122,19 @@ struct TrackGroup {
 	size_t doubles = 0; // doubles `samples` holds (16 bytes per track and lattice time)
 	pph::Dev<pp_track_result> out;
 	size_t records = 0; // records `out` holds
+};
+
+/// The broad phase's buffers (it forms its extended trajectory in ConflictGroup's `rec` and `traj`, as the delay call does): the boxes, one array per
+/// component and box-major, then plan (pp_pairs.hpp); per plan the count of its row, the row's offset in the list (two more: the total and the plans
+/// with a box) and whether it has a box; the pair list and the first box of every pair
+struct PairGroup {
+	pph::Dev<double> boxes;
+	size_t doubles = 0; // doubles `boxes` holds (32 bytes per plan and box)
+	pph::Dev<long long> counts, offsets;
+	pph::Dev<int32_t> boxed;
+	size_t plans = 0; // plans they hold (`offsets` two more)
+	pph::Dev<int32_t> pairs, firstBox;
+	size_t listed = 0; // pairs they hold (8 + 4 bytes each)
 };
 
 /// Buffers that hold `capacity` units are made to hold `wanted` ({buffer, bytes}; 0 bytes: the holder does not use it).  A holder that may not free now

@@ -211,6 +211,7 @@ struct pp_pipeline {
 	ConflictGroup conflict;
 	DelayGroup delay;
 	TrackGroup track;
+	PairGroup pair;
 	std::vector<pph::DeviceMem> heldParked; // their buffers outgrown while queries were in flight: hipFree waits for the whole device (the persistent grid
 	                                        // included), so they are kept until a call finds nothing in flight (or the pipeline goes): held_grow
 	int nWf = 2;      // wavefront streams in use: consecutive submissions' launches overlap (the tail of one under the head of the next)
@@ -1255,6 +1256,25 @@ int pp_pipeline_deconflict_tracks(pp_pipeline* P, int32_t n, const uint64_t* tic
 	if (int rc = conflict_profiles(h, P->speed, t_start, lattice, plans))
 		return rc;
 	return deconflict_tracks_plans(h, P->conflict, P->delay, P->track, P->speed, plans, lattice, params->max_delay_steps, n_pairs, pairs, tracks, results_host, track_results_host);
+}
+
+/// The pairs of n completed, held queries that can meet at all on their timetables, under any delays of 0 .. max_delay_steps (include/pp_hip.h;
+/// candidate_pairs_plans): legal beside queries in flight
+int pp_pipeline_candidate_pairs(pp_pipeline* P, int32_t n, const uint64_t* tickets, const double* t_start, const pp_pair_params* params, int32_t* pairs_host,
+	int32_t* first_box_host, double* boxes_host, pp_pair_summary* summary)
+{
+	HeldPlans h;
+	if (int rc = pipe_plans(P, n, tickets, h))
+		return rc;
+	ConflictLattice lattice;
+	if (int rc = pair_check(h, t_start, params, pairs_host, lattice))
+		return rc;
+	if (int rc = pipe_resolve(P, n, tickets, "paired", true, h.slots))
+		return rc;
+	std::vector<ConflictArg> plans;
+	if (int rc = conflict_profiles(h, P->speed, t_start, lattice, plans))
+		return rc;
+	return candidate_pairs_plans(h, P->conflict, P->pair, P->speed, plans, lattice, params, pairs_host, first_box_host, boxes_host, summary);
 }
 
 /// Launch durations seen so far (HIP events on the launching streams; harvested by pp_pipeline_poll) and reset.  Wavefront: one launch per

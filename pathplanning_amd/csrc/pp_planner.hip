@@ -23,6 +23,7 @@
 #include "pp_conflict_rule.hpp"
 #include "pp_delay_rule.hpp"
 #include "pp_track_rule.hpp"
+#include "pp_pair_rule.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -317,6 +318,8 @@ struct PipeView {
 #include "pp_deconflict.hpp"
 // ... and tracked movers beside them (one wave per track, per vehicle of a level, per (vehicle, track); the same trajectory layout)
 #include "pp_tracks.hpp"
+// the pairs that can meet at all: boxes per plan and block of lattice times, then the all-pairs box test (one wave per plan, per row; the same trajectory layout)
+#include "pp_pairs.hpp"
 
 } // namespace
 
@@ -385,6 +388,7 @@ struct pp_planner {
 	ConflictGroup conflict;
 	DelayGroup delay;
 	TrackGroup track;
+	PairGroup pair;
 };
 
 namespace {
@@ -529,6 +533,31 @@ hipError_t launch_track_pairs(hipStream_t s, const Footprint& discs, const Confl
 {
 	hipLaunchKernelGGL(k_track_pairs, dim3((unsigned)((size_t)plans * (size_t)view.M)), dim3(kTrackLanes), 0, s, discs, lattice, maxDelay, plans, view.M, trajDev, decidedDev,
 		(const double*)view.samples, view.radii, outDev);
+	return hipGetLastError();
+}
+
+/// k_plan_boxes over the plans of `view`: the extended trajectory trajDev of T + D columns per plan, B lattice times per box
+hipError_t launch_plan_boxes(hipStream_t s, int T, int maxDelay, int timesPerBox, const BoxView& view, const double* trajDev, int32_t* boxedDev)
+{
+	hipLaunchKernelGGL(k_plan_boxes, dim3((unsigned)view.n), dim3(kPairLanes), 0, s, T, maxDelay, timesPerBox, view, trajDev, boxedDev);
+	return hipGetLastError();
+}
+
+/// k_box_pairs over the rows of `view`: the count pass (fill == false: countsDev) or the fill pass (offsetsDev from k_pair_offsets; at most maxPairs pairs written)
+hipError_t launch_box_pairs(hipStream_t s, bool fill, const BoxView& view, double reach, long long maxPairs, const long long* offsetsDev, long long* countsDev, int32_t* pairsDev,
+	int32_t* firstBoxDev)
+{
+	if (fill)
+		hipLaunchKernelGGL(k_box_pairs<true>, dim3((unsigned)view.n), dim3(kPairLanes), 0, s, view, reach, maxPairs, offsetsDev, countsDev, pairsDev, firstBoxDev);
+	else
+		hipLaunchKernelGGL(k_box_pairs<false>, dim3((unsigned)view.n), dim3(kPairLanes), 0, s, view, reach, maxPairs, offsetsDev, countsDev, pairsDev, firstBoxDev);
+	return hipGetLastError();
+}
+
+/// k_pair_offsets between the two: one workgroup
+hipError_t launch_pair_offsets(hipStream_t s, int plans, const long long* countsDev, const int32_t* boxedDev, long long* offsetsDev)
+{
+	hipLaunchKernelGGL(k_pair_offsets, dim3(1), dim3(kPairLanes), 0, s, plans, countsDev, boxedDev, offsetsDev);
 	return hipGetLastError();
 }
 
@@ -938,6 +967,35 @@ int tracks_check(const pp_track_set* tracks, int64_t T)
 	return PP_ERR_INVALID;
 }
 
+/// The arguments of a broad-phase call (pp_planner_candidate_pairs, pp_pipeline_candidate_pairs): the delay call's without a pair list, the block length and
+/// the caller's rows.  NULL params pass only with n == 0, as in the delay call.
+int pair_check(const HeldPlans& h, const double* t_start, const pp_pair_params* params, const int32_t* pairs_host, ConflictLattice& lattice)
+{
+	const int32_t none[2] = { 0, 0 }; // (an empty list that exists: the call has no pair list of its own to check)
+	if (int rc = delay_check(h, t_start, 0, none, params ? &params->delay : nullptr, lattice))
+		return rc;
+	if (!params)
+		return PP_OK; // (n == 0)
+	if (params->times_per_box < 1 || params->times_per_box > ppb::kMaxTimesPerBox) {
+		set_error("invalid arguments (1 <= times_per_box <= " + std::to_string(ppb::kMaxTimesPerBox) + ", got " + std::to_string(params->times_per_box) + ")");
+		return PP_ERR_INVALID;
+	}
+	if (params->max_pairs < 0) {
+		set_error("invalid arguments (max_pairs >= 0, got " + std::to_string(params->max_pairs) + ")");
+		return PP_ERR_INVALID;
+	}
+	if (!pairs_host && params->max_pairs > 0) {
+		set_error("invalid arguments (null pairs_host with max_pairs = " + std::to_string(params->max_pairs) + ")");
+		return PP_ERR_INVALID;
+	}
+	const int64_t boxes = (int64_t)h.n * ppb::box_count(lattice.T, params->times_per_box);
+	if (boxes > ppb::kMaxBoxes) {
+		set_error("invalid arguments (n * NB = " + std::to_string(boxes) + " boxes: at most " + std::to_string(ppb::kMaxBoxes) + ")");
+		return PP_ERR_INVALID;
+	}
+	return PP_OK;
+}
+
 /// ... and what the holder remembers of its last speed-profile call for the plans of h: their rows, into `plans`, and the call's stride and limits, into `lattice`
 int conflict_profiles(const HeldPlans& h, const SpeedGroup& g, const double* t_start, ConflictLattice& lattice, std::vector<ConflictArg>& plans)
 {
@@ -1274,6 +1332,89 @@ int deconflict_tracks_plans(const HeldPlans& h, ConflictGroup& c, DelayGroup& g,
 		return rc;
 	std::copy(recs.begin(), recs.end(), results_host);
 	std::copy(trackRecs.begin(), trackRecs.end(), track_results_host);
+	return PP_OK;
+}
+
+/// The pairs of the plans of h that can meet (`plans`, `lattice`: pair_check's and conflict_profiles').  The extended trajectory is formed as deconflict_plans
+/// forms it, in the conflict call's buffers; then k_plan_boxes, k_box_pairs to count, k_pair_offsets, k_box_pairs to fill, all on the holder's stream.  The stream
+/// is synchronised once inside to learn n_found, which sizes the copy of the list, and once by held_run behind the copies.
+int candidate_pairs_plans(const HeldPlans& h, ConflictGroup& c, PairGroup& g, const SpeedGroup& speed, const std::vector<ConflictArg>& plans, const ConflictLattice& lattice,
+	const pp_pair_params* params, int32_t* pairs_host, int32_t* first_box_host, double* boxes_host, pp_pair_summary* summary)
+{
+	if (summary)
+		*summary = pp_pair_summary {};
+	if (h.n == 0)
+		return PP_OK;
+	pp_planner* const pl = h.pl;
+	PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
+	const int D = params->delay.max_delay_steps, B = params->times_per_box;
+	const size_t n = (size_t)h.n, columns = (size_t)lattice.T + (size_t)D, component = n * columns;
+	const size_t NB = (size_t)ppb::box_count(lattice.T, B), nBoxes = n * NB;
+	const long long all = (long long)n * (long long)(n - 1) / 2, room = params->max_pairs < all ? params->max_pairs : all; // (no more pairs than there are)
+	PP_HIP_TRY(held_grow(h, c.doubles, component * kTrajectoryComponents, { { &c.traj, component * kTrajectoryComponents * 8 } }));
+	PP_HIP_TRY(held_grow(h, g.doubles, nBoxes * kBoxComponents, { { &g.boxes, nBoxes * kBoxComponents * 8 } }));
+	PP_HIP_TRY(held_grow(h, g.plans, n, { { &g.counts, n * 8 }, { &g.offsets, (n + 2) * 8 }, { &g.boxed, n * 4 } }));
+	if (room)
+		PP_HIP_TRY(held_grow(h, g.listed, (size_t)room, { { &g.pairs, (size_t)room * 8 }, { &g.firstBox, (size_t)room * 4 } }));
+	const SearchArgs args = held_args(h, h.ownView);
+	const Footprint discs = stamp_discs(h.footprint, pl->map);
+	double R = 0.0;
+	for (int a = 0; a < discs.n; a++) {
+		const double r = ppb::disc_reach(discs.ox[a], discs.oy[a], (double)discs.r[a]);
+		if (r > R)
+			R = r;
+	}
+	const double reach = ppb::reach(lattice.margin, R);
+	ConflictLattice extended = lattice;
+	extended.k0 = lattice.k0 - D;
+	extended.T = lattice.T + D;
+	const BoxView view { h.n, (int)NB, g.boxes.get() };
+	long long tail[2] = { 0, 0 }; // n_found, n_boxed
+	size_t written = 0;
+	std::vector<int32_t> list, first;
+	std::vector<double> staged(boxes_host ? nBoxes * kBoxComponents : 0);
+	if (int rc = held_run(h, c.rec, plans, (pp_trajectory_result*)nullptr, [&](const int32_t* slotsDev) {
+			hipError_t e = launch_trajectory(h.stream, args, extended, discs.anyOffset != 0, h.n, slotsDev, c.rec.args.get(), pl, speed.rows.get(), c.traj.get(), c.rec.out.get());
+			if (e == hipSuccess)
+				e = launch_plan_boxes(h.stream, lattice.T, D, B, view, c.traj.get(), g.boxed.get());
+			if (e == hipSuccess)
+				e = launch_box_pairs(h.stream, false, view, reach, room, nullptr, g.counts.get(), nullptr, nullptr);
+			if (e == hipSuccess)
+				e = launch_pair_offsets(h.stream, h.n, g.counts.get(), g.boxed.get(), g.offsets.get());
+			if (e == hipSuccess && room)
+				e = launch_box_pairs(h.stream, true, view, reach, room, g.offsets.get(), nullptr, g.pairs.get(), g.firstBox.get());
+			if (e == hipSuccess)
+				e = hipMemcpyAsync(tail, g.offsets.get() + n, sizeof tail, hipMemcpyDeviceToHost, h.stream);
+			if (e == hipSuccess)
+				e = hipStreamSynchronize(h.stream); // (n_found sizes the copy)
+			if (e != hipSuccess)
+				return e;
+			written = (size_t)(tail[0] < room ? tail[0] : room);
+			list.resize(written * 2);
+			first.resize(first_box_host ? written : 0);
+			if (written)
+				e = hipMemcpyAsync(list.data(), g.pairs, written * 8, hipMemcpyDeviceToHost, h.stream);
+			if (e == hipSuccess && !first.empty())
+				e = hipMemcpyAsync(first.data(), g.firstBox, written * 4, hipMemcpyDeviceToHost, h.stream);
+			if (e == hipSuccess && !staged.empty())
+				e = hipMemcpyAsync(staged.data(), g.boxes, staged.size() * 8, hipMemcpyDeviceToHost, h.stream);
+			return e;
+		}))
+		return rc;
+	std::copy(list.begin(), list.end(), pairs_host);
+	std::copy(first.begin(), first.end(), first_box_host);
+	if (boxes_host)
+		for (size_t i = 0; i < n; i++)
+			for (size_t b = 0; b < NB; b++)
+				for (size_t k = 0; k < (size_t)kBoxComponents; k++)
+					boxes_host[(i * NB + b) * kBoxComponents + k] = staged[(k * NB + b) * n + i];
+	if (summary) {
+		summary->n_found = tail[0];
+		summary->n_written = (int32_t)written;
+		summary->n_boxes = (int32_t)NB;
+		summary->reach = reach;
+		summary->n_boxed = (int32_t)tail[1];
+	}
 	return PP_OK;
 }
 
@@ -2159,6 +2300,21 @@ int pp_planner_deconflict_tracks(pp_planner* planner, int32_t n_queries, const d
 		return rc;
 	return deconflict_tracks_plans(h, planner->conflict, planner->delay, planner->track, planner->speed, plans, lattice, params->max_delay_steps, n_pairs, pairs, tracks,
 		results_host, track_results_host);
+}
+
+int pp_planner_candidate_pairs(pp_planner* planner, int32_t n_queries, const double* t_start, const pp_pair_params* params, int32_t* pairs_host, int32_t* first_box_host,
+	double* boxes_host, pp_pair_summary* summary)
+{
+	if (int rc = batch_check(planner, n_queries, "pp_pipeline_candidate_pairs lists the pairs of its held tickets"))
+		return rc;
+	const HeldPlans h = batch_plans(planner, n_queries);
+	ConflictLattice lattice;
+	if (int rc = pair_check(h, t_start, params, pairs_host, lattice))
+		return rc;
+	std::vector<ConflictArg> plans;
+	if (int rc = conflict_profiles(h, planner->speed, t_start, lattice, plans))
+		return rc;
+	return candidate_pairs_plans(h, planner->conflict, planner->pair, planner->speed, plans, lattice, params, pairs_host, first_box_host, boxes_host, summary);
 }
 
 int pp_planner_locate(pp_planner* planner, int32_t n_queries, const double* poses_host, const double* from_length, const double* to_length, const pp_locate_params* params,

@@ -1615,6 +1615,68 @@ public:
 		}
 		return out;
 	}
+	/// The pairs of held plans that can meet at all (pp_pipeline_candidate_pairs): the list, ascending in (first, second), the first block of lattice
+	/// times each pair can meet in, and what the summary says.  `pairs` feeds Conflicts, Deconflict and DeconflictTracks as it is (allPairs = false).
+	struct Candidates {
+		std::vector<std::pair<int, int>> pairs;
+		std::vector<int> firstBox;
+		long long numFound = 0; // > pairs.size(): the list was cut at maxPairs
+		int numBoxes = 0, numBoxed = 0;
+		double reach = 0.0;
+		struct Box {
+			double xMin, yMin, xMax, yMax; // NaN: the plan is absent throughout the block
+		};
+		std::vector<std::vector<Box>> boxes; // [ticket][box]; empty without withBoxes
+	};
+	/// A space-time broad phase (include/pp_hip.h, "the pairs that can meet"): per plan and block of timesPerBox lattice times the bounding box of the
+	/// vehicle's reference point under every start delay of 0 .. maxDelaySteps steps (0 for a list meant for Conflicts); a pair is listed when in some
+	/// block its boxes are no further apart on either axis than margin and footprint allow.  Conservative, sorted, the same on every run.  maxPairs < 0:
+	/// every pair the rule lists (a second call when the list outgrows the first buffer).
+	Candidates CandidatePairs(const std::vector<uint64_t>& tickets, const std::vector<double>& tStart, const ConflictHorizon& horizon, int timesPerBox = 64,
+		int maxDelaySteps = 0, int maxPairs = -1, bool withBoxes = false)
+	{
+		for (uint64_t t : tickets)
+			HeldOf(t); // (throws for a ticket that is not held)
+		const size_t n = tickets.size();
+		if (tStart.size() != n)
+			throw std::invalid_argument("CandidatePairs: tStart holds one entry per ticket");
+		Candidates out;
+		if (!m_pipe || n == 0)
+			return out;
+		const size_t every = n * (n - 1) / 2;
+		size_t room = maxPairs < 0 ? std::min(every, std::max<size_t>(1024, 8 * n)) : (size_t)maxPairs;
+		std::vector<int32_t> list, first;
+		std::vector<double> boxes;
+		pp_pair_summary sum {};
+		for (int attempt = 0; attempt < 2; attempt++) {
+			const pp_pair_params pp { { { horizon.tFrom, horizon.tTo, horizon.dt, horizon.margin, horizon.holdBefore ? 1 : 0, horizon.holdAfter ? 1 : 0 }, maxDelaySteps, 0 },
+				timesPerBox, (int32_t)room };
+			list.assign(2 * room + 2, 0);
+			first.assign(room + 1, 0);
+			ppCheck(pp_pipeline_candidate_pairs(m_pipe, (int32_t)n, tickets.data(), tStart.data(), &pp, room ? list.data() : nullptr, room ? first.data() : nullptr, nullptr, &sum));
+			if (maxPairs >= 0 || (size_t)sum.n_found <= room)
+				break;
+			room = (size_t)sum.n_found;
+		}
+		if (withBoxes) { // (the summary has said how many boxes a plan has)
+			const pp_pair_params pp { { { horizon.tFrom, horizon.tTo, horizon.dt, horizon.margin, horizon.holdBefore ? 1 : 0, horizon.holdAfter ? 1 : 0 }, maxDelaySteps, 0 },
+				timesPerBox, 0 };
+			boxes.resize(n * (size_t)sum.n_boxes * 4);
+			ppCheck(pp_pipeline_candidate_pairs(m_pipe, (int32_t)n, tickets.data(), tStart.data(), &pp, nullptr, nullptr, boxes.data(), nullptr));
+			out.boxes.assign(n, std::vector<Candidates::Box>((size_t)sum.n_boxes));
+			for (size_t k = 0; k < n * (size_t)sum.n_boxes; k++)
+				out.boxes[k / (size_t)sum.n_boxes][k % (size_t)sum.n_boxes] = Candidates::Box { boxes[4 * k], boxes[4 * k + 1], boxes[4 * k + 2], boxes[4 * k + 3] };
+		}
+		for (int32_t p = 0; p < sum.n_written; p++) {
+			out.pairs.emplace_back(list[2 * (size_t)p], list[2 * (size_t)p + 1]);
+			out.firstBox.push_back(first[(size_t)p]);
+		}
+		out.numFound = sum.n_found;
+		out.numBoxes = sum.n_boxes;
+		out.numBoxed = sum.n_boxed;
+		out.reach = sum.reach;
+		return out;
+	}
 	/// HybridAStar::GetPath() of a held query: after PostProcess the sampled and, when the smoother succeeded, smoothed path; before it the
 	/// graph-search nodes
 	std::vector<Pose2d> GetPath(uint64_t ticket) const

@@ -560,6 +560,43 @@ PYBIND11_MODULE(pyplanning, m)
 			"min_separation, t_min, s_min) at the vehicle's reported candidate.",
 			py::arg("tickets"), py::arg("t_start"), py::arg("tracks"), py::arg("pairs") = py::none(), py::arg("t_from") = 0.0, py::arg("t_to") = 60.0, py::arg("dt") = 0.1,
 			py::arg("margin") = 0.0, py::arg("hold_before") = false, py::arg("hold_after") = false, py::arg("max_delay_steps") = 0, py::arg("details") = true)
+		.def("candidate_pairs",
+			[](HybridAStarPipeline& h, const std::vector<uint64_t>& tickets, const std::vector<double>& tStart, int timesPerBox, int maxDelaySteps, bool boxes, const py::object& maxPairs,
+				double tFrom, double tTo, double dt, double margin, bool holdBefore, bool holdAfter) {
+				HybridAStarPipeline::ConflictHorizon horizon;
+				horizon.tFrom = tFrom;
+				horizon.tTo = tTo;
+				horizon.dt = dt;
+				horizon.margin = margin;
+				horizon.holdBefore = holdBefore;
+				horizon.holdAfter = holdAfter;
+				const auto r = h.CandidatePairs(tickets, tStart, horizon, timesPerBox, maxDelaySteps, maxPairs.is_none() ? -1 : maxPairs.cast<int>(), boxes);
+				py::list pairs, first, found;
+				for (const auto& p : r.pairs)
+					pairs.append(py::make_tuple(p.first, p.second));
+				for (int b : r.firstBox)
+					first.append(b);
+				for (const auto& row : r.boxes) {
+					py::list one;
+					for (const auto& b : row)
+						one.append(py::make_tuple(b.xMin, b.yMin, b.xMax, b.yMax));
+					found.append(one);
+				}
+				py::dict summary;
+				summary["n_found"] = r.numFound;
+				summary["n_written"] = r.pairs.size();
+				summary["n_boxes"] = r.numBoxes;
+				summary["n_boxed"] = r.numBoxed;
+				summary["reach"] = r.reach;
+				return boxes ? py::tuple(py::make_tuple(pairs, first, summary, found)) : py::tuple(py::make_tuple(pairs, first, summary));
+			},
+			"the pairs of held plans that can meet at all, by a space-time broad phase: per ticket and block of times_per_box lattice times the bounding box of the vehicle's "
+			"reference point under every start delay of 0 .. max_delay_steps steps (0 for a list meant for conflicts); a pair is listed when in some block its boxes are no "
+			"further apart on either axis than margin and footprint allow.  Returns (pairs [(i, j), ...] ascending, first_box, summary dict with n_found, n_written, n_boxes, "
+			"n_boxed and reach) and, with boxes, per ticket and box (xmin, ymin, xmax, ymax).  pairs feeds conflicts, deconflict and deconflict_tracks as it is; max_pairs=None: "
+			"every pair the rule lists.  t_from, t_to, dt, margin, hold_before and hold_after are those of the call the list is meant for.",
+			py::arg("tickets"), py::arg("t_start"), py::arg("times_per_box") = 64, py::arg("max_delay_steps") = 0, py::arg("boxes") = false, py::arg("max_pairs") = py::none(),
+			py::arg("t_from") = 0.0, py::arg("t_to") = 60.0, py::arg("dt") = 0.1, py::arg("margin") = 0.0, py::arg("hold_before") = false, py::arg("hold_after") = false)
 		.def("get_path", &HybridAStarPipeline::GetPath, py::arg("ticket"))
 		.def("get_graph_search_path", &HybridAStarPipeline::GetGraphSearchPath, py::arg("ticket"))
 		.def("get_smoothing_status", &HybridAStarPipeline::GetSmoothingStatus, py::arg("ticket"))

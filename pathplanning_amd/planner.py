@@ -12,7 +12,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import (RS_PATH_DTYPE, ConflictParams, ConflictResult, DelayParams, DelayResult, FootprintDisc, HybridParams, LocateParams, LocateResult, MapDesc, PostResult, QueryResult, RevalidateResult,
+from ._lib import (RS_PATH_DTYPE, ConflictParams, ConflictResult, DelayParams, DelayResult, FootprintDisc, HybridParams, LocateParams, LocateResult, MapDesc, PairParams, PairSummary, PostResult, QueryResult, RevalidateResult,
                    SmootherParams, SpeedProfileParams, SpeedProfileResult, StampParams, StampResult, TrackResult, TrackSet, TrajectoryResult, check, ptr)
 
 
@@ -732,6 +732,13 @@ class HybridAStarBatch:
                                   lambda ts, npairs, pr, dp, tk, out, rec: self.lib.pp_planner_deconflict_tracks(self.h, n, ptr(ts), npairs, ptr(pr), C.byref(dp), tk, ptr(out),
                                                                                                                  ptr(rec)))
 
+    def candidate_pairs(self, t_start, n_queries=None, times_per_box=64, max_delay_steps=0, boxes=False, max_pairs=None, **lattice):
+        """The pairs of the plans of the first n queries of the last batch that can meet: pp_planner_candidate_pairs, the batch form of
+        HybridAStarPipeline.candidate_pairs, with the same arguments (pair indices are query indices) and return value."""
+        n = len(self._results) if n_queries is None else int(n_queries)
+        return _candidate_pairs(n, t_start, times_per_box, max_delay_steps, boxes, max_pairs, lattice,
+                                lambda ts, pp, pr, fb, bx, sm: self.lib.pp_planner_candidate_pairs(self.h, n, ptr(ts), C.byref(pp), ptr(pr), ptr(fb), ptr(bx), C.byref(sm)))
+
     def certify_lattice(self, q):
         """SURVEY 7.3 H2 as a contract (pp_planner_certify_lattice): created nodes and logged lattice-line children of query q recomputed on
         the host with glibc; returns (checked, cell mismatches, unverified events, largest pose difference).  mismatches == unverified == 0
@@ -1127,6 +1134,23 @@ class HybridAStarPipeline:
                                   lambda ts, npairs, pr, dp, tk, out, rec: self.lib.pp_pipeline_deconflict_tracks(self.h, len(t), ptr(t), ptr(ts), npairs, ptr(pr), C.byref(dp), tk,
                                                                                                                   ptr(out), ptr(rec)))
 
+    def candidate_pairs(self, tickets, t_start, times_per_box=64, max_delay_steps=0, boxes=False, max_pairs=None, **lattice):
+        """Which pairs of the completed, HELD queries `tickets` can meet at all?  The pair list for conflicts(), deconflict() and deconflict_tracks() by a
+        space-time broad phase: pp_pipeline_candidate_pairs, whose definition is in include/pp_hip.h.  Per plan and block of `times_per_box` lattice
+        times the bounding box of the vehicle's reference point, over every start delay of 0 .. max_delay_steps steps (0 for a list meant for
+        conflicts()); a pair is listed when in some block the two boxes are no further apart on either axis than the margin and the footprint allow.
+        The list is conservative -- the calls above give the same records over it as over every pair -- ascending in (i, j) and the same bytes on
+        every run.  `lattice` are the keywords t_from, t_to, dt, margin, hold_before and hold_after of the call the list is meant for.
+        Returns (pairs int32 [P, 2], first_box int32 [P], summary) and, with boxes=True, the [n, NB, 4] boxes (xmin, ymin, xmax, ymax; NaN: the plan
+        is absent throughout the block).  summary is a PairSummary: n_found, n_written, n_boxes, reach, n_boxed.  max_pairs=None sizes the buffer and
+        calls again once if the list outgrows it; with a number the FIRST max_pairs pairs come back and summary.n_found says how many there are.
+        Raises PPError, with nothing launched, for everything deconflict() refuses about tickets, starts, lattice and max_delay_steps, for
+        times_per_box outside 1 .. 2^20, max_pairs < 0 and more than 2^26 boxes."""
+        t = np.ascontiguousarray(tickets, dtype=np.uint64).reshape(-1)
+        return _candidate_pairs(len(t), t_start, times_per_box, max_delay_steps, boxes, max_pairs, lattice,
+                                lambda ts, pp, pr, fb, bx, sm: self.lib.pp_pipeline_candidate_pairs(self.h, len(t), ptr(t), ptr(ts), C.byref(pp), ptr(pr), ptr(fb), ptr(bx),
+                                                                                                    C.byref(sm)))
+
     def get_expanded_of(self, ticket):
         """expansion sequence (log_expansions=True) of a completed query polled with release=False"""
         slot = self.lib.pp_pipeline_slot_of(self.h, C.c_uint64(int(ticket)))
@@ -1268,6 +1292,41 @@ def _deconflict(n, t_start, pairs, t_from, t_to, dt, margin, hold_before, hold_a
     out = np.zeros(max(n, 1), dtype=DELAY_DTYPE)
     check(call(ts, n_pairs, pr, dp, out))
     return out[:n].view(np.recarray)
+
+
+def _box_count(t_from, t_to, dt, times_per_box):
+    """NB of a candidate_pairs call, to size its boxes: ceil(T / B) with T the lattice times k * dt of [t_from, t_to]; 1 for arguments the call refuses"""
+    with np.errstate(all="ignore"):
+        T = conflict_lattice(t_from, t_to, dt)[1]
+    B = int(times_per_box)
+    return -(-T // B) if 1 <= T <= 1 << 20 and B >= 1 else 1
+
+
+def _candidate_pairs(n, t_start, times_per_box, max_delay_steps, boxes, max_pairs, lattice, call):
+    """the parameters and start times of a broad-phase call, the call (twice if the list outgrows a buffer sized here), the list, the first box of every
+    pair, the summary and (if wanted) the boxes"""
+    unknown = set(lattice) - {"t_from", "t_to", "dt", "margin", "hold_before", "hold_after"}
+    if unknown:
+        raise TypeError("candidate_pairs: unexpected keyword %s" % ", ".join(sorted(unknown)))
+    kw = dict(dict(t_from=0.0, t_to=60.0, dt=0.1, margin=0.0, hold_before=False, hold_after=False), **lattice)
+    cp = ConflictParams(float(kw["t_from"]), float(kw["t_to"]), float(kw["dt"]), float(kw["margin"]), int(kw["hold_before"]), int(kw["hold_after"]))
+    ts = _per_plan(t_start, n)
+    if ts is None and n:
+        raise ValueError("one start time per plan")
+    every = n * (n - 1) // 2
+    room = min(every, max(1024, 8 * n)) if max_pairs is None else int(max_pairs)
+    box = np.zeros((n, _box_count(kw["t_from"], kw["t_to"], kw["dt"], times_per_box), 4)) if boxes else None
+    while True:
+        pp = PairParams(DelayParams(cp, int(max_delay_steps), 0), int(times_per_box), room)
+        pairs, first, summary = np.zeros((max(room, 1), 2), dtype=np.int32), np.zeros(max(room, 1), dtype=np.int32), PairSummary()
+        check(call(ts, pp, pairs if room > 0 else None, first if room > 0 else None, box if box is not None and box.size else None, summary))
+        if max_pairs is not None or summary.n_found <= room:
+            break
+        room = int(summary.n_found)
+    if box is not None and n:
+        assert box.shape[1] == summary.n_boxes, (box.shape, summary.n_boxes)
+    out = (pairs[:summary.n_written], first[:summary.n_written], summary)
+    return out + (box,) if boxes else out
 
 
 # pp_track_result as a numpy record: a deconflict_tracks call returns an [n, M] array of these
