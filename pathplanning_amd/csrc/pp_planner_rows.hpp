@@ -60,9 +60,18 @@ constexpr int kPollEvery = PP_PIPE_POLL_EVERY; // pipeline: an idle row that fou
 #if PP_ROWS_FOOTPRINT
 #define PP_ROWS_KERNEL k_hybrid_search_rows_footprint
 #define PP_ROWS_FOOT_ARG Footprint foot, // (by value and wave-uniform: the disc loops are uniform control flow)
+// The footprint form takes its view of the arguments AGAIN at the head of the march, the truncation and the cost block (each a scope of its own): with the
+// footprint's 54 dwords next to the map's, one view for the whole children phase keeps more scalars alive than a wave has, the phase's vector-register
+// peak rises with them, and row state goes to scratch at the head of every expansion (tests/test_footprint_pipeline_host.py gates those stores).
+#define ROWS_FOOT_VIEW_AGAIN                                \
+	const RowsKernargHead& K = rows_kernargs_here();        \
+	const SearchArgs& H = K.A;                              \
+	const Footprint& foot = K.foot;                         \
+	const MapView& m = H.m;
 #else
 #define PP_ROWS_KERNEL k_hybrid_search_rows
 #define PP_ROWS_FOOT_ARG
+#define ROWS_FOOT_VIEW_AGAIN
 #endif
 template <bool kPiped>
 __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER_SIMD) PP_ROWS_KERNEL(SearchArgs A, PP_ROWS_FOOT_ARG int nQueries, const double* __restrict__ starts,
@@ -141,8 +150,6 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 	HeapEntry* const spillBuf = W.spill[lane >> 4];
 	uint32_t* const bandCnt = W.bandCnt[lane >> 4];
 
-	const MapView& m = A.m;
-	const int P = A.prims.n;
 	const int maxNodes = A.maxNodes;
 
 	// ---- per-row state (replicated in the row's lanes)
@@ -621,6 +628,15 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 		const HeapEntry top = front_pop_row(front, frontCount, lane); // the front buffer holds the globally best entries
 #endif
 		ROWS_STAMP(2) // pop + refill
+		// what the expansion reads of the by-value arguments comes from the kernel-argument segment HERE, in scalar loads that cannot leave the loop
+		// (pp_rows_rs.hpp: rows_kernargs_here): as loop invariants most of them were spilled to lanes of a VGPR, and every use in the phases below was a lane read
+		const RowsKernargHead& K = rows_kernargs_here();
+		const SearchArgs& H = K.A;
+#if PP_ROWS_FOOTPRINT
+		const Footprint& foot = K.foot; // (hides the by-value argument: the disc loops read the segment too)
+#endif
+		const MapView& m = H.m;
+		const int P = H.prims.n;
 		const int ni = (int)top.node;
 		// ---- the popped node: from the staging of the previous expansion when it is one of its children, else from the
 		// prefetch of the probable next pop, else from HBM
@@ -691,7 +707,7 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 		rsNode = -1;
 		nExpanded++;
 		int pix, piy, pit;
-		discretize_pose(ppose, A.rp.lat, A.rp.headingAlias, pix, piy, pit);
+		discretize_pose(ppose, H.rp.lat, H.rp.headingAlias, pix, piy, pit);
 		const double hCost = pH; // RS gate input (hybrid_a_star.cpp:81): computed when the node was created
 		// the raw 64-bit draw the RS gate may need is fetched now (one word of the query's engine state in HBM)
 		unsigned long long mtRaw = 0ull;
@@ -715,25 +731,25 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 				a.init = ppose;
 				a.sinF = pSin;
 				a.cosF = pCos;
-				a.kappa = A.prims.kappa[p];
-				a.invKappa = A.prims.invKappa[p];
-				a.length = A.rp.arcLength;
-				a.backward = A.prims.backward[p];
+				a.kappa = H.prims.kappa[p];
+				a.invKappa = H.prims.invKappa[p];
+				a.length = H.rp.arcLength;
+				a.backward = H.prims.backward[p];
 				child = a.interpolate_sc(1.0, cs, cc);
 				int ix, iy, it;
-				lanePathChecks += (long long)discretize_pose(child, A.rp.lat, A.rp.headingAlias, ix, iy, it) << kGuardShift;
+				lanePathChecks += (long long)discretize_pose(child, H.rp.lat, H.rp.headingAlias, ix, iy, it) << kGuardShift;
 				ROWS_STAMP(11) // endpoint
 				// look-ups of the full-length child are issued before the validity march so that their latency
 				// overlaps it (they are redone only when the arc gets truncated)
-				bool packed = A.ks.pack(ix, iy, it, key);
+				bool packed = H.ks.pack(ix, iy, it, key);
 				if (packed)
 					st = keymap[key];
 				HeurLoads hl;
-				combined_heuristic_issue(A.heur, m, field, goal, child, cs, cc, hl);
+				combined_heuristic_issue(H.heur, m, field, goal, child, cs, cc, hl);
 				ROWS_STAMP(12) // key map + heuristics
 				// Voronoi term of the full-length arc: its only map read (the last sample, Q8) is issued with the look-ups
 				float voroRaw;
-				voronoi_cost_issue(m, a, A.rp.voroDiagRes, voroRaw);
+				voronoi_cost_issue(m, a, H.rp.voroDiagRes, voroRaw);
 				ROWS_STAMP(13) // Voronoi term
 				float lastValidRatio;
 				int checks = 0;
@@ -750,31 +766,36 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 				ROWS_STAMP(4) // child's own validity
 #if PP_ROWS_FOOTPRINT
 				// the footprint's march from the parent's stored clearance; a disc centre moves up to 1 + |kappa| rho faster than the reference point
-				const bool pathValid = is_arc_valid_fp_from(m, foot, fp_gain(foot, fabs(a.kappa)), a, pDist0, lastValidRatio, checks);
+				bool pathValid;
+				{
+					ROWS_FOOT_VIEW_AGAIN
+					pathValid = is_arc_valid_fp_from(m, foot, fp_gain(foot, fabs(a.kappa)), a, pDist0, lastValidRatio, checks);
+				}
 #else
 				const bool pathValid = is_path_valid_from(m, a, a.init, pDist0, lastValidRatio, checks);
 #endif
 				ROWS_STAMP(5) // validity march
 				// the values the look-ups above fetched (loaded under the march)
-				hh = combined_heuristic_finish(A.heur, hl);
-				const double voroFull = voronoi_cost_finish(voroRaw, A.rp.voroDiagRes, A.rp.voronoiMult);
+				hh = combined_heuristic_finish(H.heur, hl);
+				const double voroFull = voronoi_cost_finish(voroRaw, H.rp.voroDiagRes, H.rp.voronoiMult);
 #if PP_ROWS_FOOTPRINT
 				d0 = fp_state_valid_finish(foot, cIn, cRaw, cd0) ? cd0 : -1.0f;
 #else
 				d0 = is_state_valid_finish(m, cIn, cd0) ? cd0 : -1.0f;
 #endif
 				if (!pathValid) {
+					ROWS_FOOT_VIEW_AGAIN
 					// PathConstantSteer::Truncate, paths/path_constant_steer.cpp:16-20
 					child = a.interpolate_sc((double)lastValidRatio, cs, cc);
 					a.length *= (double)lastValidRatio;
-					lanePathChecks += (long long)discretize_pose(child, A.rp.lat, A.rp.headingAlias, ix, iy, it) << kGuardShift;
+					lanePathChecks += (long long)discretize_pose(child, H.rp.lat, H.rp.headingAlias, ix, iy, it) << kGuardShift;
 					if (ix == pix && iy == piy && it == pit)
 						ok = false;
 					else {
-						packed = A.ks.pack(ix, iy, it, key);
+						packed = H.ks.pack(ix, iy, it, key);
 						if (packed)
 							st = keymap[key];
-						hh = combined_heuristic_sc(A.heur, m, field, goal, child, cs, cc);
+						hh = combined_heuristic_sc(H.heur, m, field, goal, child, cs, cc);
 #if PP_ROWS_FOOTPRINT
 						float cb;
 						d0 = fp_state_valid_sc(m, foot, child.x, child.y, child.t, cs, cc, cd0, cb) ? cd0 : -1.0f;
@@ -785,8 +806,9 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 				}
 				laneStateChecks += checks;
 				if (ok) {
-					const double pathCost = (a.backward ? A.rp.reverseMult : A.rp.forwardMult) * a.length;
-					const double voro = pathValid ? voroFull : voronoi_cost(m, a, A.rp.voroDiagRes, A.rp.voronoiMult);
+					ROWS_FOOT_VIEW_AGAIN
+					const double pathCost = (a.backward ? H.rp.reverseMult : H.rp.forwardMult) * a.length;
+					const double voro = pathValid ? voroFull : voronoi_cost(m, a, H.rp.voroDiagRes, H.rp.voronoiMult);
 					const double cost = pathCost + 0.0 + voro; // switching cost is always 0 (hybrid_a_star.cpp:142)
 					len = a.length;
 					gcost = pPathCost + cost;
@@ -1078,4 +1100,5 @@ __global__ void __launch_bounds__(64 * PP_ROWS_WAVES_PER_WG, PP_SEARCH_WAVES_PER
 #undef ROW_BANDS
 }
 #undef PP_ROWS_KERNEL
+#undef ROWS_FOOT_VIEW_AGAIN
 #undef PP_ROWS_FOOT_ARG

@@ -56,6 +56,19 @@ __device__ __forceinline__ const RowsKernargHead& rows_kernargs(const uint64_t s
 	return *(const RowsKernargHead*)(SegPtr)(uintptr_t)(((uint64_t)hi << 32) | lo);
 }
 
+/// The KERNEL's view of its own by-value arguments inside the expansion loop.  Read as `A.member`, every member is a loop invariant: the compiler
+/// loads them all in front of the loop, finds far more than a wave's ~100 SGPRs and parks the rest in lanes of a spill VGPR -- one v_readlane (a VALU
+/// issue slot, a double two) per use inside the loop.  Here the segment's address passes through an empty asm, so the loads stay behind it: wide
+/// scalar loads (one instruction on the scalar-memory port for up to sixteen dwords) of constant memory at the head of the phase that uses them, and
+/// the values are dead at the phase's end.  Same memory, same values; DESIGN.md section 4.4, "scalar spills".
+__device__ __forceinline__ const RowsKernargHead& rows_kernargs_here()
+{
+	typedef const __attribute__((address_space(4))) RowsKernargHead* SegPtr;
+	uint64_t segment = rows_kernarg_segment();
+	asm volatile("" : "+s"(segment));
+	return *(const RowsKernargHead*)(SegPtr)(uintptr_t)segment;
+}
+
 /// The one copy of the f64 sincos that the constant-steer arcs of an expansion share (end point, Voronoi sample, march samples, truncation,
 /// Voronoi term of a truncated arc): inlined, each use carries ocml's argument reduction and polynomials -- about 200 instructions and nine
 /// hoisted coefficient pairs a site.  Values come and go in registers.

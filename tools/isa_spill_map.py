@@ -67,7 +67,53 @@ def spill_map(path, kernel, body, phases):
     return out
 
 
+def lane_map(path, kernel, body, phases):
+    """The scalar side of the same attribution: {phase: [instructions, v_readlane_b32, v_writelane_b32, s_nop, s_load_*]} of one kernel.  The row primitives of
+    the rows kernels use ds_bpermute and DPP, so nearly every lane read / write of theirs is the reload / save of a spilled SGPR (its home is one of the
+    kernel's topmost VGPRs), each a VALU issue slot, partly with an s_nop of hazard padding behind it."""
+    lines = open(path).read().split("\n")
+    start = next(i for i, l in enumerate(lines) if l.startswith("_Z") and kernel in l and ": " in l)
+    end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
+    cur = None
+    per_line = collections.defaultdict(lambda: [0, 0, 0, 0, 0])
+    inst = re.compile(r"(v_|s_|ds_|global_|scratch_|buffer_|flat_)")
+    frame = re.compile(r"([\w./+-]+):(\d+):\d+")
+    cols = ("v_readlane_b32", "v_writelane_b32", "s_nop", "s_load_")
+    for l in lines[start:end]:
+        s = l.strip()
+        if s.startswith(".loc"):
+            c = s.split(";", 1)[1] if ";" in s else ""
+            inb = [int(n) for f, n in frame.findall(c) if f.split("/")[-1] == body and int(n) > 0]
+            cur = inb[-1] if inb else cur
+            continue
+        if inst.match(s):
+            e = per_line[cur]
+            e[0] += 1
+            for i, c in enumerate(cols):
+                if s.startswith(c):
+                    e[i + 1] += 1
+    out = {}
+    for name, lo, hi in phases:
+        v = [0, 0, 0, 0, 0]
+        for ln, e in per_line.items():
+            if ln is not None and lo <= ln <= hi:
+                for i in range(5):
+                    v[i] += e[i]
+        out[name] = v
+    return out
+
+
 def main():
+    if "--lanes" in sys.argv:  # the scalar-spill table: lane reads / writes, s_nop and scalar loads per phase
+        argv = [a for a in sys.argv[1:] if a != "--lanes"]
+        phases = phases_from_stamps(next(a for a in argv if a.startswith("--stamps=")).split("=", 1)[1])
+        m = lane_map(argv[0], argv[1], argv[2], phases)
+        print("%-18s %8s %10s %11s %8s %8s" % ("phase", "insts", "lane reads", "lane writes", "s_nop", "s_load"))
+        for name, _, _ in phases:
+            print("%-18s %8d %10d %11d %8d %8d" % ((name,) + tuple(m[name])))
+        hot = ("pop+refill", "node", "children", "insertion", "node-records")
+        print("%-18s %8d %10d %11d %8d %8d" % (("per-expansion",) + tuple(sum(m[p][i] for p in hot) for i in range(5))))
+        return
     path, kernel, body = sys.argv[1], sys.argv[2], sys.argv[3]
     phases = []
     for a in sys.argv[4:]:
