@@ -974,6 +974,88 @@ int pp_pipeline_candidate_pairs(pp_pipeline* pipeline, int32_t n, const uint64_t
 /* The same kernels over the first n_queries queries of the planner's last batch, as pp_planner_deconflict is to pp_pipeline_deconflict. */
 int pp_planner_candidate_pairs(pp_planner* planner, int32_t n_queries, const double* t_start, const pp_pair_params* params, int32_t* pairs_host,
 	int32_t* first_box_host, double* boxes_host, pp_pair_summary* summary);
+/* ---- timetable look-ups and stops ---------------------------------------------------------------------------------------------------------------
+ * The services above read the timetable (s, v, t) a speed-profile call leaves on the device; this call answers questions about it without the rows
+ * coming down: where is the vehicle, how fast and on which pose, u seconds after its start; when, on its timetable, is it at arc length s (the s a
+ * locate call returned: t_start = now - t re-anchors a vehicle under way for the conflict and delay calls); where does it stand, and for how long.
+ * It reads no map and writes only its own buffers.  Every expression is in double, in the order written.
+ *  Profile. The holder's most recent speed-profile call, exactly as the conflict call reads it: the rows (s_j, v_j, t_j), j = 0 .. N - 1, a_acc and
+ *           a_dec.  A plan whose profile has a status other than 0 gets plan status -1, and every look-up of it status -1.
+ *  Stops.   Sample j is a STOP iff v_j == 0.0 -- row 0 and row N - 1 included when they stand.  t_depart = t_j; t_arrive = 0 for j == 0, else
+ *           t_{j-1} + step_time(s_j - s_{j-1}, v_{j-1}, v_j) ("speed profiles", Time).  t_j is t_{j-1} + (step_time + dwell), and addition is
+ *           monotone, so t_arrive <= t_depart; at a cusp stop they differ by the dwell.  The stops are listed in row order; the FIRST max_stops are
+ *           written, nothing behind them, and the list has the same bytes on every run (a stop's place is a count, no atomic).
+ *  By time  (by == 1, the value is u).  u < 0: status 1 and the record of u = 0.  u > t_{N-1}: status 2 and the record of u = t_{N-1}.  Otherwise
+ *           status 0.  t is the clamped u; j and s are the conflict call's "Position" (the largest j with t_j <= t, the position within the step), so
+ *           s has the bits the conflict call's trajectory has for tau - t_start == u.  With delta = t - t_j, ds = s_{j+1} - s_j and m = step_time(ds,
+ *           v_j, v_{j+1}), by the first case that applies:
+ *             j == N - 1 or ds == 0            v = v_j                      a = 0
+ *             delta >= m (the dwell)           v = v_{j+1}                  a = 0
+ *             v_j + v_{j+1} > 0 (trapezoid)    a = (v_{j+1} - v_j) / m      v = v_j + a * delta
+ *             delta <= ta (triangle)           v = a_acc * delta            a = a_acc           x = ds a_dec / (a_acc + a_dec), ta = sqrt(2 x / a_acc)
+ *             otherwise                        v = a_dec * (m - delta)      a = -a_dec
+ *  By arc length (by == 0, the value is s).  s < s_0: status 1 and the record of s_0.  s > s_{N-1}: status 2 and the record of s_{N-1}.  Otherwise
+ *           status 0.  The reported s is the clamped value.  j is the largest index with s_j <= s -- behind equal arc lengths the LAST row, so a
+ *           vehicle found at a cusp stop is on the departure side.  j == N - 1: t = t_j, v = v_j, a = 0.  Otherwise ds = s_{j+1} - s_j > 0,
+ *           sigma = s - s_j, m = step_time(ds, v_j, v_{j+1}), and
+ *             v_j + v_{j+1} > 0:   a = (v_{j+1} - v_j) / m;  sigma == 0: delta = 0, v = v_j;  else w = v_j v_j + (2 a) sigma (0 if less), v = sqrt(w),
+ *                                  delta = (2 sigma) / (v_j + v)
+ *             else (triangle)      x = ds a_dec / (a_acc + a_dec);  sigma == 0: delta = 0, v = v_j (= 0), a = a_acc;
+ *                                  sigma <= x: delta = sqrt(2 sigma / a_acc), v = a_acc delta, a = a_acc;
+ *                                  otherwise r = sqrt(2 (ds - sigma) / a_dec), delta = m - r, v = a_dec r, a = -a_dec
+ *           delta is clamped into [0, m] (anything that is not >= 0 is 0), and t = t_j + delta.  t(s) never decreases in s.
+ *  Pose.    The conflict call's "Pose" at the reported s: the edge (the largest e with S_e <= s) and the ratio of the locate call's mapping, then the
+ *           path object's interpolation.  direction and kappa are the path object's own at that ratio, by the calls the speed profile uses (+1 / -1,
+ *           0 where it reports no motion; |curvature|); no direction is carried over from earlier samples.  A one-pose plan gives its pose, edge 0,
+ *           ratio 0, direction 0 and kappa 0.
+ *  Next stop. next_stop is the index, in the plan's LISTED stops, of the first one with row > j; -1 if none is listed.  When n_stops > max_stops only
+ *           the listed ones are searched: a look-up behind the last listed stop says -1 although the plan stops again.  s_to_stop = stop.s - s and
+ *           t_to_stop = stop.t_arrive - t; t_remaining = t_{N-1} - t.
+ *  - PP_ERR_INVALID, nothing launched, the holder usable as before, the message naming the first offender: everything the conflict call refuses about
+ *    n, the tickets and a missing profile ("run speed_profile first"); NULL params, or NULL values_host with n * n_points > 0; by outside {0, 1};
+ *    max_stops outside 0 .. 2^16; a reserved field that is not zero; n_points < 0 or n * n_points > 2^26; a value that is not finite.
+ *  - Any of the three output pointers may be NULL.  NULL stops_host with max_stops > 0 is allowed: the list is formed (next_stop refers to it) and
+ *    counted, not copied.  Rows of stops_host behind a plan's n_listed are left as they are.
+ *  - n == 0 is PP_OK.  n_points == 0 gives plans and stops only.
+ *  - Legal beside queries in flight: it writes only its own buffers (40 bytes per plan, 32 per plan and listed stop, 8 + 128 per look-up), kept aside
+ *    like the others when they have to grow then (k_timetable_tickets, one wave per plan). */
+typedef struct pp_timetable_params {
+	int32_t by;         /* 0: values are arc lengths s (metres); 1: values are times u since the plan's start (seconds) */
+	int32_t max_stops;  /* 0 .. 2^16: rows of stops_host per plan; 0: no stop list */
+	int32_t reserved[2];/* zero */
+} pp_timetable_params;      /* 16 bytes */
+typedef struct pp_timetable_plan {   /* per ticket */
+	int32_t status;     /* 0; -1 the ticket's profile has status != 0 */
+	int32_t n_samples;  /* N of the profile */
+	int32_t n_stops;    /* stops the rule finds */
+	int32_t n_listed;   /* min(n_stops, max_stops): the FIRST ones in row order */
+	double  s_first, s_last, duration;   /* s_0, s_{N-1}, t_{N-1} */
+} pp_timetable_plan;        /* 40 bytes; for status -1 every field but status is zero */
+typedef struct pp_timetable_stop {
+	int32_t row;        /* j */
+	int32_t reserved;
+	double  s, t_arrive, t_depart;
+} pp_timetable_stop;        /* 32 bytes */
+typedef struct pp_timetable_result { /* per look-up */
+	int32_t status;     /* 0 inside the profile; 1 before it (the record of its first point); 2 behind it (the record of its last point); -1 plan status -1 */
+	int32_t row;        /* j */
+	int32_t edge;       /* as pp_locate_result::edge */
+	int32_t direction;  /* +1 / -1 / 0: the path object's travel direction at the ratio (0: it reports no motion there) */
+	double  s, t, v, a; /* arc length, time since the start, speed, acceleration along the path */
+	double  ratio, kappa; /* position on the edge; |curvature| as the speed profile defines kappa_j */
+	double  pose[3];
+	int32_t next_stop;  /* index into the plan's LISTED stops of the first one with row > j; -1: none listed */
+	int32_t reserved;
+	double  s_to_stop, t_to_stop; /* stop.s - s, stop.t_arrive - t; zero for next_stop == -1 */
+	double  t_remaining;          /* t_{N-1} - t */
+	double  reserved1;
+} pp_timetable_result;      /* 128 bytes; for status -1 every field but status is zero */
+int pp_pipeline_timetable(pp_pipeline* pipeline, int32_t n, const uint64_t* tickets, int32_t n_points /* P >= 0 */, const double* values_host /* [n][P], finite */,
+	const pp_timetable_params* params, pp_timetable_plan* plans_host /* may be NULL; [n] */, pp_timetable_stop* stops_host /* may be NULL; [n][max_stops] */,
+	pp_timetable_result* results_host /* may be NULL; [n][P] */);
+/* The same kernel over the first n_queries queries of the planner's last batch, as pp_planner_conflicts is to pp_pipeline_conflicts. */
+int pp_planner_timetable(pp_planner* planner, int32_t n_queries, int32_t n_points, const double* values_host, const pp_timetable_params* params,
+	pp_timetable_plan* plans_host, pp_timetable_stop* stops_host, pp_timetable_result* results_host);
 /* Diagnostics: waves of the search grid that are alive right now (a blocking device-to-host copy; -1 on error). */
 int pp_pipeline_alive_waves(pp_pipeline* pipeline);
 pp_planner* pp_pipeline_planner(pp_pipeline* pipeline);           /* the buffer set: set_nonholo_table, set_primitives, get_path(slot), ... */

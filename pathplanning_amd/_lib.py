@@ -165,6 +165,32 @@ class PairSummary(C.Structure):
     _fields_ = [("n_found", C.c_int64), ("n_written", C.c_int32), ("n_boxes", C.c_int32), ("reach", C.c_double), ("n_boxed", C.c_int32), ("reserved", C.c_int32)]
 
 
+class TimetableParams(C.Structure):
+    """pp_timetable_params: by (0: the values are arc lengths, 1: times since the plan's start), max_stops (0 .. 2^16 rows of the stop list per plan);
+    reserved is zero"""
+    _fields_ = [("by", C.c_int32), ("max_stops", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class TimetablePlan(C.Structure):
+    """pp_timetable_plan: status (0; -1: the profile has a status other than 0), the profile's N, the stops the rule finds and how many of them are
+    listed (the first ones in row order), s_0, s_{N-1} and t_{N-1}"""
+    _fields_ = [("status", C.c_int32), ("n_samples", C.c_int32), ("n_stops", C.c_int32), ("n_listed", C.c_int32), ("s_first", C.c_double), ("s_last", C.c_double),
+                ("duration", C.c_double)]
+
+
+class TimetableStop(C.Structure):
+    """pp_timetable_stop: the row of a standing sample, its arc length, when the vehicle arrives there and when it leaves; reserved is zero"""
+    _fields_ = [("row", C.c_int32), ("reserved", C.c_int32), ("s", C.c_double), ("t_arrive", C.c_double), ("t_depart", C.c_double)]
+
+
+class TimetableResult(C.Structure):
+    """pp_timetable_result: one look-up -- status (0 inside the profile, 1 before it, 2 behind it, -1 no profile), row, edge, direction, s, t, v, a,
+    ratio, kappa, the pose, the index of the next listed stop (-1: none) with the distance and the time to it, the time to the plan's end"""
+    _fields_ = [("status", C.c_int32), ("row", C.c_int32), ("edge", C.c_int32), ("direction", C.c_int32), ("s", C.c_double), ("t", C.c_double), ("v", C.c_double),
+                ("a", C.c_double), ("ratio", C.c_double), ("kappa", C.c_double), ("pose", C.c_double * 3), ("next_stop", C.c_int32), ("reserved", C.c_int32),
+                ("s_to_stop", C.c_double), ("t_to_stop", C.c_double), ("t_remaining", C.c_double), ("reserved1", C.c_double)]
+
+
 class TrackSet(C.Structure):
     """pp_track_set: M tracked movers for a deconflict_tracks call -- host pointers to offsets [M + 1] (int32, offsets[0] == 0, strictly increasing),
     waypoints [offsets[M]][3] (t, x, y; t strictly increasing within a track) and radii [M] (>= 0); reserved is zero"""
@@ -325,6 +351,8 @@ def load():
     L.pp_planner_deconflict_tracks.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.POINTER(DelayParams), C.POINTER(TrackSet), vp, vp]
     L.pp_pipeline_candidate_pairs.argtypes = [vp, C.c_int32, vp, vp, C.POINTER(PairParams), vp, vp, vp, C.POINTER(PairSummary)]
     L.pp_planner_candidate_pairs.argtypes = [vp, C.c_int32, vp, C.POINTER(PairParams), vp, vp, vp, C.POINTER(PairSummary)]
+    L.pp_pipeline_timetable.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.POINTER(TimetableParams), vp, vp, vp]
+    L.pp_planner_timetable.argtypes = [vp, C.c_int32, C.c_int32, vp, C.POINTER(TimetableParams), vp, vp, vp]
     L.pp_pipeline_timings.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.pp_pipeline_backlog.argtypes = [vp, vp, vp]
     L.pp_pipeline_planner.argtypes = [vp]

@@ -306,6 +306,36 @@ def build_pair_rule_test(verbose=True):
     return out
 
 
+def build_pipeline_timetable_test(verbose=True):
+    """tests/cpp/test_pipeline_timetable.cpp: Timetable(tickets, values) of HybridAStarPipeline against a plain sequential loop over the rows SpeedProfile
+    downloads (run on the GPU box)."""
+    build()
+    out = os.path.join(LIB_DIR, "test_pipeline_timetable")
+    src = os.path.join(HERE, "..", "tests", "cpp", "test_pipeline_timetable.cpp")
+    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", src, "-o", out, "-L" + LIB_DIR, "-lpphip", "-Wl,-rpath,$ORIGIN"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return out
+
+
+def build_timetable_rule_test(verbose=True):
+    """tests/cpp/test_timetable_rule.cpp: the row search by arc length, the inverse step, speed and acceleration by time, the stops and the next-stop
+    search (csrc/pp_timetable_rule.hpp) alone, on the CPU, under the address and undefined-behaviour sanitizers; without contraction, as the library is
+    built."""
+    os.makedirs(LIB_DIR, exist_ok=True)
+    out = os.path.join(LIB_DIR, "test_timetable_rule")
+    src = os.path.join(HERE, "..", "tests", "cpp", "test_timetable_rule.cpp")
+    headers = [os.path.join(CSRC, h) for h in ("pp_timetable_rule.hpp", "pp_conflict_rule.hpp", "pp_speed_rule.hpp", "pp_stamp_rule.hpp")]
+    if os.path.exists(out) and os.path.getmtime(out) > max(os.path.getmtime(f) for f in [src] + headers):
+        return out
+    cmd = ["g++", "-std=c++17", "-g", "-O1", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC, src, "-o", out]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return out
+
+
 def build_ticket_table_test(verbose=True):
     """tests/cpp/test_ticket_table.cpp: the pipeline's slot and ticket bookkeeping (csrc/pp_ticket_table.hpp) alone, on the CPU, under the address and
     undefined-behaviour sanitizers."""
@@ -356,5 +386,7 @@ if __name__ == "__main__":
     print(build_track_rule_test())
     print(build_pipeline_candidate_pairs_test())
     print(build_pair_rule_test())
+    print(build_pipeline_timetable_test())
+    print(build_timetable_rule_test())
     print(build_ticket_table_test())
     print(build_row_test())

@@ -2,8 +2,8 @@
 // names their argument types) and in front of pp_planner and pp_pipeline, which both keep one buffer group per service.
 //
 // Finished plans (path records, Reeds-Shepp log, result record) are held by a batch planner, as queries 0 .. n-1 of its last batch, or by a pipeline, as
-// the slots of held tickets.  A service over them -- post-processing, re-validation, the stamp, the locate call, the speed profile, the conflict call, the delay call without and with tracked movers, the broad phase -- has one core (post_process_plans,
-// revalidate_plans, stamp_plans, locate_plans, speed_profile_plans, conflict_plans, deconflict_plans, deconflict_tracks_plans, candidate_pairs_plans in pp_planner.hip) that takes a HeldPlans and goes through held_grow and held_run; its two extern "C"
+// the slots of held tickets.  A service over them -- post-processing, re-validation, the stamp, the locate call, the speed profile, the conflict call, the delay call without and with tracked movers, the broad phase, the timetable look-ups -- has one core (post_process_plans,
+// revalidate_plans, stamp_plans, locate_plans, speed_profile_plans, conflict_plans, deconflict_plans, deconflict_tracks_plans, candidate_pairs_plans, timetable_plans in pp_planner.hip) that takes a HeldPlans and goes through held_grow and held_run; its two extern "C"
 // entries check what is the holder's own and describe the holder (batch_plans, pipe_plans).
 #pragma once
 
@@ -135,6 +135,17 @@ struct PairGroup {
 	size_t plans = 0; // plans they hold (`offsets` two more)
 	pph::Dev<int32_t> pairs, firstBox;
 	size_t listed = 0; // pairs they hold (8 + 4 bytes each)
+};
+
+/// The timetable call's buffers: per plan the slot list, the profile row (a ConflictArg whose start time is not read) and the plan record; the values
+/// looked up and their records; the stop lists, max_stops rows per plan
+struct TimetableGroup {
+	HeldBuffers<ConflictArg, pp_timetable_plan> rec;
+	pph::Dev<double> values;
+	pph::Dev<pp_timetable_result> results;
+	size_t lookups = 0; // look-ups they hold (8 + 128 bytes each)
+	pph::Dev<pp_timetable_stop> stops;
+	size_t listed = 0; // stops `stops` holds (32 bytes each)
 };
 
 /// Buffers that hold `capacity` units are made to hold `wanted` ({buffer, bytes}; 0 bytes: the holder does not use it).  A holder that may not free now

@@ -212,6 +212,7 @@ struct pp_pipeline {
 	DelayGroup delay;
 	TrackGroup track;
 	PairGroup pair;
+	TimetableGroup timetable;
 	std::vector<pph::DeviceMem> heldParked; // their buffers outgrown while queries were in flight: hipFree waits for the whole device (the persistent grid
 	                                        // included), so they are kept until a call finds nothing in flight (or the pipeline goes): held_grow
 	int nWf = 2;      // wavefront streams in use: consecutive submissions' launches overlap (the tail of one under the head of the next)
@@ -1275,6 +1276,24 @@ int pp_pipeline_candidate_pairs(pp_pipeline* P, int32_t n, const uint64_t* ticke
 	if (int rc = conflict_profiles(h, P->speed, t_start, lattice, plans))
 		return rc;
 	return candidate_pairs_plans(h, P->conflict, P->pair, P->speed, plans, lattice, params, pairs_host, first_box_host, boxes_host, summary);
+}
+
+/// Look-ups into the timetables of n completed, held queries and the lists of their stops (include/pp_hip.h; timetable_plans): legal beside queries in flight
+int pp_pipeline_timetable(pp_pipeline* P, int32_t n, const uint64_t* tickets, int32_t n_points, const double* values_host, const pp_timetable_params* params,
+	pp_timetable_plan* plans_host, pp_timetable_stop* stops_host, pp_timetable_result* results_host)
+{
+	HeldPlans h;
+	if (int rc = pipe_plans(P, n, tickets, h))
+		return rc;
+	if (int rc = timetable_check(h, n_points, values_host, params))
+		return rc;
+	if (int rc = pipe_resolve(P, n, tickets, "asked for its timetable", true, h.slots))
+		return rc;
+	std::vector<ConflictArg> plans;
+	TimetableCall call;
+	if (int rc = timetable_profiles(h, P->speed, n_points, params, plans, call))
+		return rc;
+	return timetable_plans(h, P->timetable, P->speed, plans, call, values_host, plans_host, stops_host, results_host);
 }
 
 /// Launch durations seen so far (HIP events on the launching streams; harvested by pp_pipeline_poll) and reset.  Wavefront: one launch per

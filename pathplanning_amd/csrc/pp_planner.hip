@@ -24,6 +24,7 @@
 #include "pp_delay_rule.hpp"
 #include "pp_track_rule.hpp"
 #include "pp_pair_rule.hpp"
+#include "pp_timetable_rule.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -320,6 +321,8 @@ struct PipeView {
 #include "pp_tracks.hpp"
 // the pairs that can meet at all: boxes per plan and block of lattice times, then the all-pairs box test (one wave per plan, per row; the same trajectory layout)
 #include "pp_pairs.hpp"
+// questions to a plan's timetable: look-ups by arc length or by time and the list of its stops (one wave per plan)
+#include "pp_timetable.hpp"
 
 } // namespace
 
@@ -389,6 +392,7 @@ struct pp_planner {
 	DelayGroup delay;
 	TrackGroup track;
 	PairGroup pair;
+	TimetableGroup timetable;
 };
 
 namespace {
@@ -561,6 +565,15 @@ hipError_t launch_pair_offsets(hipStream_t s, int plans, const long long* counts
 	return hipGetLastError();
 }
 
+/// k_timetable_tickets over `count` plans of buffer set p (count = 0 on a grid of one: the warm-up, which dereferences nothing)
+hipError_t launch_timetable(hipStream_t s, const SearchArgs& args, const TimetableCall& call, int count, const int32_t* slotsDev, const ConflictArg* argsDev, pp_planner* p,
+	const double* rowsDev, const double* valuesDev, pp_timetable_stop* stopsDev, pp_timetable_result* lookupsDev, pp_timetable_plan* outDev)
+{
+	hipLaunchKernelGGL(k_timetable_tickets, dim3(count > 0 ? count : 1), dim3(kTimetableLanes), trajectory_lds_bytes(args.maxPath), s, args, call, count, slotsDev, argsDev,
+		p->paths.get(), p->rsLogs.get(), p->results.get(), rowsDev, valuesDev, stopsDev, lookupsDev, outDev);
+	return hipGetLastError();
+}
+
 /// An empty dispatch of each kernel that works on held plans (post-processing in the holder's form), on stream s, which is drained behind each: the queue
 /// allocates their scratch here, where a failure is an error code (see warm_up_kernels).  *service names the service whose kernel failed.
 hipError_t warm_up_held_kernels(pp_planner* p, hipStream_t s, bool byTicket, const char** service)
@@ -588,6 +601,8 @@ hipError_t warm_up_held_kernels(pp_planner* p, hipStream_t s, bool byTicket, con
 					(void)ok("conflict pairs", launch_conflict_pairs(s, Footprint {}, ConflictLattice {}, 0, 0, nullptr, nullptr, nullptr, nullptr));
 	if (e == hipSuccess)
 		(void)ok("delay levels", launch_delay_level(s, Footprint {}, ConflictLattice {}, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+	if (e == hipSuccess)
+		(void)ok("timetable", launch_timetable(s, p->args, TimetableCall {}, 0, nullptr, nullptr, p, nullptr, nullptr, nullptr, nullptr, nullptr));
 	return e;
 }
 
@@ -996,6 +1011,46 @@ int pair_check(const HeldPlans& h, const double* t_start, const pp_pair_params* 
 	return PP_OK;
 }
 
+/// The arguments of a timetable call (pp_planner_timetable, pp_pipeline_timetable) that do not depend on who holds the plans: the parameters, the count of
+/// look-ups and the values (h.name(i) names plan i in a refusal)
+int timetable_check(const HeldPlans& h, int n_points, const double* values_host, const pp_timetable_params* params)
+{
+	if (h.n == 0)
+		return PP_OK;
+	if (!params) {
+		set_error("invalid arguments (null params: a pp_timetable_params is needed)");
+		return PP_ERR_INVALID;
+	}
+	if (params->by != 0 && params->by != 1) {
+		set_error("invalid arguments (the timetable call's by is 0, arc lengths, or 1, times: got " + std::to_string(params->by) + ")");
+		return PP_ERR_INVALID;
+	}
+	if (params->max_stops < 0 || params->max_stops > ppm::kMaxStops) {
+		set_error("invalid arguments (0 <= max_stops <= " + std::to_string(ppm::kMaxStops) + ", got " + std::to_string(params->max_stops) + ")");
+		return PP_ERR_INVALID;
+	}
+	if (params->reserved[0] != 0 || params->reserved[1] != 0) {
+		set_error("invalid arguments (the reserved fields of pp_timetable_params are zero)");
+		return PP_ERR_INVALID;
+	}
+	if (n_points < 0 || (int64_t)h.n * n_points > ppm::kMaxLookups) {
+		set_error("invalid arguments (n_points >= 0 and n * n_points <= " + std::to_string(ppm::kMaxLookups) + ", got n_points = " + std::to_string(n_points) + " for " +
+			std::to_string(h.n) + " plans)");
+		return PP_ERR_INVALID;
+	}
+	if (n_points > 0 && !values_host) {
+		set_error("invalid arguments (null values_host with n * n_points = " + std::to_string((int64_t)h.n * n_points) + " look-ups)");
+		return PP_ERR_INVALID;
+	}
+	for (int i = 0; i < h.n; i++)
+		for (int p = 0; p < n_points; p++)
+			if (!std::isfinite(values_host[(size_t)i * (size_t)n_points + (size_t)p])) {
+				set_error(h.name(i) + " has a value that is not finite (look-up " + std::to_string(p) + ")");
+				return PP_ERR_INVALID;
+			}
+	return PP_OK;
+}
+
 /// ... and what the holder remembers of its last speed-profile call for the plans of h: their rows, into `plans`, and the call's stride and limits, into `lattice`
 int conflict_profiles(const HeldPlans& h, const SpeedGroup& g, const double* t_start, ConflictLattice& lattice, std::vector<ConflictArg>& plans)
 {
@@ -1013,6 +1068,20 @@ int conflict_profiles(const HeldPlans& h, const SpeedGroup& g, const double* t_s
 	lattice.maxSamples = g.maxSamples;
 	lattice.aAcc = g.aAcc;
 	lattice.aDec = g.aDec;
+	return PP_OK;
+}
+
+/// ... the same for a timetable call, which has no start times: the rows into `plans`, the call into `call`
+int timetable_profiles(const HeldPlans& h, const SpeedGroup& g, int n_points, const pp_timetable_params* params, std::vector<ConflictArg>& plans, TimetableCall& call)
+{
+	call = TimetableCall {};
+	if (h.n == 0)
+		return PP_OK;
+	const std::vector<double> noStart((size_t)h.n, 0.0);
+	ConflictLattice lattice {};
+	if (int rc = conflict_profiles(h, g, noStart.data(), lattice, plans))
+		return rc;
+	call = TimetableCall { params->by, params->max_stops, n_points, lattice.maxSamples, lattice.aAcc, lattice.aDec };
 	return PP_OK;
 }
 
@@ -1415,6 +1484,49 @@ int candidate_pairs_plans(const HeldPlans& h, ConflictGroup& c, PairGroup& g, co
 		summary->reach = reach;
 		summary->n_boxed = (int32_t)tail[1];
 	}
+	return PP_OK;
+}
+
+/// Look-ups into the timetables of the plans of h and their stop lists (`plans`, `call`: timetable_check's and timetable_profiles').  The values go up, the kernel
+/// and every copy behind it run on the holder's stream, which held_run synchronises once.  The stop lists come down whole and only the listed rows of each plan
+/// reach the caller's array.
+int timetable_plans(const HeldPlans& h, TimetableGroup& g, const SpeedGroup& speed, const std::vector<ConflictArg>& plans, const TimetableCall& call, const double* values_host,
+	pp_timetable_plan* plans_host, pp_timetable_stop* stops_host, pp_timetable_result* results_host)
+{
+	if (h.n == 0)
+		return PP_OK;
+	pp_planner* const pl = h.pl;
+	PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
+	const size_t n = (size_t)h.n, lookups = n * (size_t)call.nPoints, listed = n * (size_t)call.maxStops;
+	if (lookups)
+		PP_HIP_TRY(held_grow(h, g.lookups, lookups, { { &g.values, lookups * 8 }, { &g.results, lookups * sizeof(pp_timetable_result) } }));
+	if (listed)
+		PP_HIP_TRY(held_grow(h, g.listed, listed, { { &g.stops, listed * sizeof(pp_timetable_stop) } }));
+	const SearchArgs args = held_args(h, h.ownView);
+	std::vector<pp_timetable_stop> staged(stops_host ? listed : 0);
+	std::vector<pp_timetable_result> recs(results_host ? lookups : 0);
+	std::vector<pp_timetable_plan> kept;
+	if (int rc = held_run(
+			h, g.rec, plans, plans_host,
+			[&](const int32_t* slotsDev) {
+				hipError_t e = hipSuccess;
+				if (lookups)
+					e = hipMemcpyAsync(g.values, values_host, lookups * 8, hipMemcpyHostToDevice, h.stream);
+				if (e == hipSuccess)
+					e = launch_timetable(h.stream, args, call, h.n, slotsDev, g.rec.args.get(), pl, speed.rows.get(), lookups ? g.values.get() : nullptr,
+						listed ? g.stops.get() : nullptr, lookups ? g.results.get() : nullptr, g.rec.out.get());
+				if (e == hipSuccess && !recs.empty())
+					e = hipMemcpyAsync(recs.data(), g.results, lookups * sizeof(pp_timetable_result), hipMemcpyDeviceToHost, h.stream);
+				if (e == hipSuccess && !staged.empty())
+					e = hipMemcpyAsync(staged.data(), g.stops, listed * sizeof(pp_timetable_stop), hipMemcpyDeviceToHost, h.stream);
+				return e;
+			},
+			&kept))
+		return rc;
+	std::copy(recs.begin(), recs.end(), results_host);
+	if (!staged.empty())
+		for (size_t i = 0; i < n; i++) // (rows behind n_listed stay as the caller left them)
+			std::copy(staged.begin() + i * (size_t)call.maxStops, staged.begin() + i * (size_t)call.maxStops + (size_t)kept[i].n_listed, stops_host + i * (size_t)call.maxStops);
 	return PP_OK;
 }
 
@@ -2315,6 +2427,21 @@ int pp_planner_candidate_pairs(pp_planner* planner, int32_t n_queries, const dou
 	if (int rc = conflict_profiles(h, planner->speed, t_start, lattice, plans))
 		return rc;
 	return candidate_pairs_plans(h, planner->conflict, planner->pair, planner->speed, plans, lattice, params, pairs_host, first_box_host, boxes_host, summary);
+}
+
+int pp_planner_timetable(pp_planner* planner, int32_t n_queries, int32_t n_points, const double* values_host, const pp_timetable_params* params, pp_timetable_plan* plans_host,
+	pp_timetable_stop* stops_host, pp_timetable_result* results_host)
+{
+	if (int rc = batch_check(planner, n_queries, "pp_pipeline_timetable looks its held tickets' timetables up"))
+		return rc;
+	const HeldPlans h = batch_plans(planner, n_queries);
+	if (int rc = timetable_check(h, n_points, values_host, params))
+		return rc;
+	std::vector<ConflictArg> plans;
+	TimetableCall call;
+	if (int rc = timetable_profiles(h, planner->speed, n_points, params, plans, call))
+		return rc;
+	return timetable_plans(h, planner->timetable, planner->speed, plans, call, values_host, plans_host, stops_host, results_host);
 }
 
 int pp_planner_locate(pp_planner* planner, int32_t n_queries, const double* poses_host, const double* from_length, const double* to_length, const pp_locate_params* params,

@@ -1021,6 +1021,7 @@ struct RRTStarParameters {
 /// Stamp(tickets, into, spacing) writes the cells held plans sweep into a map's occupancy grid (pp_pipeline_stamp): the reservation map of the next vehicle.
 /// Locate(tickets, poses, spacing) finds each vehicle on its held plan (pp_pipeline_locate): the arc length that windows Stamp, the errors a controller steers on.
 /// SpeedProfile(tickets, spacing, limits) gives the speed and the arrival time at every sample of a held plan (pp_pipeline_speed_profile): what a controller tracks at s.
+/// Timetable(tickets, values) asks that timetable at arc lengths or times and lists a plan's stops (pp_pipeline_timetable): the set-point and the lateness at the located s.
 class HybridAStarPipeline {
 public:
 	struct Result {
@@ -1675,6 +1676,99 @@ public:
 		out.numBoxes = sum.n_boxes;
 		out.numBoxed = sum.n_boxed;
 		out.reach = sum.reach;
+		return out;
+	}
+	/// What Timetable says about one held plan (pp_timetable_plan), its listed stops (pp_timetable_stop) and its look-ups (pp_timetable_result)
+	struct Timetabled {
+		enum class Status { Profiled = 0, NoProfile = -1 };
+		struct Stop {
+			int row = 0;
+			double s = 0.0, tArrive = 0.0, tDepart = 0.0;
+		};
+		struct LookUp {
+			enum class Status { Inside = 0, Before = 1, Behind = 2, NoProfile = -1 };
+			Status status = Status::NoProfile;
+			int row = 0, edge = 0, direction = 0;
+			double s = 0.0, t = 0.0, v = 0.0, a = 0.0, ratio = 0.0, kappa = 0.0;
+			Pose2d pose;
+			int nextStop = -1; // index into `stops`; -1: none listed behind the look-up
+			double sToStop = 0.0, tToStop = 0.0, tRemaining = 0.0;
+		};
+		Status status = Status::NoProfile;
+		int numSamples = 0, numStops = 0; // numStops > stops.size(): the list was cut at maxStops
+		double sFirst = 0.0, sLast = 0.0, duration = 0.0;
+		std::vector<Stop> stops;
+		std::vector<LookUp> lookUps;
+	};
+	/// Questions to the timetables the LAST SpeedProfile call left on the device (pp_pipeline_timetable; include/pp_hip.h has the definition), without the rows
+	/// coming down: values[i] are arc lengths along plan i (byTime false: the s Locate returned gives the set-point speed and the time the timetable has the
+	/// vehicle there) or seconds since its start (byTime true); every look-up gives row, s, t, v, a, the pose with its edge, ratio, direction and curvature, and
+	/// the next listed stop with the distance and the time to it.  The stops of a plan are its standing samples in row order, each with its arrival and its
+	/// departure (a cusp stop dwells in between); the first maxStops are listed.  values: empty (stops only), or one vector per ticket, all of one length.
+	/// Legal beside queries in flight.
+	std::vector<Timetabled> Timetable(const std::vector<uint64_t>& tickets, const std::vector<std::vector<double>>& values, bool byTime = false, int maxStops = 16)
+	{
+		for (uint64_t t : tickets)
+			HeldOf(t); // (throws for a ticket that is not held)
+		const size_t n = tickets.size();
+		if (!values.empty() && values.size() != n)
+			throw std::invalid_argument("Timetable: values is empty or holds one vector per ticket");
+		const size_t P = values.empty() ? 0 : values[0].size();
+		for (const auto& v : values)
+			if (v.size() != P)
+				throw std::invalid_argument("Timetable: every ticket gets the same number of values");
+		std::vector<Timetabled> out(n);
+		if (!m_pipe || n == 0)
+			return out;
+		std::vector<double> flat;
+		for (const auto& v : values)
+			flat.insert(flat.end(), v.begin(), v.end());
+		const pp_timetable_params tp { byTime ? 1 : 0, maxStops, { 0, 0 } };
+		const size_t room = maxStops > 0 ? (size_t)maxStops : 0;
+		std::vector<pp_timetable_plan> plans(n);
+		std::vector<pp_timetable_stop> stops(n * room + 1);
+		std::vector<pp_timetable_result> results(n * P + 1);
+		ppCheck(pp_pipeline_timetable(m_pipe, (int32_t)n, tickets.data(), (int32_t)P, flat.empty() ? nullptr : flat.data(), &tp, plans.data(), stops.data(), results.data()));
+		for (size_t i = 0; i < n; i++) {
+			Timetabled& o = out[i];
+			o.status = (Timetabled::Status)plans[i].status;
+			o.numSamples = plans[i].n_samples;
+			o.numStops = plans[i].n_stops;
+			o.sFirst = plans[i].s_first;
+			o.sLast = plans[i].s_last;
+			o.duration = plans[i].duration;
+			for (int k = 0; k < plans[i].n_listed; k++) {
+				const pp_timetable_stop& st = stops[i * room + (size_t)k];
+				Timetabled::Stop stop;
+				stop.row = st.row;
+				stop.s = st.s;
+				stop.tArrive = st.t_arrive;
+				stop.tDepart = st.t_depart;
+				o.stops.push_back(stop);
+			}
+			for (size_t p = 0; p < P; p++) {
+				const pp_timetable_result& r = results[i * P + p];
+				Timetabled::LookUp u;
+				u.status = (Timetabled::LookUp::Status)r.status;
+				u.row = r.row;
+				u.edge = r.edge;
+				u.direction = r.direction;
+				u.s = r.s;
+				u.t = r.t;
+				u.v = r.v;
+				u.a = r.a;
+				u.ratio = r.ratio;
+				u.kappa = r.kappa;
+				u.pose.x() = r.pose[0]; // (the record's doubles as they are: the constructor would wrap theta)
+				u.pose.y() = r.pose[1];
+				u.pose.theta = r.pose[2];
+				u.nextStop = r.next_stop;
+				u.sToStop = r.s_to_stop;
+				u.tToStop = r.t_to_stop;
+				u.tRemaining = r.t_remaining;
+				o.lookUps.push_back(u);
+			}
+		}
 		return out;
 	}
 	/// HybridAStar::GetPath() of a held query: after PostProcess the sampled and, when the smoother succeeded, smoothed path; before it the

@@ -597,6 +597,54 @@ PYBIND11_MODULE(pyplanning, m)
 			"every pair the rule lists.  t_from, t_to, dt, margin, hold_before and hold_after are those of the call the list is meant for.",
 			py::arg("tickets"), py::arg("t_start"), py::arg("times_per_box") = 64, py::arg("max_delay_steps") = 0, py::arg("boxes") = false, py::arg("max_pairs") = py::none(),
 			py::arg("t_from") = 0.0, py::arg("t_to") = 60.0, py::arg("dt") = 0.1, py::arg("margin") = 0.0, py::arg("hold_before") = false, py::arg("hold_after") = false)
+		.def("timetable",
+			[](HybridAStarPipeline& h, const std::vector<uint64_t>& tickets, const std::vector<std::vector<double>>& values, const std::string& by, int maxStops) {
+				if (by != "length" && by != "time")
+					throw std::invalid_argument("timetable: by is \"length\" or \"time\"");
+				const auto r = h.Timetable(tickets, values, by == "time", maxStops);
+				py::list plans, stops, results;
+				for (const auto& p : r) {
+					py::dict plan;
+					plan["status"] = (int)p.status;
+					plan["n_samples"] = p.numSamples;
+					plan["n_stops"] = p.numStops;
+					plan["n_listed"] = p.stops.size();
+					plan["s_first"] = p.sFirst;
+					plan["s_last"] = p.sLast;
+					plan["duration"] = p.duration;
+					plans.append(plan);
+					py::list listed, looked;
+					for (const auto& st : p.stops)
+						listed.append(py::make_tuple(st.row, st.s, st.tArrive, st.tDepart));
+					for (const auto& u : p.lookUps) {
+						py::dict d;
+						d["status"] = (int)u.status;
+						d["row"] = u.row;
+						d["edge"] = u.edge;
+						d["direction"] = u.direction;
+						d["s"] = u.s;
+						d["t"] = u.t;
+						d["v"] = u.v;
+						d["a"] = u.a;
+						d["ratio"] = u.ratio;
+						d["kappa"] = u.kappa;
+						d["pose"] = py::make_tuple(u.pose.x(), u.pose.y(), u.pose.theta);
+						d["next_stop"] = u.nextStop;
+						d["s_to_stop"] = u.sToStop;
+						d["t_to_stop"] = u.tToStop;
+						d["t_remaining"] = u.tRemaining;
+						looked.append(d);
+					}
+					stops.append(listed);
+					results.append(looked);
+				}
+				return py::make_tuple(plans, stops, results);
+			},
+			"questions to the timetables the last speed_profile call left on the device: values holds one list per ticket (all of one length; empty: stops only) of arc "
+			"lengths (by=\"length\") or seconds since the plan's start (by=\"time\").  Returns (plans, stops, results): per ticket a dict (status, n_samples, n_stops, "
+			"n_listed, s_first, s_last, duration), the list of its first max_stops stops as (row, s, t_arrive, t_depart), and per value a dict (status 0 inside the "
+			"profile, 1 before, 2 behind it, -1 no profile; row, edge, direction, s, t, v, a, ratio, kappa, pose, next_stop, s_to_stop, t_to_stop, t_remaining).",
+			py::arg("tickets"), py::arg("values"), py::arg("by") = "length", py::arg("max_stops") = 16)
 		.def("get_path", &HybridAStarPipeline::GetPath, py::arg("ticket"))
 		.def("get_graph_search_path", &HybridAStarPipeline::GetGraphSearchPath, py::arg("ticket"))
 		.def("get_smoothing_status", &HybridAStarPipeline::GetSmoothingStatus, py::arg("ticket"))

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (RS_PATH_DTYPE, ConflictParams, ConflictResult, DelayParams, DelayResult, FootprintDisc, HybridParams, LocateParams, LocateResult, MapDesc, PairParams, PairSummary, PostResult, QueryResult, RevalidateResult,
-                   SmootherParams, SpeedProfileParams, SpeedProfileResult, StampParams, StampResult, TrackResult, TrackSet, TrajectoryResult, check, ptr)
+                   SmootherParams, SpeedProfileParams, SpeedProfileResult, StampParams, StampResult, TimetableParams, TimetablePlan, TimetableResult, TimetableStop, TrackResult, TrackSet, TrajectoryResult, check, ptr)
 
 
 class Status:
@@ -739,6 +739,12 @@ class HybridAStarBatch:
         return _candidate_pairs(n, t_start, times_per_box, max_delay_steps, boxes, max_pairs, lattice,
                                 lambda ts, pp, pr, fb, bx, sm: self.lib.pp_planner_candidate_pairs(self.h, n, ptr(ts), C.byref(pp), ptr(pr), ptr(fb), ptr(bx), C.byref(sm)))
 
+    def timetable(self, values, n_queries=None, by="length", max_stops=16):
+        """Look-ups into the timetables of the first n queries of the last batch and the lists of their stops: pp_planner_timetable, the batch form of
+        HybridAStarPipeline.timetable, with the same arguments and return value."""
+        n = len(self._results) if n_queries is None else int(n_queries)
+        return _timetable(n, values, by, max_stops, lambda P, v, tp, pl, st, out: self.lib.pp_planner_timetable(self.h, n, P, ptr(v), C.byref(tp), ptr(pl), ptr(st), ptr(out)))
+
     def certify_lattice(self, q):
         """SURVEY 7.3 H2 as a contract (pp_planner_certify_lattice): created nodes and logged lattice-line children of query q recomputed on
         the host with glibc; returns (checked, cell mismatches, unverified events, largest pose difference).  mismatches == unverified == 0
@@ -1151,6 +1157,22 @@ class HybridAStarPipeline:
                                 lambda ts, pp, pr, fb, bx, sm: self.lib.pp_pipeline_candidate_pairs(self.h, len(t), ptr(t), ptr(ts), C.byref(pp), ptr(pr), ptr(fb), ptr(bx),
                                                                                                     C.byref(sm)))
 
+    def timetable(self, tickets, values, by="length", max_stops=16):
+        """Ask the timetables of the completed, HELD queries `tickets` -- the (s, v, t) rows the last speed_profile() call left on the device -- without
+        downloading them: pp_pipeline_timetable, whose definition is in include/pp_hip.h.  `values` is [n, P] (a scalar or [P]: the same for every
+        plan): arc lengths in metres with by="length" (the s a locate() call returned gives the set-point speed v, and t, whose difference to the clock
+        is the vehicle's lateness and whose now - t is the t_start that re-anchors a vehicle under way for conflicts() and deconflict()), or times in
+        seconds since the plan's start with by="time".  Returns three numpy record arrays: plans [n] of TIMETABLE_PLAN_DTYPE (status, n_samples,
+        n_stops, n_listed, s_first, s_last, duration), stops [n, max_stops] of TIMETABLE_STOP_DTYPE (row, s, t_arrive, t_depart; the first n_listed
+        rows of a plan are its stops in row order -- every sample with v == 0 -- the others zero) and results [n, P] of TIMETABLE_DTYPE (status 0 inside
+        the profile, 1 before and 2 behind it, -1 without a profile; row, edge, direction, s, t, v, a, ratio, kappa, pose, next_stop -- an index into the
+        plan's listed stops, -1: none -- s_to_stop, t_to_stop, t_remaining).  Legal beside queries in flight.
+        Raises PPError, with nothing launched, for everything conflicts() refuses about the tickets and a missing speed profile, for max_stops outside
+        0 .. 2^16, more than 2^26 look-ups and a value that is not finite."""
+        t = np.ascontiguousarray(tickets, dtype=np.uint64).reshape(-1)
+        return _timetable(len(t), values, by, max_stops,
+                          lambda P, v, tp, pl, st, out: self.lib.pp_pipeline_timetable(self.h, len(t), ptr(t), P, ptr(v), C.byref(tp), ptr(pl), ptr(st), ptr(out)))
+
     def get_expanded_of(self, ticket):
         """expansion sequence (log_expansions=True) of a completed query polled with release=False"""
         slot = self.lib.pp_pipeline_slot_of(self.h, C.c_uint64(int(ticket)))
@@ -1327,6 +1349,34 @@ def _candidate_pairs(n, t_start, times_per_box, max_delay_steps, boxes, max_pair
         assert box.shape[1] == summary.n_boxes, (box.shape, summary.n_boxes)
     out = (pairs[:summary.n_written], first[:summary.n_written], summary)
     return out + (box,) if boxes else out
+
+
+# pp_timetable_plan, pp_timetable_stop and pp_timetable_result as numpy records: what a timetable call returns
+TIMETABLE_PLAN_DTYPE = np.dtype([("status", np.int32), ("n_samples", np.int32), ("n_stops", np.int32), ("n_listed", np.int32), ("s_first", np.float64), ("s_last", np.float64),
+                                 ("duration", np.float64)])
+TIMETABLE_STOP_DTYPE = np.dtype([("row", np.int32), ("reserved", np.int32), ("s", np.float64), ("t_arrive", np.float64), ("t_depart", np.float64)])
+TIMETABLE_DTYPE = np.dtype([("status", np.int32), ("row", np.int32), ("edge", np.int32), ("direction", np.int32), ("s", np.float64), ("t", np.float64), ("v", np.float64),
+                            ("a", np.float64), ("ratio", np.float64), ("kappa", np.float64), ("pose", np.float64, 3), ("next_stop", np.int32), ("reserved", np.int32),
+                            ("s_to_stop", np.float64), ("t_to_stop", np.float64), ("t_remaining", np.float64), ("reserved1", np.float64)])
+assert TIMETABLE_PLAN_DTYPE.itemsize == C.sizeof(TimetablePlan) and TIMETABLE_STOP_DTYPE.itemsize == C.sizeof(TimetableStop) and TIMETABLE_DTYPE.itemsize == C.sizeof(TimetableResult)
+
+
+def _timetable(n, values, by, max_stops, call):
+    """the values and parameters of a timetable call, the call, its three record arrays (no object per record)"""
+    if by not in ("length", "time"):
+        raise ValueError('by is "length" or "time", got %r' % (by,))
+    v = np.asarray(values, dtype=np.float64)
+    if v.ndim < 2:
+        v = np.broadcast_to(v.reshape(1, -1), (n, v.size))
+    if v.ndim != 2 or v.shape[0] != n:
+        raise ValueError("values is [n, P] with one row per plan: got %s for %d plans" % (v.shape, n))
+    v = np.ascontiguousarray(v)
+    P, M = int(v.shape[1]), int(max_stops)
+    plans = np.zeros(max(n, 1), dtype=TIMETABLE_PLAN_DTYPE)
+    stops = np.zeros((max(n, 1), max(M, 1)), dtype=TIMETABLE_STOP_DTYPE)
+    out = np.zeros((max(n, 1), max(P, 1)), dtype=TIMETABLE_DTYPE)
+    check(call(P, v if v.size else None, TimetableParams(0 if by == "length" else 1, M), plans, stops, out))
+    return plans[:n].view(np.recarray), stops[:n, :max(M, 0)].view(np.recarray), out[:n, :P].view(np.recarray)
 
 
 # pp_track_result as a numpy record: a deconflict_tracks call returns an [n, M] array of these
