@@ -1056,6 +1056,84 @@ int pp_pipeline_timetable(pp_pipeline* pipeline, int32_t n, const uint64_t* tick
 /* The same kernel over the first n_queries queries of the planner's last batch, as pp_planner_conflicts is to pp_pipeline_conflicts. */
 int pp_planner_timetable(pp_planner* planner, int32_t n_queries, int32_t n_points, const double* values_host, const pp_timetable_params* params,
 	pp_timetable_plan* plans_host, pp_timetable_stop* stops_host, pp_timetable_result* results_host);
+/* ---- waits at stops that clear conflicts, by priority and ticket ---------------------------------------------------------------------------------
+ * A start delay fits a vehicle that has not left; one under way can still wait where its timetable already has it standing: at a cusp stop, a
+ * sample with v_j == 0.  This call is the delay call with such waits as further candidates, and with waits already committed as an input, so that
+ * it can be called in a loop.  No plan data leaves the device; it reads no map and writes nothing but its own buffers, so the call is legal beside
+ * queries in flight.  Every expression is in double, in the order written.
+ *  Lattice. Lattice, profiles, position, pose, discs, separation, hold flags, priority, pair list, levels and D = max_delay_steps are exactly those
+ *           of "start delays that clear conflicts" for params->delay.  The extended trajectory is k_trajectory_tickets, unchanged, over the lattice
+ *           indices k0 - D .. k1: T + D columns, column c with tau_c = (double)(k0 - D + c) * dt and u_c = tau_c - t_start[i].
+ *  Stops.   The stops of a plan are the timetable call's: a row j with v_j == 0.0, t_arrive as there.  The ARRIVE COLUMN a of a stop is the smallest
+ *           c in 0 .. T + D - 1 with u_c >= t_arrive, or T + D if there is none (u_c never decreases in c: a binary search).  The STANDING POSE of a
+ *           stop is the conflict call's "Pose" at s_j; sin and cos of its heading come from the sincos call k_trajectory_tickets makes.  So wherever
+ *           a column falls inside the stop's dwell (t_arrive <= u_c <= t_depart) the standing pose equals that column's x, y, theta, s, sin and cos
+ *           bit for bit.
+ *  Places.  The places of a FREE vehicle are its stops with 0 < row < N - 1 and D <= a < T + D -- stops reached inside the horizon k0 .. k1 -- in row
+ *           order, the first max_places of them; a stop reached before k0 or never is skipped and takes no slot of the list.  A free vehicle may
+ *           also wait at its START unless no_start_wait[i] != 0: that is place -1, and it is the delay call's delay.
+ *  Position under a wait (place, d) at lattice time m, with c = m + D.  No wait, or d == 0: column c.  The start: column c - d.  A stop with arrive
+ *           column a: c < a gives column c; a <= c < a + d gives PRESENT, AT THE STANDING POSE, with arc length s_j; otherwise column c - d.  A NaN
+ *           column is "absent", as before.  A wait of zero steps is no wait: it is reported as place -2.
+ *  Candidates of a free vehicle, in this order: d = 0; then, for d = 1 .. D, the start (if allowed) and then the listed places in ascending order.
+ *           The first candidate that is CLEAR is taken: at no m, against no scheduled partner j < i under that partner's own wait, are both present
+ *           with separation < margin.  n_tried is the chosen candidate's ordinal plus one, and the number of candidates for status 1.  blocker,
+ *           t_block and s_block describe the LAST REJECTED candidate by its least key (m, j), as in the delay call; s_block is read through the
+ *           position rule.  (If the d = 0 candidate's least key is at time m0, a candidate (stop q, d) with a_q > m0 + D is where d = 0 was at every
+ *           time up to m0, so it is rejected with that same key: the kernel counts and records such a candidate without evaluating it.)
+ *  Fixed.   A vehicle with fixed != NULL and fixed[i].row != -2 is not decided: its one candidate is (fixed[i].row, fixed[i].steps).  row == -1 is a
+ *           start wait; row >= 0 a wait at that row, which must be a stop (v_row == 0, any row 0 .. N - 1) with a < T + D -- no lower bound on a:
+ *           the vehicle may stand there already.  A row that does not qualify gives status -2, and the vehicle is ignored like one of status -1.  A
+ *           qualifying fixed vehicle is ALWAYS scheduled: status 0 if its candidate is clear, else 2 with the blocker filled in; the vehicles below
+ *           see it either way.  Its list of places is its one row (place 0).
+ *  Status 1 of a free vehicle: no candidate was clear; the vehicles below it are scheduled as if it were absent, as in the delay call.
+ *  Caveat.  A standing pose is not a trajectory column: it lies on the path between columns a - 1 and a.  pp_*_candidate_pairs' guarantee therefore
+ *           covers waits only if that call's margin is increased by the longest step, v_peak * dt.  This call does not do that.
+ *  - PP_ERR_INVALID, nothing launched, the holder usable as before: every refusal of the delay call; max_places outside 0 .. 2^10; reserved != 0; a
+ *    no_start_wait value other than 0 or 1; a fixed row < -2; fixed steps outside 0 .. D.  n == 0 is PP_OK.
+ *  - no_start_wait, fixed and each of the three outputs may be NULL.  places_host is [n][max(max_places, 1)]; rows behind a vehicle's n_places are
+ *    left as they are.
+ *  - The holder owns, beside the delay call's buffers, 8 + 1 + 4 + 16 + 80 bytes per plan and 64 per plan and place, kept aside like the others when
+ *    they have to grow beside queries in flight (k_wait_places, one wave per plan; k_wait_level, one wave per vehicle of a level). */
+typedef struct pp_wait_params {
+	pp_delay_params delay;  /* the delay call's: lattice, margin, hold flags, D */
+	int32_t max_places;     /* 0 .. 2^10: stops listed per free vehicle; 0: start waits only */
+	int32_t reserved;       /* zero */
+} pp_wait_params;           /* 56 bytes */
+typedef struct pp_wait_fixed {
+	int32_t row;            /* -2 free: the call decides; -1 a wait at the start; >= 0 a wait at that row of the profile */
+	int32_t steps;          /* 0 .. D */
+} pp_wait_fixed;            /* 8 bytes */
+typedef struct pp_wait_result {
+	int32_t status;         /* 0 scheduled; 1 no candidate is clear; 2 a fixed wait in conflict (scheduled); -1 the ticket's profile has status != 0;
+	                           -2 the fixed row does not qualify */
+	int32_t place;          /* -2 no wait; -1 the start; >= 0 the index in the vehicle's listed places */
+	int32_t row;            /* the stop's row; else -1 */
+	int32_t wait_steps;     /* d; -1 unless scheduled */
+	int32_t n_tried;
+	int32_t blocker;        /* as pp_delay_result::blocker */
+	double  t_start;        /* the effective start t_start[i] + (double)d * dt without a wait (d = 0) and for a start wait, as pp_delay_result::t_start;
+	                           t_start[i] itself for a wait at a stop and for status 1 */
+	double  t_hold;         /* (double)(k0 - D + a) * dt: the lattice time from which the vehicle stands */
+	double  t_resume;       /* (double)(k0 - D + a + d) * dt: the first lattice time it is on its shifted trajectory again */
+	double  s_wait;         /* the stop's arc length */
+	double  t_block;
+	double  s_block[2];
+} pp_wait_result;           /* 80 bytes; t_hold, t_resume and s_wait are zero without a wait at a stop; for status -1 and -2 every field but status,
+                               place, row, wait_steps and blocker is zero */
+typedef struct pp_wait_place {
+	int32_t row, column;    /* the stop's row j and its arrive column a */
+	double  s, t_arrive;
+	double  pose[3];        /* the standing pose */
+	double  sin_theta, cos_theta;
+} pp_wait_place;            /* 64 bytes */
+int pp_pipeline_deconflict_waits(pp_pipeline* pipeline, int32_t n, const uint64_t* tickets, const double* t_start /* [n], finite */,
+	const uint8_t* no_start_wait /* may be NULL; [n], 0 or 1 */, const pp_wait_fixed* fixed /* may be NULL; [n] */, int32_t n_pairs,
+	const int32_t* pairs /* may be NULL */, const pp_wait_params* params, int32_t* n_places_host /* may be NULL; [n] */,
+	pp_wait_place* places_host /* may be NULL; [n][max(max_places, 1)] */, pp_wait_result* results_host /* may be NULL; [n] */);
+/* The same kernels over the first n_queries queries of the planner's last batch, as pp_planner_deconflict is to pp_pipeline_deconflict. */
+int pp_planner_deconflict_waits(pp_planner* planner, int32_t n_queries, const double* t_start, const uint8_t* no_start_wait, const pp_wait_fixed* fixed,
+	int32_t n_pairs, const int32_t* pairs, const pp_wait_params* params, int32_t* n_places_host, pp_wait_place* places_host, pp_wait_result* results_host);
 /* Diagnostics: waves of the search grid that are alive right now (a blocking device-to-host copy; -1 on error). */
 int pp_pipeline_alive_waves(pp_pipeline* pipeline);
 pp_planner* pp_pipeline_planner(pp_pipeline* pipeline);           /* the buffer set: set_nonholo_table, set_primitives, get_path(slot), ... */

@@ -191,6 +191,33 @@ class TimetableResult(C.Structure):
                 ("s_to_stop", C.c_double), ("t_to_stop", C.c_double), ("t_remaining", C.c_double), ("reserved1", C.c_double)]
 
 
+class WaitParams(C.Structure):
+    """pp_wait_params: the delay call's parameters and max_places (0 .. 2^10 stops listed per free vehicle; 0: start waits only); reserved is zero"""
+    _fields_ = [("delay", DelayParams), ("max_places", C.c_int32), ("reserved", C.c_int32)]
+
+
+class WaitFixed(C.Structure):
+    """pp_wait_fixed: a wait already committed -- row -2 free (the call decides), -1 a wait at the start, >= 0 a wait at that row of the profile; steps
+    0 .. max_delay_steps"""
+    _fields_ = [("row", C.c_int32), ("steps", C.c_int32)]
+
+
+class WaitResult(C.Structure):
+    """pp_wait_result: status 0 scheduled, 1 no candidate is clear, 2 a fixed wait in conflict (scheduled), -1 no profile, -2 the fixed row does not
+    qualify; the place (-2 no wait, -1 the start, >= 0 the index in the vehicle's listed places), the stop's row, the steps waited, the candidates
+    tried, the blocker, the effective start, the lattice times from which the vehicle stands and at which it moves again, the stop's arc length, and
+    the lattice time and the two arc lengths of the last rejected candidate's first conflict"""
+    _fields_ = [("status", C.c_int32), ("place", C.c_int32), ("row", C.c_int32), ("wait_steps", C.c_int32), ("n_tried", C.c_int32), ("blocker", C.c_int32),
+                ("t_start", C.c_double), ("t_hold", C.c_double), ("t_resume", C.c_double), ("s_wait", C.c_double), ("t_block", C.c_double), ("s_block", C.c_double * 2)]
+
+
+class WaitPlace(C.Structure):
+    """pp_wait_place: a stop a vehicle may wait at -- its row, its arrive column in the extended trajectory, its arc length and arrival time, the
+    standing pose and the sine and cosine of its heading"""
+    _fields_ = [("row", C.c_int32), ("column", C.c_int32), ("s", C.c_double), ("t_arrive", C.c_double), ("pose", C.c_double * 3), ("sin_theta", C.c_double),
+                ("cos_theta", C.c_double)]
+
+
 class TrackSet(C.Structure):
     """pp_track_set: M tracked movers for a deconflict_tracks call -- host pointers to offsets [M + 1] (int32, offsets[0] == 0, strictly increasing),
     waypoints [offsets[M]][3] (t, x, y; t strictly increasing within a track) and radii [M] (>= 0); reserved is zero"""
@@ -353,6 +380,8 @@ def load():
     L.pp_planner_candidate_pairs.argtypes = [vp, C.c_int32, vp, C.POINTER(PairParams), vp, vp, vp, C.POINTER(PairSummary)]
     L.pp_pipeline_timetable.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.POINTER(TimetableParams), vp, vp, vp]
     L.pp_planner_timetable.argtypes = [vp, C.c_int32, C.c_int32, vp, C.POINTER(TimetableParams), vp, vp, vp]
+    L.pp_pipeline_deconflict_waits.argtypes = [vp, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, C.POINTER(WaitParams), vp, vp, vp]
+    L.pp_planner_deconflict_waits.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, vp, C.POINTER(WaitParams), vp, vp, vp]
     L.pp_pipeline_timings.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.pp_pipeline_backlog.argtypes = [vp, vp, vp]
     L.pp_pipeline_planner.argtypes = [vp]

@@ -336,6 +336,35 @@ def build_timetable_rule_test(verbose=True):
     return out
 
 
+def build_pipeline_deconflict_waits_test(verbose=True):
+    """tests/cpp/test_pipeline_deconflict_waits.cpp: DeconflictWaits(tickets, starts) of HybridAStarPipeline against a plain sequential loop over the poses Conflicts
+    returns and the places the call returns (run on the GPU box)."""
+    build()
+    out = os.path.join(LIB_DIR, "test_pipeline_deconflict_waits")
+    src = os.path.join(HERE, "..", "tests", "cpp", "test_pipeline_deconflict_waits.cpp")
+    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", src, "-o", out, "-L" + LIB_DIR, "-lpphip", "-Wl,-rpath,$ORIGIN"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return out
+
+
+def build_wait_rule_test(verbose=True):
+    """tests/cpp/test_wait_rule.cpp: the arrive column, the position under a wait, the place filter, the candidate order and the shortcut's predicate
+    (csrc/pp_wait_rule.hpp) alone, on the CPU, under the address and undefined-behaviour sanitizers; without contraction, as the library is built."""
+    os.makedirs(LIB_DIR, exist_ok=True)
+    out = os.path.join(LIB_DIR, "test_wait_rule")
+    src = os.path.join(HERE, "..", "tests", "cpp", "test_wait_rule.cpp")
+    headers = [os.path.join(CSRC, "pp_wait_rule.hpp")]
+    if os.path.exists(out) and os.path.getmtime(out) > max(os.path.getmtime(f) for f in [src] + headers):
+        return out
+    cmd = ["g++", "-std=c++17", "-g", "-O1", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC, src, "-o", out]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return out
+
+
 def build_ticket_table_test(verbose=True):
     """tests/cpp/test_ticket_table.cpp: the pipeline's slot and ticket bookkeeping (csrc/pp_ticket_table.hpp) alone, on the CPU, under the address and
     undefined-behaviour sanitizers."""
@@ -388,5 +417,7 @@ if __name__ == "__main__":
     print(build_pair_rule_test())
     print(build_pipeline_timetable_test())
     print(build_timetable_rule_test())
+    print(build_pipeline_deconflict_waits_test())
+    print(build_wait_rule_test())
     print(build_ticket_table_test())
     print(build_row_test())

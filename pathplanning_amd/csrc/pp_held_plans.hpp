@@ -2,8 +2,8 @@
 // names their argument types) and in front of pp_planner and pp_pipeline, which both keep one buffer group per service.
 //
 // Finished plans (path records, Reeds-Shepp log, result record) are held by a batch planner, as queries 0 .. n-1 of its last batch, or by a pipeline, as
-// the slots of held tickets.  A service over them -- post-processing, re-validation, the stamp, the locate call, the speed profile, the conflict call, the delay call without and with tracked movers, the broad phase, the timetable look-ups -- has one core (post_process_plans,
-// revalidate_plans, stamp_plans, locate_plans, speed_profile_plans, conflict_plans, deconflict_plans, deconflict_tracks_plans, candidate_pairs_plans, timetable_plans in pp_planner.hip) that takes a HeldPlans and goes through held_grow and held_run; its two extern "C"
+// the slots of held tickets.  A service over them -- post-processing, re-validation, the stamp, the locate call, the speed profile, the conflict call, the delay call without and with tracked movers, the broad phase, the timetable look-ups, the waits at stops -- has one core (post_process_plans,
+// revalidate_plans, stamp_plans, locate_plans, speed_profile_plans, conflict_plans, deconflict_plans, deconflict_tracks_plans, candidate_pairs_plans, timetable_plans, deconflict_waits_plans in pp_planner.hip) that takes a HeldPlans and goes through held_grow and held_run; its two extern "C"
 // entries check what is the holder's own and describe the holder (batch_plans, pipe_plans).
 #pragma once
 
@@ -146,6 +146,20 @@ struct TimetableGroup {
 	size_t lookups = 0; // look-ups they hold (8 + 128 bytes each)
 	pph::Dev<pp_timetable_stop> stops;
 	size_t listed = 0; // stops `stops` holds (32 bytes each)
+};
+
+/// What the call with waits at stops adds to the delay call's buffers (it forms its extended trajectory in ConflictGroup's `rec` and `traj` and keeps its level
+/// order and partner lists in DelayGroup's, as the delay call does): per plan the committed wait, the start-wait flag, the count of its places and the wait it
+/// was given (what the vehicles below read); the places, max(max_places, 1) rows per plan; the records
+struct WaitGroup {
+	pph::Dev<pp_wait_fixed> fixed;
+	pph::Dev<uint8_t> noStart;
+	pph::Dev<int32_t> counts;
+	pph::Dev<WaitState> states;
+	pph::Dev<pp_wait_result> out;
+	size_t vehicles = 0; // plans they hold
+	pph::Dev<pp_wait_place> places;
+	size_t listed = 0; // places `places` holds (64 bytes each)
 };
 
 /// Buffers that hold `capacity` units are made to hold `wanted` ({buffer, bytes}; 0 bytes: the holder does not use it).  A holder that may not free now

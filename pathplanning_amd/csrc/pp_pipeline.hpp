@@ -213,6 +213,7 @@ struct pp_pipeline {
 	TrackGroup track;
 	PairGroup pair;
 	TimetableGroup timetable;
+	WaitGroup wait;
 	std::vector<pph::DeviceMem> heldParked; // their buffers outgrown while queries were in flight: hipFree waits for the whole device (the persistent grid
 	                                        // included), so they are kept until a call finds nothing in flight (or the pipeline goes): held_grow
 	int nWf = 2;      // wavefront streams in use: consecutive submissions' launches overlap (the tail of one under the head of the next)
@@ -1294,6 +1295,26 @@ int pp_pipeline_timetable(pp_pipeline* P, int32_t n, const uint64_t* tickets, in
 	if (int rc = timetable_profiles(h, P->speed, n_points, params, plans, call))
 		return rc;
 	return timetable_plans(h, P->timetable, P->speed, plans, call, values_host, plans_host, stops_host, results_host);
+}
+
+/// Waits at the start or at stops that clear the conflicts of n completed, held queries with their pair partners of higher priority (include/pp_hip.h;
+/// deconflict_waits_plans): legal beside queries in flight
+int pp_pipeline_deconflict_waits(pp_pipeline* P, int32_t n, const uint64_t* tickets, const double* t_start, const uint8_t* no_start_wait, const pp_wait_fixed* fixed,
+	int32_t n_pairs, const int32_t* pairs, const pp_wait_params* params, int32_t* n_places_host, pp_wait_place* places_host, pp_wait_result* results_host)
+{
+	HeldPlans h;
+	if (int rc = pipe_plans(P, n, tickets, h))
+		return rc;
+	ConflictLattice lattice;
+	if (int rc = wait_check(h, t_start, no_start_wait, fixed, n_pairs, pairs, params, lattice))
+		return rc;
+	if (int rc = pipe_resolve(P, n, tickets, "scheduled", true, h.slots))
+		return rc;
+	std::vector<ConflictArg> plans;
+	if (int rc = conflict_profiles(h, P->speed, t_start, lattice, plans))
+		return rc;
+	return deconflict_waits_plans(h, P->conflict, P->delay, P->wait, P->speed, plans, lattice, params, no_start_wait, fixed, n_pairs, pairs, n_places_host, places_host,
+		results_host);
 }
 
 /// Launch durations seen so far (HIP events on the launching streams; harvested by pp_pipeline_poll) and reset.  Wavefront: one launch per

@@ -22,6 +22,7 @@
 #include "pp_speed_rule.hpp"
 #include "pp_conflict_rule.hpp"
 #include "pp_delay_rule.hpp"
+#include "pp_wait_rule.hpp"
 #include "pp_track_rule.hpp"
 #include "pp_pair_rule.hpp"
 #include "pp_timetable_rule.hpp"
@@ -323,6 +324,8 @@ struct PipeView {
 #include "pp_pairs.hpp"
 // questions to a plan's timetable: look-ups by arc length or by time and the list of its stops (one wave per plan)
 #include "pp_timetable.hpp"
+// waits at the start or at a timetable's stops that clear conflicts, by priority (one wave per plan lists the places, then one wave per vehicle of a level)
+#include "pp_waits.hpp"
 
 } // namespace
 
@@ -393,6 +396,7 @@ struct pp_planner {
 	TrackGroup track;
 	PairGroup pair;
 	TimetableGroup timetable;
+	WaitGroup wait;
 };
 
 namespace {
@@ -574,6 +578,33 @@ hipError_t launch_timetable(hipStream_t s, const SearchArgs& args, const Timetab
 	return hipGetLastError();
 }
 
+/// k_wait_places over `count` plans of buffer set p (count = 0 on a grid of one: the warm-up, which dereferences nothing)
+hipError_t launch_wait_places(hipStream_t s, const SearchArgs& args, const ConflictLattice& lattice, const WaitCall& call, int count, const int32_t* slotsDev,
+	const ConflictArg* argsDev, pp_planner* p, const double* rowsDev, const pp_wait_fixed* fixedDev, pp_wait_place* placesDev, int32_t* countsDev)
+{
+	if (fixedDev)
+		hipLaunchKernelGGL(k_wait_places<true>, dim3(count > 0 ? count : 1), dim3(kWaitLanes), trajectory_lds_bytes(args.maxPath), s, args, lattice, call, count, slotsDev, argsDev,
+			p->paths.get(), p->rsLogs.get(), p->results.get(), rowsDev, fixedDev, placesDev, countsDev);
+	else
+		hipLaunchKernelGGL(k_wait_places<false>, dim3(count > 0 ? count : 1), dim3(kWaitLanes), trajectory_lds_bytes(args.maxPath), s, args, lattice, call, count, slotsDev, argsDev,
+			p->paths.get(), p->rsLogs.get(), p->results.get(), rowsDev, fixedDev, placesDev, countsDev);
+	return hipGetLastError();
+}
+
+/// k_wait_level over the `count` vehicles `membersDev` of one level (count = 0 on a grid of one: the warm-up, which dereferences nothing)
+hipError_t launch_wait_level(hipStream_t s, const Footprint& discs, const ConflictLattice& lattice, const WaitCall& call, int plans, int count, const int32_t* membersDev,
+	const int32_t* offsetsDev, const int32_t* partnersDev, const ConflictArg* argsDev, const double* trajDev, const pp_trajectory_result* plansDev, const pp_wait_fixed* fixedDev,
+	const uint8_t* noStartDev, const pp_wait_place* placesDev, const int32_t* countsDev, WaitState* statesDev, pp_wait_result* outDev)
+{
+	if (discs.anyOffset)
+		hipLaunchKernelGGL(k_wait_level<true>, dim3((unsigned)(count > 0 ? count : 1)), dim3(kWaitLanes), 0, s, discs, lattice, call, plans, count, membersDev, offsetsDev, partnersDev,
+			argsDev, trajDev, plansDev, fixedDev, noStartDev, placesDev, countsDev, statesDev, outDev);
+	else
+		hipLaunchKernelGGL(k_wait_level<false>, dim3((unsigned)(count > 0 ? count : 1)), dim3(kWaitLanes), 0, s, discs, lattice, call, plans, count, membersDev, offsetsDev, partnersDev,
+			argsDev, trajDev, plansDev, fixedDev, noStartDev, placesDev, countsDev, statesDev, outDev);
+	return hipGetLastError();
+}
+
 /// An empty dispatch of each kernel that works on held plans (post-processing in the holder's form), on stream s, which is drained behind each: the queue
 /// allocates their scratch here, where a failure is an error code (see warm_up_kernels).  *service names the service whose kernel failed.
 hipError_t warm_up_held_kernels(pp_planner* p, hipStream_t s, bool byTicket, const char** service)
@@ -603,6 +634,11 @@ hipError_t warm_up_held_kernels(pp_planner* p, hipStream_t s, bool byTicket, con
 		(void)ok("delay levels", launch_delay_level(s, Footprint {}, ConflictLattice {}, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
 	if (e == hipSuccess)
 		(void)ok("timetable", launch_timetable(s, p->args, TimetableCall {}, 0, nullptr, nullptr, p, nullptr, nullptr, nullptr, nullptr, nullptr));
+	// (both forms of k_wait_places have a private segment; the second one's `fixed` is any address that is not null: an empty dispatch dereferences nothing)
+	if (e == hipSuccess && ok("wait places", launch_wait_places(s, p->args, ConflictLattice {}, WaitCall {}, 0, nullptr, nullptr, p, nullptr, nullptr, nullptr, nullptr)) &&
+		ok("wait places", launch_wait_places(s, p->args, ConflictLattice {}, WaitCall {}, 0, nullptr, nullptr, p, nullptr, (const pp_wait_fixed*)p->results.get(), nullptr, nullptr)))
+		(void)ok("wait levels", launch_wait_level(s, Footprint {}, ConflictLattice {}, WaitCall {}, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+			nullptr, nullptr, nullptr, nullptr));
 	return e;
 }
 
@@ -948,6 +984,40 @@ int delay_check(const HeldPlans& h, const double* t_start, int n_pairs, const in
 	if (params->reserved != 0) {
 		set_error("invalid arguments (the delay call's reserved field is zero)");
 		return PP_ERR_INVALID;
+	}
+	return PP_OK;
+}
+
+/// The arguments of a call with waits at stops (pp_planner_deconflict_waits, pp_pipeline_deconflict_waits): the delay call's, the number of places, and per plan the
+/// start-wait flag and the committed wait (either may be NULL)
+int wait_check(const HeldPlans& h, const double* t_start, const uint8_t* no_start_wait, const pp_wait_fixed* fixed, int n_pairs, const int32_t* pairs,
+	const pp_wait_params* params, ConflictLattice& lattice)
+{
+	if (int rc = delay_check(h, t_start, n_pairs, pairs, params ? &params->delay : nullptr, lattice))
+		return rc;
+	if (!params)
+		return PP_OK; // (n == 0)
+	if (params->max_places < 0 || params->max_places > ppw::kMaxPlaces) {
+		set_error("invalid arguments (max_places in 0 .. " + std::to_string(ppw::kMaxPlaces) + ", got " + std::to_string(params->max_places) + ")");
+		return PP_ERR_INVALID;
+	}
+	if (params->reserved != 0) {
+		set_error("invalid arguments (the wait call's reserved field is zero)");
+		return PP_ERR_INVALID;
+	}
+	for (int i = 0; i < h.n; i++) {
+		if (no_start_wait && no_start_wait[i] > 1) {
+			set_error(h.name(i) + " has a no_start_wait flag that is neither 0 nor 1 (" + std::to_string(no_start_wait[i]) + ")");
+			return PP_ERR_INVALID;
+		}
+		if (fixed && fixed[i].row < ppw::kFree) {
+			set_error(h.name(i) + " has a fixed row below -2 (" + std::to_string(fixed[i].row) + ")");
+			return PP_ERR_INVALID;
+		}
+		if (fixed && (fixed[i].steps < 0 || fixed[i].steps > params->delay.max_delay_steps)) {
+			set_error(h.name(i) + " has fixed steps outside 0 .. max_delay_steps = " + std::to_string(params->delay.max_delay_steps) + " (" + std::to_string(fixed[i].steps) + ")");
+			return PP_ERR_INVALID;
+		}
 	}
 	return PP_OK;
 }
@@ -1328,6 +1398,80 @@ int deconflict_plans(const HeldPlans& h, ConflictGroup& c, DelayGroup& g, const 
 		}))
 		return rc;
 	std::copy(recs.begin(), recs.end(), results_host);
+	return PP_OK;
+}
+
+/// Waits at the start or at stops of the plans of h (`plans`, `lattice`: wait_check's and conflict_profiles').  deconflict_plans with three additions on the holder's
+/// stream: the flags and the committed waits go up; k_wait_places lists every plan's places behind the extended trajectory; and every level is k_wait_level.  The
+/// places and their counts come down only for a caller that wants them.  held_run synchronises the stream once.
+int deconflict_waits_plans(const HeldPlans& h, ConflictGroup& c, DelayGroup& g, WaitGroup& w, const SpeedGroup& speed, const std::vector<ConflictArg>& plans,
+	const ConflictLattice& lattice, const pp_wait_params* params, const uint8_t* no_start_wait, const pp_wait_fixed* fixed, int n_pairs, const int32_t* pairs,
+	int32_t* n_places_host, pp_wait_place* places_host, pp_wait_result* results_host)
+{
+	if (h.n == 0)
+		return PP_OK;
+	pp_planner* const pl = h.pl;
+	PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
+	const int D = params->delay.max_delay_steps;
+	const WaitCall call { D, params->max_places, params->max_places > 0 ? params->max_places : 1, 0 };
+	const size_t n = (size_t)h.n, columns = (size_t)lattice.T + (size_t)D, nListed = (size_t)n_pairs, component = n * columns, stride = (size_t)call.stride;
+	std::vector<int32_t> offsets(n + 1), cursor(n), list(nListed), level(n), members(n);
+	ppy::partner_offsets(h.n, n_pairs, pairs, offsets.data());
+	ppy::partner_list(h.n, n_pairs, pairs, offsets.data(), cursor.data(), list.data());
+	const int nLevels = ppy::levels(h.n, offsets.data(), list.data(), level.data());
+	std::vector<int32_t> first((size_t)nLevels + 1);
+	ppy::members_by_level(h.n, nLevels, level.data(), first.data(), members.data());
+	PP_HIP_TRY(held_grow(h, c.doubles, component * kTrajectoryComponents, { { &c.traj, component * kTrajectoryComponents * 8 } }));
+	PP_HIP_TRY(held_grow(h, g.vehicles, n, { { &g.members, n * 4 }, { &g.offsets, (n + 1) * 4 }, { &g.delays, n * 4 } }));
+	if (nListed)
+		PP_HIP_TRY(held_grow(h, g.listed, nListed, { { &g.partners, nListed * 4 } }));
+	PP_HIP_TRY(held_grow(h, w.vehicles, n,
+		{ { &w.fixed, n * sizeof(pp_wait_fixed) }, { &w.noStart, n }, { &w.counts, n * 4 }, { &w.states, n * sizeof(WaitState) }, { &w.out, n * sizeof(pp_wait_result) } }));
+	PP_HIP_TRY(held_grow(h, w.listed, n * stride, { { &w.places, n * stride * sizeof(pp_wait_place) } }));
+	const SearchArgs args = held_args(h, h.ownView);
+	const Footprint discs = stamp_discs(h.footprint, pl->map);
+	ConflictLattice extended = lattice;
+	extended.k0 = lattice.k0 - D;
+	extended.T = lattice.T + D;
+	const pp_wait_fixed* const fixedDev = fixed ? w.fixed.get() : nullptr;
+	const uint8_t* const noStartDev = no_start_wait ? w.noStart.get() : nullptr;
+	std::vector<pp_wait_result> recs(results_host ? n : 0);
+	std::vector<int32_t> counts(n_places_host || places_host ? n : 0);
+	std::vector<pp_wait_place> listedPlaces(places_host ? n * stride : 0);
+	if (int rc = held_run(h, c.rec, plans, (pp_trajectory_result*)nullptr, [&](const int32_t* slotsDev) {
+			hipError_t e = hipMemcpyAsync(g.members, members.data(), n * 4, hipMemcpyHostToDevice, h.stream);
+			if (e == hipSuccess)
+				e = hipMemcpyAsync(g.offsets, offsets.data(), (n + 1) * 4, hipMemcpyHostToDevice, h.stream);
+			if (e == hipSuccess && nListed)
+				e = hipMemcpyAsync(g.partners, list.data(), nListed * 4, hipMemcpyHostToDevice, h.stream);
+			if (e == hipSuccess && fixed)
+				e = hipMemcpyAsync(w.fixed, fixed, n * sizeof(pp_wait_fixed), hipMemcpyHostToDevice, h.stream);
+			if (e == hipSuccess && no_start_wait)
+				e = hipMemcpyAsync(w.noStart, no_start_wait, n, hipMemcpyHostToDevice, h.stream);
+			if (e == hipSuccess)
+				e = launch_trajectory(h.stream, args, extended, discs.anyOffset != 0, h.n, slotsDev, c.rec.args.get(), pl, speed.rows.get(), c.traj.get(), c.rec.out.get());
+			if (e == hipSuccess)
+				e = launch_wait_places(h.stream, args, lattice, call, h.n, slotsDev, c.rec.args.get(), pl, speed.rows.get(), fixedDev, w.places.get(), w.counts.get());
+			for (int l = 0; l < nLevels && e == hipSuccess; l++)
+				e = launch_wait_level(h.stream, discs, lattice, call, h.n, first[(size_t)l + 1] - first[(size_t)l], g.members.get() + first[(size_t)l], g.offsets.get(),
+					g.partners.get(), c.rec.args.get(), c.traj.get(), c.rec.out.get(), fixedDev, noStartDev, w.places.get(), w.counts.get(), w.states.get(), w.out.get());
+			if (e == hipSuccess && !recs.empty())
+				e = hipMemcpyAsync(recs.data(), w.out, n * sizeof(pp_wait_result), hipMemcpyDeviceToHost, h.stream);
+			if (e == hipSuccess && !counts.empty())
+				e = hipMemcpyAsync(counts.data(), w.counts, n * 4, hipMemcpyDeviceToHost, h.stream);
+			if (e == hipSuccess && !listedPlaces.empty())
+				e = hipMemcpyAsync(listedPlaces.data(), w.places, listedPlaces.size() * sizeof(pp_wait_place), hipMemcpyDeviceToHost, h.stream);
+			return e;
+		}))
+		return rc;
+	std::copy(recs.begin(), recs.end(), results_host);
+	for (size_t i = 0; i < counts.size(); i++) {
+		const size_t listedHere = counts[i] > 0 ? (size_t)counts[i] : 0; // (kWaitNoPlace: a fixed row that does not qualify lists nothing)
+		if (n_places_host)
+			n_places_host[i] = (int32_t)listedHere;
+		if (places_host)
+			std::copy(listedPlaces.begin() + i * stride, listedPlaces.begin() + i * stride + listedHere, places_host + i * stride);
+	}
 	return PP_OK;
 }
 
@@ -2412,6 +2556,22 @@ int pp_planner_deconflict_tracks(pp_planner* planner, int32_t n_queries, const d
 		return rc;
 	return deconflict_tracks_plans(h, planner->conflict, planner->delay, planner->track, planner->speed, plans, lattice, params->max_delay_steps, n_pairs, pairs, tracks,
 		results_host, track_results_host);
+}
+
+int pp_planner_deconflict_waits(pp_planner* planner, int32_t n_queries, const double* t_start, const uint8_t* no_start_wait, const pp_wait_fixed* fixed, int32_t n_pairs,
+	const int32_t* pairs, const pp_wait_params* params, int32_t* n_places_host, pp_wait_place* places_host, pp_wait_result* results_host)
+{
+	if (int rc = batch_check(planner, n_queries, "pp_pipeline_deconflict_waits schedules its held tickets"))
+		return rc;
+	const HeldPlans h = batch_plans(planner, n_queries);
+	ConflictLattice lattice;
+	if (int rc = wait_check(h, t_start, no_start_wait, fixed, n_pairs, pairs, params, lattice))
+		return rc;
+	std::vector<ConflictArg> plans;
+	if (int rc = conflict_profiles(h, planner->speed, t_start, lattice, plans))
+		return rc;
+	return deconflict_waits_plans(h, planner->conflict, planner->delay, planner->wait, planner->speed, plans, lattice, params, no_start_wait, fixed, n_pairs, pairs,
+		n_places_host, places_host, results_host);
 }
 
 int pp_planner_candidate_pairs(pp_planner* planner, int32_t n_queries, const double* t_start, const pp_pair_params* params, int32_t* pairs_host, int32_t* first_box_host,

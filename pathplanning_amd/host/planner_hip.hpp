@@ -1531,6 +1531,99 @@ public:
 		}
 		return out;
 	}
+	/// What DeconflictWaits says about one held plan (pp_wait_result)
+	struct Wait {
+		enum class Status { Scheduled = 0, NoClearCandidate = 1, FixedInConflict = 2, NoProfile = -1, FixedRowNoStop = -2 };
+		Status status = Status::NoProfile;
+		int place = -2;        // -2 no wait; -1 the start; >= 0 the index in the vehicle's listed places
+		int row = -1;          // the stop's row of the profile; else -1
+		int waitSteps = -1, numTried = 0;
+		int blocker = -1;      // as Delay::blocker
+		double tStart = 0.0;   // the effective start: it moves only for a wait at the start
+		double tHold = 0.0, tResume = 0.0, sWait = 0.0; // a wait at a stop: the lattice times from which it stands and at which it moves again, the stop's arc length
+		double tBlock = 0.0, sBlock[2] = { 0.0, 0.0 };
+	};
+	/// A wait already committed, for DeconflictWaits (pp_wait_fixed): row -2 free, -1 the start, >= 0 that row of the profile; 0 .. maxDelaySteps steps
+	struct FixedWait {
+		int row = -2, steps = 0;
+	};
+	/// A stop a vehicle may wait at (pp_wait_place)
+	struct WaitPlace {
+		int row = 0, column = 0;
+		double s = 0.0, tArrive = 0.0;
+		Pose2d pose;
+		double sinTheta = 0.0, cosTheta = 1.0;
+	};
+	/// Waits at the start or at a timetable's stops that clear conflicts, by priority (pp_pipeline_deconflict_waits; include/pp_hip.h has the definition):
+	/// Deconflict with the first maxPlaces stops every plan reaches inside the horizon as further candidates.  noStartWait (empty: nobody is barred) says
+	/// who may not wait at the start; fixed (empty: everybody is free) commits waits, which are checked and seen, not decided.  places (may be null) gets
+	/// every vehicle's listed places.  Needs the LAST SpeedProfile call's timetables, as Conflicts does.  Legal beside queries in flight.
+	std::vector<Wait> DeconflictWaits(const std::vector<uint64_t>& tickets, const std::vector<double>& tStart, const std::vector<std::pair<int, int>>& pairs, bool allPairs,
+		const ConflictHorizon& horizon, int maxDelaySteps, int maxPlaces, const std::vector<bool>& noStartWait = {}, const std::vector<FixedWait>& fixed = {},
+		std::vector<std::vector<WaitPlace>>* places = nullptr)
+	{
+		for (uint64_t t : tickets)
+			HeldOf(t); // (throws for a ticket that is not held)
+		const size_t n = tickets.size();
+		if (tStart.size() != n || (!noStartWait.empty() && noStartWait.size() != n) || (!fixed.empty() && fixed.size() != n))
+			throw std::invalid_argument("DeconflictWaits: tStart, noStartWait and fixed hold one entry per ticket");
+		std::vector<Wait> out;
+		if (places)
+			places->clear();
+		if (!m_pipe || n == 0)
+			return out;
+		const pp_wait_params wp { { { horizon.tFrom, horizon.tTo, horizon.dt, horizon.margin, horizon.holdBefore ? 1 : 0, horizon.holdAfter ? 1 : 0 }, maxDelaySteps, 0 }, maxPlaces, 0 };
+		std::vector<int32_t> list;
+		for (const auto& p : pairs) {
+			list.push_back(p.first);
+			list.push_back(p.second);
+		}
+		const size_t nPairs = allPairs ? n * (n - 1) / 2 : pairs.size();
+		std::vector<uint8_t> flags(noStartWait.begin(), noStartWait.end());
+		std::vector<pp_wait_fixed> committed;
+		for (const auto& f : fixed)
+			committed.push_back(pp_wait_fixed { f.row, f.steps });
+		const size_t stride = maxPlaces > 0 && maxPlaces <= 1024 ? (size_t)maxPlaces : 1;
+		std::vector<int32_t> counts(places ? n : 0);
+		std::vector<pp_wait_place> listed(places ? n * stride : 0);
+		std::vector<pp_wait_result> r(n);
+		ppCheck(pp_pipeline_deconflict_waits(m_pipe, (int32_t)n, tickets.data(), tStart.data(), flags.empty() ? nullptr : flags.data(), committed.empty() ? nullptr : committed.data(),
+			(int32_t)nPairs, allPairs ? nullptr : list.data(), &wp, places ? counts.data() : nullptr, places ? listed.data() : nullptr, r.data()));
+		out.resize(n);
+		for (size_t i = 0; i < n; i++) {
+			Wait& o = out[i];
+			o.status = (Wait::Status)r[i].status;
+			o.place = r[i].place;
+			o.row = r[i].row;
+			o.waitSteps = r[i].wait_steps;
+			o.numTried = r[i].n_tried;
+			o.blocker = r[i].blocker;
+			o.tStart = r[i].t_start;
+			o.tHold = r[i].t_hold;
+			o.tResume = r[i].t_resume;
+			o.sWait = r[i].s_wait;
+			o.tBlock = r[i].t_block;
+			o.sBlock[0] = r[i].s_block[0];
+			o.sBlock[1] = r[i].s_block[1];
+		}
+		if (places) {
+			places->resize(n);
+			for (size_t i = 0; i < n; i++)
+				for (int32_t k = 0; k < counts[i]; k++) {
+					const pp_wait_place& pl = listed[i * stride + (size_t)k];
+					WaitPlace o;
+					o.row = pl.row;
+					o.column = pl.column;
+					o.s = pl.s;
+					o.tArrive = pl.t_arrive;
+					o.pose = Pose2d(pl.pose[0], pl.pose[1], pl.pose[2]);
+					o.sinTheta = pl.sin_theta;
+					o.cosTheta = pl.cos_theta;
+					(*places)[i].push_back(o);
+				}
+		}
+		return out;
+	}
 	/// A tracked mover for DeconflictTracks: a disc of `radius` that moves along the timed waypoints (t, x, y), t strictly increasing, on straight lines
 	/// between them; absent before the first time and behind the last
 	struct Track {

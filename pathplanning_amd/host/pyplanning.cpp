@@ -520,6 +520,36 @@ PYBIND11_MODULE(pyplanning, m)
 			"status 0 scheduled with the effective start t_start, 1 no delay is clear (those below ignore it), -1 no speed profile.",
 			py::arg("tickets"), py::arg("t_start"), py::arg("pairs") = py::none(), py::arg("t_from") = 0.0, py::arg("t_to") = 60.0, py::arg("dt") = 0.1, py::arg("margin") = 0.0,
 			py::arg("hold_before") = false, py::arg("hold_after") = false, py::arg("max_delay_steps") = 0)
+		.def("deconflict_waits",
+			[](HybridAStarPipeline& h, const std::vector<uint64_t>& tickets, const std::vector<double>& tStart, const py::object& pairs, const std::vector<bool>& noStartWait,
+				const std::vector<std::pair<int, int>>& fixed, double tFrom, double tTo, double dt, double margin, bool holdBefore, bool holdAfter, int maxDelaySteps, int maxPlaces) {
+				HybridAStarPipeline::ConflictHorizon horizon;
+				horizon.tFrom = tFrom;
+				horizon.tTo = tTo;
+				horizon.dt = dt;
+				horizon.margin = margin;
+				horizon.holdBefore = holdBefore;
+				horizon.holdAfter = holdAfter;
+				const bool all = pairs.is_none();
+				std::vector<HybridAStarPipeline::FixedWait> committed;
+				for (const auto& f : fixed)
+					committed.push_back(HybridAStarPipeline::FixedWait { f.first, f.second });
+				py::list out;
+				for (const auto& w : h.DeconflictWaits(tickets, tStart, all ? std::vector<std::pair<int, int>>() : pairs.cast<std::vector<std::pair<int, int>>>(), all, horizon,
+						 maxDelaySteps, maxPlaces, noStartWait, committed))
+					out.append(py::make_tuple((int)w.status, w.place, w.row, w.waitSteps, w.numTried, w.blocker, w.tStart, w.tHold, w.tResume, w.sWait, w.tBlock,
+						py::make_tuple(w.sBlock[0], w.sBlock[1])));
+				return out;
+			},
+			"Waits at the start or at a timetable's stops that clear conflicts between held queries, by priority, on the timetables of the last speed_profile call: "
+			"deconflict with the first max_places stops every plan reaches inside the horizon as further candidates.  tickets, t_start, pairs, t_from, t_to, dt, margin, "
+			"hold_before, hold_after and max_delay_steps are deconflict's; no_start_wait: per ticket whether it may NOT wait at its start (empty: everybody may); fixed: per "
+			"ticket a committed wait (row, steps) with row -2 free, -1 the start, >= 0 a stop's row (empty: everybody is free); max_places: stops listed per vehicle.  Returns "
+			"per ticket (status, place, row, wait_steps, n_tried, blocker, t_start, t_hold, t_resume, s_wait, t_block, s_block): status 0 scheduled, 1 no candidate is clear, "
+			"2 a fixed wait in conflict, -1 no speed profile, -2 the fixed row is no stop reached in time.",
+			py::arg("tickets"), py::arg("t_start"), py::arg("pairs") = py::none(), py::arg("no_start_wait") = std::vector<bool>(),
+			py::arg("fixed") = std::vector<std::pair<int, int>>(), py::arg("t_from") = 0.0, py::arg("t_to") = 60.0, py::arg("dt") = 0.1, py::arg("margin") = 0.0,
+			py::arg("hold_before") = false, py::arg("hold_after") = false, py::arg("max_delay_steps") = 0, py::arg("max_places") = 0)
 		.def("deconflict_tracks",
 			[](HybridAStarPipeline& h, const std::vector<uint64_t>& tickets, const std::vector<double>& tStart,
 				const std::vector<std::pair<double, std::vector<std::tuple<double, double, double>>>>& tracks, const py::object& pairs, double tFrom, double tTo, double dt, double margin,

@@ -13,7 +13,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import (RS_PATH_DTYPE, ConflictParams, ConflictResult, DelayParams, DelayResult, FootprintDisc, HybridParams, LocateParams, LocateResult, MapDesc, PairParams, PairSummary, PostResult, QueryResult, RevalidateResult,
-                   SmootherParams, SpeedProfileParams, SpeedProfileResult, StampParams, StampResult, TimetableParams, TimetablePlan, TimetableResult, TimetableStop, TrackResult, TrackSet, TrajectoryResult, check, ptr)
+                   SmootherParams, SpeedProfileParams, SpeedProfileResult, StampParams, StampResult, TimetableParams, TimetablePlan, TimetableResult, TimetableStop, TrackResult, TrackSet, TrajectoryResult, WaitFixed, WaitParams, WaitPlace, WaitResult,
+                   check, ptr)
 
 
 class Status:
@@ -722,6 +723,16 @@ class HybridAStarBatch:
         return _deconflict(n, t_start, pairs, t_from, t_to, dt, margin, hold_before, hold_after, max_delay_steps,
                            lambda ts, npairs, pr, dp, out: self.lib.pp_planner_deconflict(self.h, n, ptr(ts), npairs, ptr(pr), C.byref(dp), ptr(out)))
 
+    def deconflict_waits(self, t_start, n_queries=None, pairs=None, no_start_wait=None, fixed=None, t_from=0.0, t_to=60.0, dt=0.1, margin=0.0, hold_before=False,
+                         hold_after=False, max_delay_steps=0, max_places=0, places=False):
+        """Waits at the start or at a timetable's stops that clear the conflicts between the plans of the first n queries of the last batch, by priority
+        (the query index): pp_planner_deconflict_waits, the batch form of HybridAStarPipeline.deconflict_waits, with the same arguments (pair indices
+        are query indices) and return value."""
+        n = len(self._results) if n_queries is None else int(n_queries)
+        return _deconflict_waits(n, t_start, no_start_wait, fixed, pairs, t_from, t_to, dt, margin, hold_before, hold_after, max_delay_steps, max_places, places,
+                                 lambda ts, flags, fx, npairs, pr, wp, counts, listed, out: self.lib.pp_planner_deconflict_waits(
+                                     self.h, n, ptr(ts), ptr(flags), ptr(fx), npairs, ptr(pr), C.byref(wp), ptr(counts), ptr(listed), ptr(out)))
+
     def deconflict_tracks(self, t_start, tracks, n_queries=None, pairs=None, t_from=0.0, t_to=60.0, dt=0.1, margin=0.0, hold_before=False, hold_after=False, max_delay_steps=0,
                           details=True):
         """Start delays that clear the conflicts between the plans of the first n queries of the last batch and with the tracked movers `tracks`:
@@ -1122,6 +1133,23 @@ class HybridAStarPipeline:
         return _deconflict(len(t), t_start, pairs, t_from, t_to, dt, margin, hold_before, hold_after, max_delay_steps,
                            lambda ts, npairs, pr, dp, out: self.lib.pp_pipeline_deconflict(self.h, len(t), ptr(t), ptr(ts), npairs, ptr(pr), C.byref(dp), ptr(out)))
 
+    def deconflict_waits(self, tickets, t_start, pairs=None, no_start_wait=None, fixed=None, t_from=0.0, t_to=60.0, dt=0.1, margin=0.0, hold_before=False,
+                         hold_after=False, max_delay_steps=0, max_places=0, places=False):
+        """deconflict() for a fleet under way: a vehicle that yields may wait at its start (unless no_start_wait[i]) or at one of the first `max_places`
+        stops its timetable reaches inside the horizon -- cusp stops, where it stands anyway.  pp_pipeline_deconflict_waits, whose definition is in
+        include/pp_hip.h.  Candidates are tried in the order d = 0, then for d = 1 .. max_delay_steps the start and the places in row order; the first
+        clear one is taken.  `fixed` commits waits: None, [n, 2] rows of (row, steps) with row -2 free / -1 the start / >= 0 a stop's row, or the
+        record array an earlier call returned (its scheduled vehicles stay bound, wait_fixed()); a fixed vehicle is never decided, only checked
+        (status 0, or 2 in conflict; -2 if its row is no stop it reaches in time) and seen by the vehicles below it.
+        Returns a numpy record array of WAIT_DTYPE, one record per ticket; with places=True also the listed places [n, max(max_places, 1)]
+        (WAIT_PLACE_DTYPE) and their counts [n].
+        Raises PPError, with nothing launched, for everything deconflict() refuses, max_places outside 0 .. 2^10, a fixed row below -2 or fixed steps
+        outside 0 .. max_delay_steps."""
+        t = np.ascontiguousarray(tickets, dtype=np.uint64).reshape(-1)
+        return _deconflict_waits(len(t), t_start, no_start_wait, fixed, pairs, t_from, t_to, dt, margin, hold_before, hold_after, max_delay_steps, max_places, places,
+                                 lambda ts, flags, fx, npairs, pr, wp, counts, listed, out: self.lib.pp_pipeline_deconflict_waits(
+                                     self.h, len(t), ptr(t), ptr(ts), ptr(flags), ptr(fx), npairs, ptr(pr), C.byref(wp), ptr(counts), ptr(listed), ptr(out)))
+
     def deconflict_tracks(self, tickets, t_start, tracks, pairs=None, t_from=0.0, t_to=60.0, dt=0.1, margin=0.0, hold_before=False, hold_after=False, max_delay_steps=0,
                           details=True):
         """deconflict() with tracked movers: every vehicle of the completed, HELD queries `tickets` gets the smallest start delay at which it is clear of
@@ -1314,6 +1342,68 @@ def _deconflict(n, t_start, pairs, t_from, t_to, dt, margin, hold_before, hold_a
     out = np.zeros(max(n, 1), dtype=DELAY_DTYPE)
     check(call(ts, n_pairs, pr, dp, out))
     return out[:n].view(np.recarray)
+
+
+# pp_wait_result, pp_wait_place and pp_wait_fixed as numpy records
+WAIT_DTYPE = np.dtype([("status", np.int32), ("place", np.int32), ("row", np.int32), ("wait_steps", np.int32), ("n_tried", np.int32), ("blocker", np.int32),
+                       ("t_start", np.float64), ("t_hold", np.float64), ("t_resume", np.float64), ("s_wait", np.float64), ("t_block", np.float64), ("s_block", np.float64, (2,))])
+WAIT_PLACE_DTYPE = np.dtype([("row", np.int32), ("column", np.int32), ("s", np.float64), ("t_arrive", np.float64), ("pose", np.float64, (3,)), ("sin_theta", np.float64),
+                             ("cos_theta", np.float64)])
+WAIT_FIXED_DTYPE = np.dtype([("row", np.int32), ("steps", np.int32)])
+assert WAIT_DTYPE.itemsize == C.sizeof(WaitResult) and WAIT_PLACE_DTYPE.itemsize == C.sizeof(WaitPlace) and WAIT_FIXED_DTYPE.itemsize == C.sizeof(WaitFixed)
+
+
+def wait_fixed(fixed, n):
+    """the committed waits of a deconflict_waits call as an array of WAIT_FIXED_DTYPE: None; an array of that dtype; [n, 2] integers (row, steps); or
+    the record array of an earlier call, whose scheduled vehicles (status 0 or 2) stay bound by what they were given -- a wait at the start (also one
+    of no steps) as row -1, a wait at a stop as its row -- and whose other vehicles are free (row -2)"""
+    if fixed is None:
+        return None
+    if isinstance(fixed, np.ndarray) and fixed.dtype.names and "wait_steps" in fixed.dtype.names:
+        if len(fixed) != n:
+            raise ValueError("one committed wait per plan")
+        out = np.zeros(n, dtype=WAIT_FIXED_DTYPE)
+        bound = (fixed["status"] == 0) | (fixed["status"] == 2)
+        out["row"] = np.where(bound, np.where(fixed["place"] >= 0, fixed["row"], -1), -2)
+        out["steps"] = np.where(bound, fixed["wait_steps"], 0)
+        return out
+    if isinstance(fixed, np.ndarray) and fixed.dtype == WAIT_FIXED_DTYPE:
+        out = np.ascontiguousarray(fixed).reshape(-1)
+    else:
+        pairs = np.asarray(fixed, dtype=np.int64).reshape(-1, 2)
+        if len(pairs) and (np.abs(pairs) >= 2 ** 31).any():
+            raise ValueError("a committed wait is (row, steps) in int32")
+        out = np.zeros(len(pairs), dtype=WAIT_FIXED_DTYPE)
+        out["row"], out["steps"] = pairs[:, 0], pairs[:, 1]
+    if len(out) != n:
+        raise ValueError("one committed wait per plan")
+    return out
+
+
+def _deconflict_waits(n, t_start, no_start_wait, fixed, pairs, t_from, t_to, dt, margin, hold_before, hold_after, max_delay_steps, max_places, places, call):
+    """the parameters, start times, flags, committed waits and pair list of a call with waits at stops, the call, its records as one numpy record array
+    and (places=True) the listed places [n, max(max_places, 1)] and their counts [n]"""
+    wp = WaitParams(DelayParams(ConflictParams(float(t_from), float(t_to), float(dt), float(margin), int(hold_before), int(hold_after)), int(max_delay_steps), 0),
+                    int(max_places), 0)
+    ts = _per_plan(t_start, n)
+    if ts is None and n:
+        raise ValueError("one start time per plan")
+    flags = None
+    if no_start_wait is not None:
+        flags = np.asarray(no_start_wait)
+        flags = np.full(n, bool(flags), dtype=np.uint8) if flags.ndim == 0 else np.ascontiguousarray(flags.reshape(-1) != 0, dtype=np.uint8)
+        if len(flags) != n:
+            raise ValueError("one no_start_wait flag per plan")
+    fx = wait_fixed(fixed, n)
+    pr = None if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    n_pairs = n * (n - 1) // 2 if pr is None else len(pr)
+    out = np.zeros(max(n, 1), dtype=WAIT_DTYPE)
+    stride = max(int(max_places), 1) if 0 <= int(max_places) <= 1 << 10 else 1
+    listed = np.zeros((max(n, 1), stride), dtype=WAIT_PLACE_DTYPE) if places else None
+    counts = np.zeros(max(n, 1), dtype=np.int32) if places else None
+    check(call(ts, flags, fx, n_pairs, pr, wp, counts, listed, out))
+    recs = out[:n].view(np.recarray)
+    return (recs, listed[:n].view(np.recarray), counts[:n]) if places else recs
 
 
 def _box_count(t_from, t_to, dt, times_per_box):
