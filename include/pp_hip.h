@@ -1083,7 +1083,9 @@ int pp_planner_timetable(pp_planner* planner, int32_t n_queries, int32_t n_point
  *           time up to m0, so it is rejected with that same key: the kernel counts and records such a candidate without evaluating it.)
  *  Fixed.   A vehicle with fixed != NULL and fixed[i].row != -2 is not decided: its one candidate is (fixed[i].row, fixed[i].steps).  row == -1 is a
  *           start wait; row >= 0 a wait at that row, which must be a stop (v_row == 0, any row 0 .. N - 1) with a < T + D -- no lower bound on a:
- *           the vehicle may stand there already.  A row that does not qualify gives status -2, and the vehicle is ignored like one of status -1.  A
+ *           the vehicle may stand there already.  After pp_*_retime ("decided waits written into the timetables") has written a committed wait at a
+ *           stop into the rows, that wait needs no fixed entry any more and the vehicle is free again.
+ *           A row that does not qualify gives status -2, and the vehicle is ignored like one of status -1.  A
  *           qualifying fixed vehicle is ALWAYS scheduled: status 0 if its candidate is clear, else 2 with the blocker filled in; the vehicles below
  *           see it either way.  Its list of places is its one row (place 0).
  *  Status 1 of a free vehicle: no candidate was clear; the vehicles below it are scheduled as if it were absent, as in the delay call.
@@ -1134,6 +1136,61 @@ int pp_pipeline_deconflict_waits(pp_pipeline* pipeline, int32_t n, const uint64_
 /* The same kernels over the first n_queries queries of the planner's last batch, as pp_planner_deconflict is to pp_pipeline_deconflict. */
 int pp_planner_deconflict_waits(pp_planner* planner, int32_t n_queries, const double* t_start, const uint8_t* no_start_wait, const pp_wait_fixed* fixed,
 	int32_t n_pairs, const int32_t* pairs, const pp_wait_params* params, int32_t* n_places_host, pp_wait_place* places_host, pp_wait_result* results_host);
+/* ---- decided waits written into the timetables, by ticket ----------------------------------------------------------------------------------------
+ * pp_*_deconflict_waits tells a vehicle to stand d steps longer at row j of its timetable; the calls above take a start time per plan and nothing
+ * else, so none of them learns of it.  This call writes such HOLDS into the (s, v, t) rows themselves: t_j carries the dwell of row j and
+ * arrive_time derives the arrival from row j - 1, so standing w seconds longer at row j is t_k += w for every k >= j, and nothing else.  Behind it
+ * every service above sees the wait without a changed line: the conflict call verifies a decided schedule, the timetable call reports the true ETA
+ * and the longer t_depart, the broad phase boxes the schedule actually driven, and the next pp_*_deconflict_waits round finds the vehicle free, so
+ * that it can be given a second wait further on.  Every expression is in double, in the order written.
+ *  Profile. The holder's most recent speed-profile call, exactly as the conflict call reads it: the rows (s_j, v_j, t_j), j = 0 .. N - 1, of plan i
+ *           where the speed-profile kernel left them, a_acc and a_dec.  The call rewrites their t column IN PLACE and touches nothing else of them.
+ *           A plan whose profile has a status other than 0 gets status -1; its holds are skipped, not refused.
+ *  Holds.   `holds` is sorted strictly ascending by (plan, row): at most one hold per row.  plan indexes `tickets` (the queries of a batch planner);
+ *           row is in 1 .. N - 1 -- row 0 cannot be held, t_0 = 0 is what every reader assumes, and a wait at the start is the caller's t_start, as
+ *           before; seconds is finite and may be negative, which shortens a dwell committed earlier.
+ *  Validity, on the ORIGINAL rows, per plan, all or nothing.  A hold at row r needs v_r == 0.0 (the timetable call's stop), else the plan gets
+ *           status -2; with delta_r = t_r - t_arrive(r) (t_arrive as the timetable call defines it) it needs delta_r + seconds >= 0, else status
+ *           -3 (per hold the stop test comes first).  The first offender in list order is reported in bad_hold, and a plan with an offender keeps
+ *           every byte of its rows.
+ *  Prefix.  P_0 = seconds_0 and P_h = P_{h-1} + seconds_h, summed sequentially in list order over the plan's holds; `held` is the last P.
+ *  Rewrite. For row k let h(k) be the last hold of the plan with row <= k.  If there is none the row is untouched; otherwise t'_k = t_k + P_{h(k)}:
+ *           one addition per row.  fl(x + P) is monotone in x, so within one hold segment (the rows that share h(k)) the times stay non-decreasing
+ *           bit for bit, and in front of the first hold they are untouched.  Across a segment's first row validity bounds the step by rounding only.
+ *           A t_arrive recomputed afterwards from row r - 1 may differ from t'_r less the dwell by one ulp, as it already can from the rows as the
+ *           speed profile left them (t_j there is t_{j-1} + (step_time + dwell), not t_arrive + dwell).
+ *  Accumulation. The call is incremental: a second call adds to what the first left.  Adding -w after +w restores the times to rounding, not bit for
+ *           bit.  A new speed-profile call replaces everything.
+ *  Consequence. A wait of d steps at the stop of row r decided by pp_*_deconflict_waits on a lattice of step dt is the hold (i, r, (double)d * dt).
+ *           A later conflict call forms u = tau - t_start afresh against the retimed rows; it agrees with that call's "Position under a wait" to
+ *           rounding, as the delay call's text already says for effective starts.
+ *  - PP_ERR_INVALID, nothing launched, the holder usable as before, the message naming the first offender: every refusal of the timetable call about
+ *    n, the tickets and a missing profile ("run speed_profile first"); n_holds < 0; NULL holds with n_holds > 0; a plan outside 0 .. n - 1; a row < 1
+ *    (for row 0 the message says to shift t_start instead) or, for a plan with a profile, > N - 1; seconds that is not finite; a list that is not
+ *    strictly ascending in (plan, row); more than 2^10 holds for one plan.
+ *  - n == 0 is PP_OK, whatever the holds.  rows_host, if given, receives the rows after the call in the speed-profile call's layout: the first N rows
+ *    of every plan with a profile, nothing else written.  n_holds == 0 with rows_host is the way to read the rows as they are.
+ *  - Legal beside queries in flight: it writes only the speed-profile group's own rows and its own buffers (16 + 4 + 40 bytes per plan, 16 per hold),
+ *    kept aside like the others when they have to grow then, on the holder's stream, which it alone synchronises (k_retime_tickets, one wave per
+ *    plan). */
+typedef struct pp_hold {
+	int32_t plan;       /* index into the call's tickets (queries) */
+	int32_t row;        /* 1 .. N - 1: a stop of that plan's profile */
+	double  seconds;    /* finite; added to the dwell of the row */
+} pp_hold;                  /* 16 bytes */
+typedef struct pp_retime_result {
+	int32_t status;     /* 0 applied (also a plan with no hold); -1 the ticket's profile has status != 0; -2 a hold's row is not a stop;
+	                       -3 a hold would make a dwell negative */
+	int32_t n_holds;    /* holds listed for this plan */
+	int32_t first_row;  /* the smallest row whose time changed; -1: none */
+	int32_t bad_hold;   /* index into the call's `holds` of the first offending hold (status -2, -3); else -1 */
+	double  held;       /* P of the plan's last hold; 0 without one, and for status -2 and -3 */
+	double  duration_before, duration;   /* t_{N-1} before and after */
+} pp_retime_result;         /* 40 bytes; for status -1 every field but status and bad_hold (-1) is zero */
+int pp_pipeline_retime(pp_pipeline* pipeline, int32_t n, const uint64_t* tickets, int32_t n_holds, const pp_hold* holds /* may be NULL iff n_holds == 0 */,
+	double* rows_host /* may be NULL; [n][max_samples][3] of the remembered profile call */, pp_retime_result* results_host /* may be NULL; [n] */);
+/* The same kernel over the first n_queries queries of the planner's last batch, as pp_planner_timetable is to pp_pipeline_timetable. */
+int pp_planner_retime(pp_planner* planner, int32_t n_queries, int32_t n_holds, const pp_hold* holds, double* rows_host, pp_retime_result* results_host);
 /* Diagnostics: waves of the search grid that are alive right now (a blocking device-to-host copy; -1 on error). */
 int pp_pipeline_alive_waves(pp_pipeline* pipeline);
 pp_planner* pp_pipeline_planner(pp_pipeline* pipeline);           /* the buffer set: set_nonholo_table, set_primitives, get_path(slot), ... */

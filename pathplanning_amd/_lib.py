@@ -211,6 +211,19 @@ class WaitResult(C.Structure):
                 ("t_start", C.c_double), ("t_hold", C.c_double), ("t_resume", C.c_double), ("s_wait", C.c_double), ("t_block", C.c_double), ("s_block", C.c_double * 2)]
 
 
+class Hold(C.Structure):
+    """pp_hold: `seconds` (finite, may be negative) added to the dwell of the stop at `row` (1 .. N - 1) of plan `plan` of a retime call"""
+    _fields_ = [("plan", C.c_int32), ("row", C.c_int32), ("seconds", C.c_double)]
+
+
+class RetimeResult(C.Structure):
+    """pp_retime_result: status 0 applied, -1 no profile, -2 a hold's row is not a stop, -3 a hold would make a dwell negative; the holds listed for the
+    plan, the smallest row rewritten (-1: none), the index in the call's list of the first offending hold (-1: none), the sum of the plan's holds, and
+    t_{N-1} before and after"""
+    _fields_ = [("status", C.c_int32), ("n_holds", C.c_int32), ("first_row", C.c_int32), ("bad_hold", C.c_int32), ("held", C.c_double),
+                ("duration_before", C.c_double), ("duration", C.c_double)]
+
+
 class WaitPlace(C.Structure):
     """pp_wait_place: a stop a vehicle may wait at -- its row, its arrive column in the extended trajectory, its arc length and arrival time, the
     standing pose and the sine and cosine of its heading"""
@@ -382,6 +395,8 @@ def load():
     L.pp_planner_timetable.argtypes = [vp, C.c_int32, C.c_int32, vp, C.POINTER(TimetableParams), vp, vp, vp]
     L.pp_pipeline_deconflict_waits.argtypes = [vp, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, C.POINTER(WaitParams), vp, vp, vp]
     L.pp_planner_deconflict_waits.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, vp, C.POINTER(WaitParams), vp, vp, vp]
+    L.pp_pipeline_retime.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp]
+    L.pp_planner_retime.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp]
     L.pp_pipeline_timings.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.pp_pipeline_backlog.argtypes = [vp, vp, vp]
     L.pp_pipeline_planner.argtypes = [vp]

@@ -365,6 +365,22 @@ def build_wait_rule_test(verbose=True):
     return out
 
 
+def build_retime_rule_test(verbose=True):
+    """tests/cpp/test_retime_rule.cpp: the dwell of a row, the validity of a hold, the prefix, the hold a row belongs to and the rewritten time
+    (csrc/pp_retime_rule.hpp) alone, on the CPU, under the address and undefined-behaviour sanitizers; without contraction, as the library is built."""
+    os.makedirs(LIB_DIR, exist_ok=True)
+    out = os.path.join(LIB_DIR, "test_retime_rule")
+    src = os.path.join(HERE, "..", "tests", "cpp", "test_retime_rule.cpp")
+    headers = [os.path.join(CSRC, h) for h in ("pp_retime_rule.hpp", "pp_timetable_rule.hpp", "pp_conflict_rule.hpp", "pp_speed_rule.hpp", "pp_stamp_rule.hpp")]
+    if os.path.exists(out) and os.path.getmtime(out) > max(os.path.getmtime(f) for f in [src] + headers):
+        return out
+    cmd = ["g++", "-std=c++17", "-g", "-O1", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC, src, "-o", out]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return out
+
+
 def build_ticket_table_test(verbose=True):
     """tests/cpp/test_ticket_table.cpp: the pipeline's slot and ticket bookkeeping (csrc/pp_ticket_table.hpp) alone, on the CPU, under the address and
     undefined-behaviour sanitizers."""
@@ -419,5 +435,6 @@ if __name__ == "__main__":
     print(build_timetable_rule_test())
     print(build_pipeline_deconflict_waits_test())
     print(build_wait_rule_test())
+    print(build_retime_rule_test())
     print(build_ticket_table_test())
     print(build_row_test())

@@ -2,8 +2,8 @@
 // names their argument types) and in front of pp_planner and pp_pipeline, which both keep one buffer group per service.
 //
 // Finished plans (path records, Reeds-Shepp log, result record) are held by a batch planner, as queries 0 .. n-1 of its last batch, or by a pipeline, as
-// the slots of held tickets.  A service over them -- post-processing, re-validation, the stamp, the locate call, the speed profile, the conflict call, the delay call without and with tracked movers, the broad phase, the timetable look-ups, the waits at stops -- has one core (post_process_plans,
-// revalidate_plans, stamp_plans, locate_plans, speed_profile_plans, conflict_plans, deconflict_plans, deconflict_tracks_plans, candidate_pairs_plans, timetable_plans, deconflict_waits_plans in pp_planner.hip) that takes a HeldPlans and goes through held_grow and held_run; its two extern "C"
+// the slots of held tickets.  A service over them -- post-processing, re-validation, the stamp, the locate call, the speed profile, the conflict call, the delay call without and with tracked movers, the broad phase, the timetable look-ups, the waits at stops, the retime call -- has one core (post_process_plans,
+// revalidate_plans, stamp_plans, locate_plans, speed_profile_plans, conflict_plans, deconflict_plans, deconflict_tracks_plans, candidate_pairs_plans, timetable_plans, deconflict_waits_plans, retime_plans in pp_planner.hip) that takes a HeldPlans and goes through held_grow and held_run; its two extern "C"
 // entries check what is the holder's own and describe the holder (batch_plans, pipe_plans).
 #pragma once
 
@@ -160,6 +160,16 @@ struct WaitGroup {
 	size_t vehicles = 0; // plans they hold
 	pph::Dev<pp_wait_place> places;
 	size_t listed = 0; // places `places` holds (64 bytes each)
+};
+
+/// The retime call's buffers: per plan the slot list (uploaded by held_run, not read by the kernel), the profile row (a ConflictArg whose start time is
+/// not read) and the record; the start of each plan's holds in the call's list; the holds
+struct RetimeGroup {
+	HeldBuffers<ConflictArg, pp_retime_result> rec;
+	pph::Dev<int32_t> offsets;
+	size_t plans = 0; // plans `offsets` holds (one entry more)
+	pph::Dev<pp_hold> holds;
+	size_t listed = 0; // holds `holds` holds (16 bytes each)
 };
 
 /// Buffers that hold `capacity` units are made to hold `wanted` ({buffer, bytes}; 0 bytes: the holder does not use it).  A holder that may not free now

@@ -213,6 +213,7 @@ struct pp_pipeline {
 	TrackGroup track;
 	PairGroup pair;
 	TimetableGroup timetable;
+	RetimeGroup retime;
 	WaitGroup wait;
 	std::vector<pph::DeviceMem> heldParked; // their buffers outgrown while queries were in flight: hipFree waits for the whole device (the persistent grid
 	                                        // included), so they are kept until a call finds nothing in flight (or the pipeline goes): held_grow
@@ -1315,6 +1316,25 @@ int pp_pipeline_deconflict_waits(pp_pipeline* P, int32_t n, const uint64_t* tick
 		return rc;
 	return deconflict_waits_plans(h, P->conflict, P->delay, P->wait, P->speed, plans, lattice, params, no_start_wait, fixed, n_pairs, pairs, n_places_host, places_host,
 		results_host);
+}
+
+/// Holds written into the timetables of n completed, held queries (include/pp_hip.h; retime_plans): legal beside queries in flight
+int pp_pipeline_retime(pp_pipeline* P, int32_t n, const uint64_t* tickets, int32_t n_holds, const pp_hold* holds, double* rows_host, pp_retime_result* results_host)
+{
+	HeldPlans h;
+	if (int rc = pipe_plans(P, n, tickets, h))
+		return rc;
+	if (int rc = retime_check(h, n_holds, holds))
+		return rc;
+	if (int rc = pipe_resolve(P, n, tickets, "retimed", true, h.slots))
+		return rc;
+	std::vector<ConflictArg> plans;
+	std::vector<int32_t> offsets;
+	RetimeCall call;
+	int most = 0;
+	if (int rc = retime_profiles(h, P->speed, n_holds, holds, plans, call, offsets, most))
+		return rc;
+	return retime_plans(h, P->retime, P->speed, plans, call, offsets, most, n_holds, holds, rows_host, results_host);
 }
 
 /// Launch durations seen so far (HIP events on the launching streams; harvested by pp_pipeline_poll) and reset.  Wavefront: one launch per

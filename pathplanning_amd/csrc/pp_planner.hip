@@ -26,6 +26,7 @@
 #include "pp_track_rule.hpp"
 #include "pp_pair_rule.hpp"
 #include "pp_timetable_rule.hpp"
+#include "pp_retime_rule.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -326,6 +327,8 @@ struct PipeView {
 #include "pp_timetable.hpp"
 // waits at the start or at a timetable's stops that clear conflicts, by priority (one wave per plan lists the places, then one wave per vehicle of a level)
 #include "pp_waits.hpp"
+// decided waits written into a plan's timetable: t_k += the holds at or before row k, in place (one wave per plan)
+#include "pp_retime.hpp"
 
 } // namespace
 
@@ -396,6 +399,7 @@ struct pp_planner {
 	TrackGroup track;
 	PairGroup pair;
 	TimetableGroup timetable;
+	RetimeGroup retime;
 	WaitGroup wait;
 };
 
@@ -575,6 +579,14 @@ hipError_t launch_timetable(hipStream_t s, const SearchArgs& args, const Timetab
 {
 	hipLaunchKernelGGL(k_timetable_tickets, dim3(count > 0 ? count : 1), dim3(kTimetableLanes), trajectory_lds_bytes(args.maxPath), s, args, call, count, slotsDev, argsDev,
 		p->paths.get(), p->rsLogs.get(), p->results.get(), rowsDev, valuesDev, stopsDev, lookupsDev, outDev);
+	return hipGetLastError();
+}
+
+/// k_retime_tickets over `count` >= 1 plans whose longest hold list has `most` entries (the kernel has no private segment: no warm-up dispatch)
+hipError_t launch_retime(hipStream_t s, const RetimeCall& call, int count, int most, const ConflictArg* argsDev, const int32_t* offsetsDev, const pp_hold* holdsDev,
+	double* rowsDev, pp_retime_result* outDev)
+{
+	hipLaunchKernelGGL(k_retime_tickets, dim3(count), dim3(kRetimeLanes), retime_lds_bytes(most), s, call, count, argsDev, offsetsDev, holdsDev, rowsDev, outDev);
 	return hipGetLastError();
 }
 
@@ -1155,6 +1167,86 @@ int timetable_profiles(const HeldPlans& h, const SpeedGroup& g, int n_points, co
 	return PP_OK;
 }
 
+/// The hold list of a retime call (pp_planner_retime, pp_pipeline_retime) as far as it does not depend on the profiles: the count, the pointer, every
+/// plan index, seconds and row >= 1, the order and the holds per plan (h.name(i) names plan i in a refusal)
+int retime_check(const HeldPlans& h, int n_holds, const pp_hold* holds)
+{
+	if (h.n == 0)
+		return PP_OK;
+	if (n_holds < 0) {
+		set_error("invalid arguments (n_holds >= 0, got " + std::to_string(n_holds) + ")");
+		return PP_ERR_INVALID;
+	}
+	if (n_holds > 0 && !holds) {
+		set_error("invalid arguments (null holds with n_holds = " + std::to_string(n_holds) + ")");
+		return PP_ERR_INVALID;
+	}
+	int run = 0; // holds of the current plan so far
+	for (int k = 0; k < n_holds; k++) {
+		const pp_hold& x = holds[k];
+		const std::string which = "hold " + std::to_string(k);
+		if (x.plan < 0 || x.plan >= h.n) {
+			set_error("invalid arguments (" + which + " names plan " + std::to_string(x.plan) + " of " + std::to_string(h.n) + ")");
+			return PP_ERR_INVALID;
+		}
+		if (x.row == 0) {
+			set_error(h.name(x.plan) + ": " + which + " is at row 0, which cannot be held (t_0 = 0): shift the plan's t_start instead");
+			return PP_ERR_INVALID;
+		}
+		if (x.row < 1) {
+			set_error(h.name(x.plan) + ": " + which + " is at row " + std::to_string(x.row) + " (a hold's row is 1 .. N - 1)");
+			return PP_ERR_INVALID;
+		}
+		if (!std::isfinite(x.seconds)) {
+			set_error(h.name(x.plan) + ": " + which + " has seconds that are not finite");
+			return PP_ERR_INVALID;
+		}
+		if (k > 0 && (x.plan < holds[k - 1].plan || (x.plan == holds[k - 1].plan && x.row <= holds[k - 1].row))) {
+			set_error("invalid arguments (the holds are strictly ascending in (plan, row): " + which + " is not behind the one before it)");
+			return PP_ERR_INVALID;
+		}
+		run = k > 0 && x.plan == holds[k - 1].plan ? run + 1 : 1;
+		if (run > ppr::kMaxHolds) {
+			set_error(h.name(x.plan) + " has more than " + std::to_string(ppr::kMaxHolds) + " holds");
+			return PP_ERR_INVALID;
+		}
+	}
+	return PP_OK;
+}
+
+/// ... and against what the holder remembers of its last speed-profile call: the rows into `plans`, the call into `call`, a hold's row against the N of
+/// its plan's profile (a plan without one gets status -1 and its holds are skipped), the start of every plan's holds into `offsets` (n + 1) and the most
+/// holds of one plan into `most`
+int retime_profiles(const HeldPlans& h, const SpeedGroup& g, int n_holds, const pp_hold* holds, std::vector<ConflictArg>& plans, RetimeCall& call, std::vector<int32_t>& offsets,
+	int& most)
+{
+	call = RetimeCall {};
+	most = 0;
+	if (h.n == 0)
+		return PP_OK;
+	const std::vector<double> noStart((size_t)h.n, 0.0);
+	ConflictLattice lattice {};
+	if (int rc = conflict_profiles(h, g, noStart.data(), lattice, plans))
+		return rc;
+	call = RetimeCall { lattice.maxSamples, 0, lattice.aAcc, lattice.aDec };
+	offsets.assign((size_t)h.n + 1, 0);
+	for (int k = 0; k < n_holds; k++) {
+		const pp_hold& x = holds[k];
+		const int N = plans[(size_t)x.plan].nSamples;
+		if (N > 0 && x.row > N - 1) {
+			set_error(h.name(x.plan) + ": hold " + std::to_string(k) + " is at row " + std::to_string(x.row) + " of a profile of " + std::to_string(N) +
+				" rows (a hold's row is 1 .. N - 1)");
+			return PP_ERR_INVALID;
+		}
+		offsets[(size_t)x.plan + 1]++;
+	}
+	for (int i = 0; i < h.n; i++) {
+		most = std::max(most, (int)offsets[(size_t)i + 1]);
+		offsets[(size_t)i + 1] += offsets[(size_t)i];
+	}
+	return PP_OK;
+}
+
 // ---- the services over held plans, one core each (pp_held_plans.hpp); both holders' extern "C" entries end here
 
 /// the plans of a batch planner's last batch: queries 0 .. n-1
@@ -1671,6 +1763,49 @@ int timetable_plans(const HeldPlans& h, TimetableGroup& g, const SpeedGroup& spe
 	if (!staged.empty())
 		for (size_t i = 0; i < n; i++) // (rows behind n_listed stay as the caller left them)
 			std::copy(staged.begin() + i * (size_t)call.maxStops, staged.begin() + i * (size_t)call.maxStops + (size_t)kept[i].n_listed, stops_host + i * (size_t)call.maxStops);
+	return PP_OK;
+}
+
+/// The holds of a call written into the timetables of the plans of h (`plans`, `call`, `offsets`, `most`: retime_check's and retime_profiles').  Offsets and
+/// holds go up, the kernel rewrites the t column of the speed-profile group's rows in place, and every copy runs behind it on the holder's stream, which
+/// held_run synchronises once.  When the rows are wanted, the span of the rows buffer the call's plans lie in comes down in one copy, and the first N rows of
+/// every plan with a profile go on to the caller's array.
+int retime_plans(const HeldPlans& h, RetimeGroup& g, SpeedGroup& speed, const std::vector<ConflictArg>& plans, const RetimeCall& call, const std::vector<int32_t>& offsets,
+	int most, int n_holds, const pp_hold* holds, double* rows_host, pp_retime_result* results_host)
+{
+	if (h.n == 0)
+		return PP_OK;
+	pp_planner* const pl = h.pl;
+	PP_HIP_TRY(hipSetDevice(pl->map->ctx->device));
+	PP_HIP_TRY(held_grow(h, g.plans, h.rows, { { &g.offsets, (h.rows + 1) * 4 } }));
+	if (n_holds)
+		PP_HIP_TRY(held_grow(h, g.listed, (size_t)n_holds, { { &g.holds, (size_t)n_holds * sizeof(pp_hold) } }));
+	const size_t stride = (size_t)call.maxSamples * 3;
+	size_t lo = SIZE_MAX, hi = 0; // the rows of the speed-profile group that plans of this call with a profile use
+	if (rows_host)
+		for (const ConflictArg& a : plans)
+			if (a.nSamples > 0) {
+				lo = std::min(lo, (size_t)a.row);
+				hi = std::max(hi, (size_t)a.row + 1);
+			}
+	std::vector<double> staged(lo < hi ? (hi - lo) * stride : 0);
+	if (int rc = held_run(h, g.rec, plans, results_host, [&](const int32_t*) {
+			hipError_t e = hipMemcpyAsync(g.offsets, offsets.data(), offsets.size() * 4, hipMemcpyHostToDevice, h.stream);
+			if (e == hipSuccess && n_holds)
+				e = hipMemcpyAsync(g.holds, holds, (size_t)n_holds * sizeof(pp_hold), hipMemcpyHostToDevice, h.stream);
+			if (e == hipSuccess)
+				e = launch_retime(h.stream, call, h.n, most, g.rec.args.get(), g.offsets.get(), n_holds ? g.holds.get() : nullptr, speed.rows.get(), g.rec.out.get());
+			if (e == hipSuccess && !staged.empty())
+				e = hipMemcpyAsync(staged.data(), speed.rows.get() + lo * stride, staged.size() * 8, hipMemcpyDeviceToHost, h.stream);
+			return e;
+		}))
+		return rc;
+	if (!staged.empty())
+		for (size_t i = 0; i < (size_t)h.n; i++)
+			if (plans[i].nSamples > 0) {
+				const double* const from = staged.data() + ((size_t)plans[i].row - lo) * stride;
+				std::copy(from, from + (size_t)plans[i].nSamples * 3, rows_host + i * stride);
+			}
 	return PP_OK;
 }
 
@@ -2602,6 +2737,22 @@ int pp_planner_timetable(pp_planner* planner, int32_t n_queries, int32_t n_point
 	if (int rc = timetable_profiles(h, planner->speed, n_points, params, plans, call))
 		return rc;
 	return timetable_plans(h, planner->timetable, planner->speed, plans, call, values_host, plans_host, stops_host, results_host);
+}
+
+int pp_planner_retime(pp_planner* planner, int32_t n_queries, int32_t n_holds, const pp_hold* holds, double* rows_host, pp_retime_result* results_host)
+{
+	if (int rc = batch_check(planner, n_queries, "pp_pipeline_retime writes holds into its held tickets' timetables"))
+		return rc;
+	const HeldPlans h = batch_plans(planner, n_queries);
+	if (int rc = retime_check(h, n_holds, holds))
+		return rc;
+	std::vector<ConflictArg> plans;
+	std::vector<int32_t> offsets;
+	RetimeCall call;
+	int most = 0;
+	if (int rc = retime_profiles(h, planner->speed, n_holds, holds, plans, call, offsets, most))
+		return rc;
+	return retime_plans(h, planner->retime, planner->speed, plans, call, offsets, most, n_holds, holds, rows_host, results_host);
 }
 
 int pp_planner_locate(pp_planner* planner, int32_t n_queries, const double* poses_host, const double* from_length, const double* to_length, const pp_locate_params* params,

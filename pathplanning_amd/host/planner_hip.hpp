@@ -1022,6 +1022,7 @@ struct RRTStarParameters {
 /// Locate(tickets, poses, spacing) finds each vehicle on its held plan (pp_pipeline_locate): the arc length that windows Stamp, the errors a controller steers on.
 /// SpeedProfile(tickets, spacing, limits) gives the speed and the arrival time at every sample of a held plan (pp_pipeline_speed_profile): what a controller tracks at s.
 /// Timetable(tickets, values) asks that timetable at arc lengths or times and lists a plan's stops (pp_pipeline_timetable): the set-point and the lateness at the located s.
+/// Retime(tickets, holds) writes decided waits at stops into that timetable (pp_pipeline_retime): every service above then sees the schedule actually driven.
 class HybridAStarPipeline {
 public:
 	struct Result {
@@ -1861,6 +1862,49 @@ public:
 				u.tRemaining = r.t_remaining;
 				o.lookUps.push_back(u);
 			}
+		}
+		return out;
+	}
+	/// A wait to write into a timetable (pp_hold): `seconds` more (less, if negative) standing at the stop of row `row` of plan `plan` of the call's tickets
+	struct Hold {
+		int plan = 0, row = 0;
+		double seconds = 0.0;
+	};
+	/// What Retime says about one held plan (pp_retime_result)
+	struct Retimed {
+		enum class Status { Applied = 0, NoProfile = -1, NotAStop = -2, NegativeDwell = -3 };
+		Status status = Status::NoProfile;
+		int numHolds = 0, firstRow = -1;
+		int badHold = -1; // index into the call's holds of the first offending one (NotAStop, NegativeDwell)
+		double held = 0.0, durationBefore = 0.0, duration = 0.0;
+	};
+	/// Decided waits written into the timetables the LAST SpeedProfile call left on the device (pp_pipeline_retime; include/pp_hip.h has the definition):
+	/// a hold of w seconds at the stop of row r is t_k += w for every k >= r, in place, so that Conflicts, Timetable, CandidatePairs and the Deconflict
+	/// calls see it afterwards.  `holds` is strictly ascending in (plan, row), row in 1 .. N - 1.  A wait of d steps at row r that DeconflictWaits decided on
+	/// a lattice of step dt is { i, r, d * dt }.  A plan is retimed whole or not at all; the call accumulates, and a new SpeedProfile call replaces
+	/// everything.  Legal beside queries in flight.
+	std::vector<Retimed> Retime(const std::vector<uint64_t>& tickets, const std::vector<Hold>& holds)
+	{
+		for (uint64_t t : tickets)
+			HeldOf(t); // (throws for a ticket that is not held)
+		const size_t n = tickets.size();
+		std::vector<Retimed> out(n);
+		if (!m_pipe || n == 0)
+			return out;
+		std::vector<pp_hold> list;
+		for (const Hold& h : holds)
+			list.push_back(pp_hold { h.plan, h.row, h.seconds });
+		std::vector<pp_retime_result> r(n);
+		ppCheck(pp_pipeline_retime(m_pipe, (int32_t)n, tickets.data(), (int32_t)list.size(), list.empty() ? nullptr : list.data(), nullptr, r.data()));
+		for (size_t i = 0; i < n; i++) {
+			Retimed& o = out[i];
+			o.status = (Retimed::Status)r[i].status;
+			o.numHolds = r[i].n_holds;
+			o.firstRow = r[i].first_row;
+			o.badHold = r[i].bad_hold;
+			o.held = r[i].held;
+			o.durationBefore = r[i].duration_before;
+			o.duration = r[i].duration;
 		}
 		return out;
 	}

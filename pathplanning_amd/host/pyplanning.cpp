@@ -675,6 +675,35 @@ PYBIND11_MODULE(pyplanning, m)
 			"n_listed, s_first, s_last, duration), the list of its first max_stops stops as (row, s, t_arrive, t_depart), and per value a dict (status 0 inside the "
 			"profile, 1 before, 2 behind it, -1 no profile; row, edge, direction, s, t, v, a, ratio, kappa, pose, next_stop, s_to_stop, t_to_stop, t_remaining).",
 			py::arg("tickets"), py::arg("values"), py::arg("by") = "length", py::arg("max_stops") = 16)
+		.def("retime",
+			[](HybridAStarPipeline& h, const std::vector<uint64_t>& tickets, const std::vector<std::tuple<int, int, double>>& holds) {
+				std::vector<HybridAStarPipeline::Hold> list;
+				for (const auto& [plan, row, seconds] : holds) {
+					HybridAStarPipeline::Hold x;
+					x.plan = plan;
+					x.row = row;
+					x.seconds = seconds;
+					list.push_back(x);
+				}
+				py::list out;
+				for (const auto& r : h.Retime(tickets, list)) {
+					py::dict d;
+					d["status"] = (int)r.status;
+					d["n_holds"] = r.numHolds;
+					d["first_row"] = r.firstRow;
+					d["bad_hold"] = r.badHold;
+					d["held"] = r.held;
+					d["duration_before"] = r.durationBefore;
+					d["duration"] = r.duration;
+					out.append(d);
+				}
+				return out;
+			},
+			"decided waits written into the timetables the last speed_profile call left on the device: holds is a list of (plan, row, seconds), strictly ascending in "
+			"(plan, row), plan an index into tickets and row a stop of that plan's profile in 1 .. N - 1; seconds is added to every t_k with k >= row, in place, so that "
+			"conflicts, timetable, candidate_pairs and the deconflict calls see the wait.  Returns per ticket a dict (status 0 applied, -1 no profile, -2 a hold's row is "
+			"no stop, -3 a hold would make a dwell negative; n_holds, first_row, bad_hold, held, duration_before, duration).",
+			py::arg("tickets"), py::arg("holds"))
 		.def("get_path", &HybridAStarPipeline::GetPath, py::arg("ticket"))
 		.def("get_graph_search_path", &HybridAStarPipeline::GetGraphSearchPath, py::arg("ticket"))
 		.def("get_smoothing_status", &HybridAStarPipeline::GetSmoothingStatus, py::arg("ticket"))

@@ -12,7 +12,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import (RS_PATH_DTYPE, ConflictParams, ConflictResult, DelayParams, DelayResult, FootprintDisc, HybridParams, LocateParams, LocateResult, MapDesc, PairParams, PairSummary, PostResult, QueryResult, RevalidateResult,
+from ._lib import (RS_PATH_DTYPE, ConflictParams, ConflictResult, DelayParams, DelayResult, FootprintDisc, Hold, HybridParams, LocateParams, LocateResult, MapDesc, PairParams, PairSummary, PostResult, QueryResult, RetimeResult, RevalidateResult,
                    SmootherParams, SpeedProfileParams, SpeedProfileResult, StampParams, StampResult, TimetableParams, TimetablePlan, TimetableResult, TimetableStop, TrackResult, TrackSet, TrajectoryResult, WaitFixed, WaitParams, WaitPlace, WaitResult,
                    check, ptr)
 
@@ -705,9 +705,12 @@ class HybridAStarBatch:
         """Speeds and arrival times along the plans of the first n queries of the last batch: pp_planner_speed_profile, the batch form of
         HybridAStarPipeline.speed_profile, with the same arguments and return value."""
         n = len(self._results) if n_queries is None else int(n_queries)
-        return _speed_profile(n, from_length, to_length, v_start, v_end, max_samples, samples, limits,
-                              lambda a, b, vs, ve, sp, rows, out: self.lib.pp_planner_speed_profile(self.h, map_set.h if map_set is not None else None, n, ptr(a), ptr(b), ptr(vs),
-                                                                                                    ptr(ve), C.byref(sp), int(max_samples), ptr(rows), out))
+        self._profiled = None
+        out = _speed_profile(n, from_length, to_length, v_start, v_end, max_samples, samples, limits,
+                             lambda a, b, vs, ve, sp, rows, out: self.lib.pp_planner_speed_profile(self.h, map_set.h if map_set is not None else None, n, ptr(a), ptr(b), ptr(vs),
+                                                                                                   ptr(ve), C.byref(sp), int(max_samples), ptr(rows), out))
+        self._profiled = _profiled(range(n), out[0] if samples else out, max_samples)
+        return out
 
     def conflicts(self, t_start, n_queries=None, pairs=None, t_from=0.0, t_to=60.0, dt=0.1, margin=0.0, hold_before=False, hold_after=False, poses=False):
         """Space-time conflicts between the plans of the first n queries of the last batch on the timetables of the planner's last speed_profile call:
@@ -755,6 +758,13 @@ class HybridAStarBatch:
         HybridAStarPipeline.timetable, with the same arguments and return value."""
         n = len(self._results) if n_queries is None else int(n_queries)
         return _timetable(n, values, by, max_stops, lambda P, v, tp, pl, st, out: self.lib.pp_planner_timetable(self.h, n, P, ptr(v), C.byref(tp), ptr(pl), ptr(st), ptr(out)))
+
+    def retime(self, holds, n_queries=None, rows=False):
+        """Holds written into the timetables of the first n queries of the last batch: pp_planner_retime, the batch form of HybridAStarPipeline.retime,
+        with the same arguments (a hold's plan is a query index) and return value."""
+        n = len(self._results) if n_queries is None else int(n_queries)
+        return _retime(n, range(n), getattr(self, "_profiled", None), holds, rows,
+                       lambda H, hd, buf, out: self.lib.pp_planner_retime(self.h, n, H, ptr(hd), ptr(buf), ptr(out)))
 
     def certify_lattice(self, q):
         """SURVEY 7.3 H2 as a contract (pp_planner_certify_lattice): created nodes and logged lattice-line children of query q recomputed on
@@ -1097,9 +1107,12 @@ class HybridAStarPipeline:
         max_samples < 1, a NaN in a window, a v_start / v_end that is not finite and >= 0, a foreign map, or a map without a distance grid when
         clearance_gain > 0."""
         t = np.ascontiguousarray(tickets, dtype=np.uint64).reshape(-1)
-        return _speed_profile(len(t), from_length, to_length, v_start, v_end, max_samples, samples, limits,
-                              lambda a, b, vs, ve, sp, rows, out: self.lib.pp_pipeline_speed_profile(self.h, map_set.h if map_set is not None else None, len(t), ptr(t), ptr(a),
-                                                                                                     ptr(b), ptr(vs), ptr(ve), C.byref(sp), int(max_samples), ptr(rows), out))
+        self._profiled = None
+        out = _speed_profile(len(t), from_length, to_length, v_start, v_end, max_samples, samples, limits,
+                             lambda a, b, vs, ve, sp, rows, out: self.lib.pp_pipeline_speed_profile(self.h, map_set.h if map_set is not None else None, len(t), ptr(t), ptr(a),
+                                                                                                    ptr(b), ptr(vs), ptr(ve), C.byref(sp), int(max_samples), ptr(rows), out))
+        self._profiled = _profiled(t.tolist(), out[0] if samples else out, max_samples)
+        return out
 
     def conflicts(self, tickets, t_start, pairs=None, t_from=0.0, t_to=60.0, dt=0.1, margin=0.0, hold_before=False, hold_after=False, poses=False):
         """Do the vehicles of the completed, HELD queries `tickets`, each driving its plan on the timetable of the pipeline's last speed_profile call
@@ -1200,6 +1213,23 @@ class HybridAStarPipeline:
         t = np.ascontiguousarray(tickets, dtype=np.uint64).reshape(-1)
         return _timetable(len(t), values, by, max_stops,
                           lambda P, v, tp, pl, st, out: self.lib.pp_pipeline_timetable(self.h, len(t), ptr(t), P, ptr(v), C.byref(tp), ptr(pl), ptr(st), ptr(out)))
+
+    def retime(self, tickets, holds, rows=False):
+        """Write decided waits into the timetables of the completed, HELD queries `tickets` -- the (s, v, t) rows the last speed_profile() call left on the
+        device: pp_pipeline_retime, whose definition is in include/pp_hip.h.  `holds` lists (plan, row, seconds), strictly ascending in (plan, row): an
+        array of HOLD_DTYPE, [H, 3] numbers, or None / empty for none; plan indexes `tickets`, row is a stop of that plan's profile in 1 .. N - 1, and
+        seconds (may be negative) is added to every t_k with k >= row, in place.  wait_holds() turns the records of deconflict_waits() into such a
+        list.  Afterwards conflicts(), timetable(), candidate_pairs() and the deconflict calls see the waits; the call accumulates, and a new
+        speed_profile() call replaces everything.  A plan is retimed whole or not at all.  Legal beside queries in flight.
+        Returns a numpy record array of RETIME_DTYPE, one record per ticket (status 0 applied, -1 no profile, -2 a hold's row is no stop, -3 a hold
+        would make a dwell negative; n_holds, first_row, bad_hold, held, duration_before, duration) and, with rows=True, the list of (n_samples, 3)
+        arrays of (s, v, t) after the call, as speed_profile() returns them (this object's own speed_profile() call is where their layout is known from).
+        Raises PPError, with nothing launched, for everything timetable() refuses about the tickets and a missing speed profile, a plan index outside
+        the tickets, a row outside 1 .. N - 1 (a wait at the start is the plan's t_start), seconds that are not finite, a list that is not strictly
+        ascending and more than 2^10 holds for one plan."""
+        t = np.ascontiguousarray(tickets, dtype=np.uint64).reshape(-1)
+        return _retime(len(t), t.tolist(), getattr(self, "_profiled", None), holds, rows,
+                       lambda H, hd, buf, out: self.lib.pp_pipeline_retime(self.h, len(t), ptr(t), H, ptr(hd), ptr(buf), ptr(out)))
 
     def get_expanded_of(self, ticket):
         """expansion sequence (log_expansions=True) of a completed query polled with release=False"""
@@ -1467,6 +1497,63 @@ def _timetable(n, values, by, max_stops, call):
     out = np.zeros((max(n, 1), max(P, 1)), dtype=TIMETABLE_DTYPE)
     check(call(P, v if v.size else None, TimetableParams(0 if by == "length" else 1, M), plans, stops, out))
     return plans[:n].view(np.recarray), stops[:n, :max(M, 0)].view(np.recarray), out[:n, :P].view(np.recarray)
+
+
+# pp_hold and pp_retime_result as numpy records: what a retime call takes and returns
+HOLD_DTYPE = np.dtype([("plan", np.int32), ("row", np.int32), ("seconds", np.float64)])
+RETIME_DTYPE = np.dtype([("status", np.int32), ("n_holds", np.int32), ("first_row", np.int32), ("bad_hold", np.int32), ("held", np.float64), ("duration_before", np.float64),
+                         ("duration", np.float64)])
+assert HOLD_DTYPE.itemsize == C.sizeof(Hold) and RETIME_DTYPE.itemsize == C.sizeof(RetimeResult)
+
+
+def _profiled(keys, recs, max_samples):
+    """what a wrapper object remembers of its last speed_profile call for retime(rows=True): the stride of the rows and every plan's sample count"""
+    return int(max_samples), {int(k): (int(r.n_samples) if r.status == 0 else 0) for k, r in zip(keys, recs)}
+
+
+def hold_list(holds):
+    """the holds of a retime call as an array of HOLD_DTYPE: None or empty; an array of that dtype; or [H, 3] numbers (plan, row, seconds)"""
+    if holds is None:
+        return np.zeros(0, dtype=HOLD_DTYPE)
+    if isinstance(holds, np.ndarray) and holds.dtype == HOLD_DTYPE:
+        return np.ascontiguousarray(holds).reshape(-1)
+    rows = np.asarray(holds, dtype=np.float64).reshape(-1, 3)
+    if len(rows) and not (np.isfinite(rows[:, :2]).all() and (rows[:, :2] == np.rint(rows[:, :2])).all() and (np.abs(rows[:, :2]) < 2 ** 31).all()):
+        raise ValueError("a hold is (plan, row, seconds) with plan and row in int32")
+    out = np.zeros(len(rows), dtype=HOLD_DTYPE)
+    out["plan"], out["row"], out["seconds"] = rows[:, 0], rows[:, 1], rows[:, 2]
+    return out
+
+
+def _retime(n, keys, profiled, holds, rows, call):
+    """the hold list of a retime call, the call, its records as one numpy record array and (rows=True) each plan's (s, v, t) rows after it"""
+    hd = hold_list(holds)
+    if rows and n and profiled is None:
+        raise ValueError("rows=True needs the layout of the rows: call this object's speed_profile() first")
+    buf = np.zeros((n, profiled[0] if profiled else 0, 3)) if rows else None
+    out = np.zeros(max(n, 1), dtype=RETIME_DTYPE)
+    check(call(len(hd), hd if len(hd) else None, buf if rows and buf.size else None, out))
+    recs = out[:n].view(np.recarray)
+    if not rows:
+        return recs
+    return recs, [buf[i, :profiled[1].get(int(k), 0)].copy() if recs[i].status != -1 else np.zeros((0, 3)) for i, k in enumerate(keys)]
+
+
+def wait_holds(results, dt, t_start):
+    """The record array of a deconflict_waits() call as what commits it: (holds, t_start').  A scheduled vehicle (status 0 or 2) that waits
+    wait_steps > 0 steps at a stop (place >= 0) becomes the hold (i, row, wait_steps * dt) for retime(); one that waits at its start gets the
+    record's effective t_start; every other vehicle keeps its t_start.  After retime(tickets, holds) the calls that take start times see the
+    schedule the call decided under t_start', and a next deconflict_waits() round needs no `fixed` entry for these vehicles."""
+    n = len(results)
+    ts = np.array(_per_plan(t_start, n), dtype=np.float64).reshape(-1)
+    bound = (results["status"] == 0) | (results["status"] == 2)
+    at_stop = bound & (results["place"] >= 0) & (results["wait_steps"] > 0)
+    at_start = bound & (results["place"] == -1)
+    ts[at_start] = results["t_start"][at_start]
+    k = np.flatnonzero(at_stop)
+    holds = np.zeros(len(k), dtype=HOLD_DTYPE)
+    holds["plan"], holds["row"], holds["seconds"] = k, results["row"][k], results["wait_steps"][k].astype(np.float64) * np.float64(dt)
+    return holds, ts
 
 
 # pp_track_result as a numpy record: a deconflict_tracks call returns an [n, M] array of these
